@@ -14,8 +14,11 @@ Workloads (BASELINE.json configs[1..4]; --config N is an alias, N counted from 1
   --workload gcp       config 3: kat gcp, 100 M reads from a 200 Mbp genome, k = 27
   --workload comp-rr   config 5: kat comp, reads library 1 vs reads library 2 (75 M + 75 M reads per GPU), k = 31
 
-  python bench.py                                   # N = 1, config 4 at full size (+ `workloads`: configs 2, 3, 5's per-GPU shard, 3 steps each;
-                                                    #   + `end_to_end`: files -> files, config 4 at full size when /dev/shm has the room)
+  python bench.py                                   # N = 1, config 4 at full size: set up, warm up, the timed steps, the line -- nothing else
+  python bench.py --full                            # the same line + `cpu_baseline` + `workloads`: configs 2, 3, 5's per-GPU shard, 3 steps each
+                                                    #   + `end_to_end`: files -> files, config 4 at full size when /dev/shm has the room
+                                                    #   (+ hist / gcp: the sum-of-counts check, one more untimed step)
+  python bench.py --dump-outputs DIR                # also write what the last timed step computed as DIR/<name>.npy (float64)
   python bench.py --gpus 8                          # launches its own 8 ranks (torch.distributed.run, one per GPU, RCCL); weak scaling:
                                                     #   300 M reads PER GPU
   python bench.py --gpus 8 --scaling strong         # the metric's own config: 300 M reads IN TOTAL, sharded over the ranks
@@ -99,6 +102,10 @@ def parse_args():
                     "gzip's level 6 is what takes the time, ~1.4 s per million reads on the 16 CPUs a GPU box grants; 150000000, half of config 4: profiles/r06_e2e_gz.txt)")
     ap.add_argument("--e2e-gz-level", type=int, default=6, help="deflate level of the .fastq.gz files (6: gzip's default)")
     ap.add_argument("--e2e-slice", action="store_true", help="files -> files on the --e2e-reads slice even when /dev/shm has room for the whole config")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: cpu_baseline, the workloads object, the end-to-end legs and hist / gcp's "
+                    "sum-of-counts check (the --no-* / --with-* / --e2e-* options shape these; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (the reducer's arrays as the caller "
+                    "receives them, and the tables' distinct k-mers) as DIR/<name>.npy in float64")
     a = ap.parse_args()
     if a.config is not None:
         if a.workload is not None and a.workload != CONFIG_ALIAS[a.config]:
@@ -217,7 +224,7 @@ def main():
     # ---- the files -> output files leg goes first: a child process that allocates right after this one has freed a hundred GB
     # of HBM would spend seconds in the driver's scrubbing of that memory -- an artefact of benchmarking, not of the tool ----
     e2e = None
-    if rank == 0 and world == 1 and not a.no_e2e:
+    if rank == 0 and world == 1 and a.full and not a.no_e2e:
         try:
             e2e = end_to_end(eng, a, a.k, a.read_len)
         except Exception as ex:                            # the engine number stands on its own; say why the leg is missing
@@ -226,17 +233,17 @@ def main():
 
     ctx = {"rank": rank, "world": world, "comm": comm, "dist": dist, "transport": transport, "comm_info": comm_info, "torch": torch}
     line, ok, what = measure(eng, a, ctx, want_cpu=True)
-    all_ok = ok
+    all_ok = ok is not False                                # (None: hist / gcp without --full, not checked)
     if rank == 0:
         line["end_to_end_gz"] = e2e.pop("gz", None) if isinstance(e2e, dict) else None      # the same leg from .fastq.gz files (one gzip member each)
         line["end_to_end"] = e2e
     # ---- the other single-GPU configs of BASELINE.json, briefly, in the same line: configs 2, 3 and config 5's per-GPU shard ----
-    if world == 1 and a.workload == "comp" and (a.default_size or a.with_workloads) and not a.no_workloads:
+    if world == 1 and a.full and a.workload == "comp" and (a.default_size or a.with_workloads) and not a.no_workloads:
         extra = {}
         for wl in ("hist", "gcp", "comp-rr"):
             eng.release_scratch()                           # the previous workload's parked tables and arena go back to the driver
             b = copy.copy(a)
-            b.workload, b.steps, b.warmup, b.phases = wl, 3, 1, False
+            b.workload, b.steps, b.warmup, b.phases, b.dump_outputs = wl, 3, 1, False, None
             b.reads, b.genome, b.k, _ = WORKLOADS[wl]
             if not a.default_size:                          # (--with-workloads at a reduced size)
                 b.reads, b.genome = min(b.reads, a.reads), min(b.genome, a.genome)
@@ -418,6 +425,8 @@ def measure(eng, a, ctx, want_cpu):
     dt = allmax(dt)
     d1_local, cap1, cap2 = results["distinct1_local"], results["cap1"], results.get("cap2", 0)
     distinct1, distinct2 = allsum(results["distinct1"]), allsum(results.get("distinct2", 0))
+    if a.dump_outputs and rank == 0:                            # the last timed step's results, before anything below runs another step
+        dump_outputs(a.dump_outputs, wl, results["out"], [distinct1] + ([distinct2] if two_tables else []))
     exch = None
     if comm is not None:                                        # the exchange of the TIMED steps: slowest rank per phase, bytes of all ranks
         exch = {"max_over_ranks_ms_per_step": {q: round(allmax(comm_after[q] - comm_before[q]) / a.steps, 3) for q in ("extract_ms", "exchange_ms", "merge_ms", "allreduce_ms")},
@@ -440,6 +449,8 @@ def measure(eng, a, ctx, want_cpu):
         cc = out[1]
         ok = int(cc[0]) == world * inst_reads and int(cc[1]) == inst2_total
         what = "comp counters: hash1 total %d (expected %d), hash2 total %d (expected %d)" % (int(cc[0]), world * inst_reads, int(cc[1]), inst2_total)
+    elif not a.full:
+        ok, what = None, "not checked: the sum of counts takes an untimed step of its own (--full)"
     else:
         step(verify=True)                                   # once more, untimed, with the table's sum of counts
         barrier()
@@ -529,7 +540,7 @@ def measure(eng, a, ctx, want_cpu):
             v["frac"] = round(v["achieved_GBps"] / HBM_PEAK_GBPS, 4) if v["achieved_GBps"] else None
         kernels_ms = {n: round(v["ms"] / a.steps, 3) for n, v in prof.items() if v["launches"]}
         cpu = None
-        if want_cpu and not a.no_cpu_baseline and world == 1 and k <= 32:      # the host-core baseline is an N = 1 figure (the multi-threaded oracle port is one-word)
+        if want_cpu and a.full and not a.no_cpu_baseline and world == 1 and k <= 32:      # the host-core baseline is an N = 1 figure (the multi-threaded oracle port is one-word)
             cpu = cpu_baseline(eng, a, k, L)
         _, _, _, wl_name = WORKLOADS[wl]
         per = "in total, sharded over %d GPUs" % world if strong else "per GPU"
@@ -548,13 +559,27 @@ def measure(eng, a, ctx, want_cpu):
             "config": {"workload": desc, "reads_per_gpu": n_reads * (2 if wl == "comp-rr" else 1), "genome_bp": a.genome, "k": k,
                        "parallelism": "reads sharded x%d, owner-partitioned merge: %s" % (world, ctx["transport"]) if world > 1 else "single GPU", "comm": ctx["comm_info"]},
             "kmer_instances": total_instances, "distinct_table1": distinct1, "distinct_table2": distinct2 if two_tables else None,
-            "result_accounts_for_every_kmer": bool(ok), "result_check": what,
+            "result_accounts_for_every_kmer": None if ok is None else bool(ok), "result_check": what,
             "kernel_ms_per_step": kernels_ms,
             "roofline": roof, "reducers": red, "cpu_baseline": cpu,
         }
         if exch is not None:
             line["exchange"] = exch
     return line, ok, what
+
+
+DUMP_NAMES = {"comp": ("comp_main_matrix", "comp_counters", "comp_spectra"), "comp-rr": ("comp_main_matrix", "comp_counters", "comp_spectra"),
+              "hist": ("hist",), "gcp": ("gcp_matrix",)}
+
+
+def dump_outputs(path, wl, out, distinct):
+    """--dump-outputs: the reducer's arrays of one step (u64 counts, exact in float64) + the distinct k-mers of its table(s), as .npy files
+    (config 4: ~8 MB, the 1001 x 1001 main matrix)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(zip(DUMP_NAMES[wl], out))
+    arrays["distinct_kmers"] = np.asarray(distinct, dtype=np.uint64)
+    for name, x in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(x).astype(np.float64))
 
 
 def cpu_baseline(eng, a, k, L):

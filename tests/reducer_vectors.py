@@ -3,11 +3,11 @@ oracle and the HIP path to it: the cases, the way the reference's pieces are dri
 import hashlib
 import math
 import os
-import subprocess
+
+from tests import refcalls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-JF_REF = os.path.join(ROOT, "oracle", "_ref", "jf_ref")
-KAT_REF = os.path.join(ROOT, "oracle", "_ref", "kat_ref_parts")
+JF_REF, KAT_REF = refcalls.JF_REF, refcalls.KAT_REF
 GOLDEN = os.path.join(ROOT, "tests", "golden", "reducer_vectors.json")
 R1, R2 = "ecoli_r1.1K.fastq", "ecoli_r2.1K.fastq"
 
@@ -26,15 +26,22 @@ def digest(b):
     return hashlib.sha256(b if isinstance(b, bytes) else b.encode()).hexdigest()
 
 
-def run(binary, args, stdin=None):
-    r = subprocess.run([binary] + [str(a) for a in args], input=stdin, capture_output=True, timeout=600)
-    assert r.returncode == 0, (binary, args, r.returncode, r.stderr[:200])
-    return r.stdout
+def run(binary, args, stdin=None, rebuild=None):
+    rc, out = refcalls.run(binary, args, stdin, timeout=600, rebuild=rebuild)       # (replayed where oracle/_ref is not built)
+    assert rc == 0, (binary, args, rc)
+    return out
+
+
+def oracle_text(path, k):
+    """The oracle's "<k-mer> <count>" lines for the file (canonical): stands in for the reference's where only their digest is stored."""
+    from oracle import koracle as ko
+    keys, counts = ko.Table(k, True).count_files([path]).dump_sorted()
+    return "".join("%s %d\n" % (ko.decode(int(a), k), int(b)) for a, b in zip(keys, counts)).encode()
 
 
 def ref_counts(path, k):
     """{k-mer string: count} as the reference's parser + mer_iterator deliver them (canonical)."""
-    out = run(JF_REF, ["kmers", k, 1, path])
+    out = run(JF_REF, ["kmers", k, 1, path], rebuild=lambda: oracle_text(path, k))
     return {a.decode(): int(b) for a, b in (l.split() for l in out.splitlines())}
 
 
@@ -75,7 +82,8 @@ def reference_comp(refdata, k, s1, s2, b1, b2):
 def reference_gcp(refdata, k, scale, bins):
     h = ref_counts(os.path.join(refdata, R1), k)
     keys = list(h)
-    gc = [int(l.split()[1]) for l in run(KAT_REF, ["strutils"], ("\n".join(keys) + "\n").encode()).decode().splitlines()]      # the reference's gcCount
+    said = lambda: "".join("%d %d\n" % (all(ch in "ACGTacgt" for ch in w), sum(ch in "GCgc" for ch in w)) for w in keys).encode()   # (validKmer, gcCount)
+    gc = [int(l.split()[1]) for l in run(KAT_REF, ["strutils"], ("\n".join(keys) + "\n").encode(), rebuild=said).decode().splitlines()]      # the reference's gcCount
     cells = {}
     for key, g in zip(keys, gc):
         c = h[key]

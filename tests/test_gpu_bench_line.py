@@ -26,7 +26,7 @@ def _bench(args, env_extra=None, timeout=900):
 
 
 def test_single_gpu_line_carries_workloads_and_a_checked_end_to_end_leg():
-    line = _bench(SMALL + ["--e2e-reads", "2000000", "--with-workloads"], {"KATGPU_PGZ_CHUNK": str(1 << 20)})
+    line = _bench(SMALL + ["--full", "--e2e-reads", "2000000", "--with-workloads"], {"KATGPU_PGZ_CHUNK": str(1 << 20)})
     assert line["result_accounts_for_every_kmer"] and line["n_gpus"] == 1 and line["scaling"] == "weak"
     assert line["roofline"]["bound"] == "hbm" and 0 < line["roofline"]["frac"] < 1
     e = line["end_to_end"]
@@ -49,7 +49,7 @@ def test_single_gpu_line_carries_workloads_and_a_checked_end_to_end_leg():
 
 @pytest.mark.parametrize("wl", ["hist", "comp-rr"])
 def test_end_to_end_check_of_the_other_tools(wl):
-    line = _bench(["--workload", wl] + SMALL + ["--e2e-reads", "2000000"])
+    line = _bench(["--workload", wl, "--full"] + SMALL + ["--e2e-reads", "2000000"])
     e = line["end_to_end"]
     assert e.get("error") is None and e["result_check"] is True, e
 

@@ -400,14 +400,11 @@ def test_count_files_bgzf(engine, ko, refdata, tmp_path, monkeypatch):
         t.free()
 
 
-JF_REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "jf_ref")
-
-
-@pytest.mark.skipif(not os.access(JF_REF, os.X_OK), reason="oracle/_ref not built (no /root/reference at build time)")
 def test_hip_table_against_the_reference_parser_directly(engine, ko, refdata, tmp_path):
     """No oracle in between: the HIP table's (k-mer, count) dump equals what the REAL Jellyfish 2.2.0 parser + mer_iterator of the
-    reference deliver (oracle/_ref/jf_ref, compiled from /root/reference's sources) for the same files."""
-    import subprocess
+    reference deliver (oracle/_ref/jf_ref, compiled from the reference's sources; replayed where it is not built: tests/refcalls.py)
+    for the same files."""
+    from tests import refcalls
     from tests.test_oracle_vs_naive import write_messy_fasta, write_messy_fastq
     rng = np.random.default_rng(33)
     fa, fq = tmp_path / "m.fa", tmp_path / "mm.fq"
@@ -417,10 +414,10 @@ def test_hip_table_against_the_reference_parser_directly(engine, ko, refdata, tm
               [str(fa), str(fq)]]
     for paths in groups:
         for k, canonical in ((27, True), (31, False), (11, True)):
-            out = subprocess.run([JF_REF, "kmers", str(k), str(int(canonical))] + paths, capture_output=True, timeout=300)
-            assert out.returncode == 0
             t = engine.count(paths, k, canonical)
             keys, counts = t.dump_sorted()
             got = "".join("%s %d\n" % (ko.decode(int(a), k), int(b)) for a, b in zip(keys, counts)).encode()
-            assert got == out.stdout, (paths, k, canonical)
+            rc, out = refcalls.run(refcalls.JF_REF, ["kmers", k, int(canonical)] + paths, rebuild=lambda: got)
+            assert rc == 0
+            assert got == out, (paths, k, canonical)
             t.free()

@@ -228,9 +228,10 @@ def test_sect_and_cold_cli_wide(ko, refdata, tmp_path):
 
 
 def test_jf_dump_and_load_wide(engine, ko, refdata, tmp_path):
-    """-d dumps and .jf inputs at k > 32: dump -> (the reference's reader, when oracle/_ref is there) -> load gives the table back;
+    """-d dumps and .jf inputs at k > 32: dump -> the reference's reader (replayed where oracle/_ref is not built) -> load gives the table back;
     the CLI counts from the .jf what it counts from the reads."""
     import subprocess
+    from tests import refcalls
     from tests.test_oracle_vs_reference import JF_REF, ref, parse_jfread
     r1 = os.path.join(refdata, "ecoli_r1.1K.fastq")
     for k, canonical in ((45, True), (63, False)):
@@ -241,11 +242,10 @@ def test_jf_dump_and_load_wide(engine, ko, refdata, tmp_path):
         assert (back.k, back.canonical) == (k, canonical)
         ot = ko.WideTable(k, canonical).count_files([r1])
         assert_same_wide(back, ot)
-        if os.access(JF_REF, os.X_OK):
-            rc, out = ref(JF_REF, ["jfread", p])
-            assert rc == 0
-            hdr, recs = parse_jfread(out)
-            assert hdr["key_len"] == str(2 * k) and len(recs) == ot.distinct
+        rc, out = ref(JF_REF, ["jfread", p], rebuild=lambda: refcalls.jfread_text(p))
+        assert rc == 0
+        hdr, recs = parse_jfread(out)
+        assert hdr["key_len"] == str(2 * k) and len(recs) == ot.distinct
     exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "kat_amd", "bin", "katgpu")
     run = lambda args: subprocess.run([exe] + args, cwd=tmp_path, capture_output=True, text=True, timeout=300)
     r = run(["hist", "-m", "41", "-d", "-o", "a", r1])

@@ -151,14 +151,11 @@ def test_wide_sect_and_cold_vs_naive(ko, refdata, tmp_path, k, canonical):
         assert (tmp_path / "wc-stats.tsv").read_bytes() == naive.cold(counts, canonical, counts_of(ko, asm), not canonical, k, p)
 
 
-SEQAN_REF = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "seqan_ref")
-
-
-@pytest.mark.skipif(not os.access(SEQAN_REF, os.X_OK), reason="oracle/_ref not built (no /root/reference at build time)")
 def test_record_reader_against_the_real_seqan(tmp_path):
     """The records `kat sect` / `kat cold` see: tests/naive.py's statement of the SeqAn 2.0.0 reader against the library itself
-    (oracle/_ref/seqan_ref, compiled from the reference's vendored headers), on every edge case used above."""
-    import subprocess
+    (oracle/_ref/seqan_ref, compiled from the reference's vendored headers; replayed where it is not built: tests/refcalls.py), on
+    every edge case used above."""
+    from tests import refcalls
     paths, fa = make_cases(tmp_path)
     extra = {"mid.fasta": b"leading junk\r\n>r0 desc\r\nACGT\r\nAC GT\r\n>r1\r\nTT>GG\r\n\r\n", "two.fq": b"@a\nACGT\n+\n@III\n@b\nGG\nTT\n+b\n@@\n@@\n",
              "empty.fa": b"", "x.fna": b">x\nACGT\n", "nomarker.fa": b"no marker\n", "noplus.fq": b"@a\nACGT\n"}
@@ -166,10 +163,10 @@ def test_record_reader_against_the_real_seqan(tmp_path):
         (tmp_path / name).write_bytes(data)
         paths.append(str(tmp_path / name))
     for p in paths:
-        r = subprocess.run([SEQAN_REF, p], capture_output=True, timeout=60)
+        rc, out = refcalls.run(refcalls.SEQAN_REF, [p], timeout=60)
         try:
             want = b"".join(b"%d %s\n%d %s\n" % (len(n), n, len(s), s) for n, s in naive.seqan_records(p))
         except ValueError as e:
-            assert r.returncode == 5 and r.stdout.startswith(b"EXCEPTION " + str(e).encode()[:20]), (p, r.stdout[:200])
+            assert rc == 5 and out.startswith(b"EXCEPTION " + str(e).encode()[:20]), (p, out[:200])
             continue
-        assert r.returncode == 0 and r.stdout == want, p
+        assert rc == 0 and out == want, p

@@ -3,36 +3,34 @@
 oracle/Makefile (`make ref`) compiles, from the sources where they lie under /root/reference and with nothing stubbed,
   oracle/_ref/jf_ref         Jellyfish 2.2.0's parser + mer_iterator + mer_dna + file_header / binary_reader
   oracle/_ref/kat_ref_parts  KAT's CompCounters, distance metrics, SparseMatrix and str_utils
-(the tool drivers and Jellyfish's hash array need the autoconf-generated config.h and do not build).  These tests run
-wherever the two binaries exist -- in the build container, and on the GPU box, where the prebuilt binaries travel -- and
-tests/golden/reference_vectors.json holds what they printed for the fixed inputs (tests/golden/make_reference_vectors.py), so
-that the pin survives a checkout without /root/reference."""
+(the tool drivers and Jellyfish's hash array need the autoconf-generated config.h and do not build).  Where the two binaries
+exist the tests run them; elsewhere tests/refcalls.py replays what they printed for the same inputs (tests/golden/ref_calls/), and
+tests/golden/reference_vectors.json holds the digests of their answers for the fixed inputs (tests/golden/make_reference_vectors.py),
+so that the pin survives a checkout without the reference's sources."""
 import gzip
 import hashlib
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import kat_amd
+from tests import refcalls
 from tests.test_oracle_vs_naive import write_messy_fasta, write_messy_fastq
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-JF_REF = os.path.join(ROOT, "oracle", "_ref", "jf_ref")
-KAT_REF = os.path.join(ROOT, "oracle", "_ref", "kat_ref_parts")
+JF_REF, KAT_REF = refcalls.JF_REF, refcalls.KAT_REF
 GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_vectors.json")
-have_ref = pytest.mark.skipif(not (os.access(JF_REF, os.X_OK) and os.access(KAT_REF, os.X_OK)), reason="oracle/_ref not built (no /root/reference)")
 
 
-def ref(binary, args, stdin=None):
-    r = subprocess.run([binary] + [str(a) for a in args], input=stdin, capture_output=True, timeout=300)
-    return r.returncode, r.stdout
+def ref(binary, args, stdin=None, rebuild=None):
+    return refcalls.run(binary, args, stdin, rebuild=rebuild)
 
 
-def ref_kmers(paths, k, canonical):
-    rc, out = ref(JF_REF, ["kmers", k, int(canonical)] + list(paths))
+def ref_kmers(paths, k, canonical, rebuild=None):
+    """rebuild: the text the caller expects (tests/refcalls.py: stands in only where its digest is the reference's)."""
+    rc, out = ref(JF_REF, ["kmers", k, int(canonical)] + list(paths), rebuild=rebuild)
     assert rc == 0, (paths, rc)
     return out
 
@@ -61,7 +59,7 @@ def fixed_cases(refdata):
 
 
 def test_golden_reference_vectors(ko, refdata):
-    """The committed digests of what the reference's parser + iterator deliver for its own test data: needs no _ref."""
+    """The committed digests of what the reference's parser + iterator deliver for its own test data: compared with the oracle."""
     gold = json.load(open(GOLDEN))
     for tag, paths, k, c in fixed_cases(refdata):
         got = oracle_kmers(ko, paths, k, c)
@@ -71,15 +69,13 @@ def test_golden_reference_vectors(ko, refdata):
     assert gold["kmers"]["sect_test.fa:k27:C"]["distinct"] == 26
 
 
-@have_ref
-def test_reference_vectors_are_current(refdata):
+def test_reference_vectors_are_current(ko, refdata):
     gold = json.load(open(GOLDEN))
     for tag, paths, k, c in fixed_cases(refdata):
-        out = ref_kmers(paths, k, c)
+        out = ref_kmers(paths, k, c, rebuild=lambda: oracle_kmers(ko, paths, k, c))
         assert gold["kmers"][tag] == {"sha256": digest(out), "distinct": out.count(b"\n"), "total": sum(int(l.split()[1]) for l in out.splitlines())}, tag
 
 
-@have_ref
 @pytest.mark.parametrize("seed", range(3))
 def test_count_semantics_on_messy_files(ko, tmp_path, seed):
     """Multi-line records, blank lines, IUPAC / lower case / '-', qualities that start with '@' or '+', gzip: the oracle's
@@ -92,10 +88,10 @@ def test_count_semantics_on_messy_files(ko, tmp_path, seed):
     write_messy_fastq(str(gz), rng)
     for k, c in ((27, True), (11, False), (32, True), (3, False)):
         for paths in ([str(fa)], [str(fq)], [str(fqm)], [str(gz)], [str(fq), str(fa)]):
-            assert oracle_kmers(ko, paths, k, c) == ref_kmers(paths, k, c), (paths, k, c)
+            got = oracle_kmers(ko, paths, k, c)
+            assert got == ref_kmers(paths, k, c, rebuild=lambda: got), (paths, k, c)
 
 
-@have_ref
 def test_count_semantics_on_edge_files(ko, tmp_path):
     cases = {
         "header_only.fa": b">x\n",
@@ -112,10 +108,10 @@ def test_count_semantics_on_edge_files(ko, tmp_path):
         p = tmp_path / name
         p.write_bytes(data)
         for k, c in ((4, True), (7, False)):
-            assert oracle_kmers(ko, [str(p)], k, c) == ref_kmers([str(p)], k, c), (name, k, c)
+            got = oracle_kmers(ko, [str(p)], k, c)
+            assert got == ref_kmers([str(p)], k, c, rebuild=lambda: got), (name, k, c)
 
 
-@have_ref
 def test_mer_dna_arithmetic(ko):
     rng = np.random.default_rng(9)
     for k in (1, 2, 5, 16, 27, 31, 32):
@@ -138,12 +134,11 @@ def parse_jfread(out):
     return hdr, recs
 
 
-@have_ref
 def test_jf_files_as_the_reference_reads_them(ko, refdata, tmp_path):
     """(a) the reference's fixture: our reader sees what the reference's reader sees; (b) a file written by the PRODUCT's writer is
     read back by the reference's file_header + binary_reader with every field, record and hash position where it must be."""
     fixture = os.path.join(refdata, "ecoli.header.jf27")
-    rc, out = ref(JF_REF, ["jfread", fixture])
+    rc, out = ref(JF_REF, ["jfread", fixture], rebuild=lambda: refcalls.jfread_text(fixture))
     assert rc == 0
     hdr, recs = parse_jfread(out)
     t = ko.Table.from_jf(fixture)
@@ -161,7 +156,7 @@ def test_jf_files_as_the_reference_reads_them(ko, refdata, tmp_path):
         cc[0] = (1 << 40)                                              # saturates at the 4-byte counter (quirk B12)
         p = str(tmp_path / ("w%d.jf" % k))
         kat_amd.jf_write_records(p, k, canonical, kk, cc)
-        rc, out = ref(JF_REF, ["jfread", p])
+        rc, out = ref(JF_REF, ["jfread", p], rebuild=lambda: refcalls.jfread_text(p))
         assert rc == 0, (k, rc)
         hdr, recs = parse_jfread(out)
         assert (hdr["key_len"], hdr["counter_len"], hdr["canonical"], hdr["format"]) == (str(2 * k), "4", str(int(canonical)), "binary/sorted")
@@ -178,7 +173,7 @@ def test_jf_files_as_the_reference_reads_them(ko, refdata, tmp_path):
         cc[0] = (1 << 40)
         p = str(tmp_path / ("w%d.jf" % k))
         kat_amd.jf_write_records_wide(p, k, canonical, [x >> 64 for x in kk], [x & M for x in kk], cc)
-        rc, out = ref(JF_REF, ["jfread", p])
+        rc, out = ref(JF_REF, ["jfread", p], rebuild=lambda: refcalls.jfread_text(p))
         assert rc == 0, (k, rc)
         hdr, recs = parse_jfread(out)
         assert (hdr["key_len"], hdr["counter_len"], hdr["canonical"], hdr["format"]) == (str(2 * k), "4", str(int(canonical)), "binary/sorted")
@@ -193,7 +188,6 @@ def test_jf_files_as_the_reference_reads_them(ko, refdata, tmp_path):
         assert ei.value.code == 6
 
 
-@have_ref
 def test_comp_counters_text_and_distances(ko, tmp_path):
     """CompCounters::printCounts (with its five distance metrics, twice) byte for byte, on random counters and spectra."""
     rng = np.random.default_rng(12)
@@ -218,7 +212,6 @@ def test_comp_counters_text_and_distances(ko, tmp_path):
             assert all((g != g and w != w) or abs(g - w) <= 1e-5 * max(1.0, abs(w)) for g, w in zip(got, want)), (got, want)
 
 
-@have_ref
 def test_comp_counter_arithmetic(ko):
     """update{Hash1,Hash2,Shared}Counters applied as Comp::compareSlice applies them == the oracle's ko_comp on the same tables."""
     rng = np.random.default_rng(3)
@@ -242,7 +235,6 @@ def test_comp_counter_arithmetic(ko):
         assert np.array_equal(np.array(rows[1:5], np.uint64), sp)
 
 
-@have_ref
 def test_sparse_matrix_and_str_utils(ko):
     rc, out = ref(KAT_REF, ["matrix", 4, 6], b"0 0 5\n3 5 11\n3 5 1\n4 2 1000\n2 6 77\n1 3 9\n")     # (4,2) and (2,6) lie outside a 4 x 6 matrix
     assert out == b"12\n5 0 0 0 0 0\n0 0 0 9 0 0\n0 0 0 0 0 0\n0 0 0 0 0 12\n"
@@ -258,7 +250,6 @@ def test_sparse_matrix_and_str_utils(ko):
     assert gcs.tolist() == [2, -1, -1, -1, -1, 2, 2, 2, 2, 2] and counts.tolist()[0] == 3 and counts.tolist()[5] == 3
 
 
-@have_ref
 def test_matrix_files_as_the_reference_reads_them(ko, refdata, tmp_path):
     """The .mx files of `kat gcp` and `kat comp` (oracle writers == the product's CLI bytes, tests/test_gpu_cli.py) go through the
     reference's own readers: matrix_metadata_extractor finds every key, SparseMatrix(path) loads the body with the right shape,
@@ -282,7 +273,6 @@ def test_matrix_files_as_the_reference_reads_them(ko, refdata, tmp_path):
     assert lines[7].split() == ["60", "40", str(int(mx.max())), str(int(mx.sum()))]
 
 
-@have_ref
 def test_product_ingest_against_the_reference_parser(tmp_path):
     """The PRODUCT's host ingest (kat_amd.parse_file: what katgpu_count ships to the GPU), counted window by window in Python,
     is the k-mer multiset of the reference's parser + iterator -- no oracle in between."""
@@ -299,10 +289,9 @@ def test_product_ingest_against_the_reference_parser(tmp_path):
         for k, canonical in ((6, True), (13, False)):
             got = naive.count_string(stream, k, canonical)
             text = "".join("%s %d\n" % (w, c) for w, c in sorted(got.items())).encode()
-            assert text == ref_kmers([str(p)], k, canonical), (p, k, canonical)
+            assert text == ref_kmers([str(p)], k, canonical, rebuild=lambda: text), (p, k, canonical)
 
 
-@have_ref
 def test_documented_deviations_on_truncated_fastq(ko, tmp_path):
     """DESIGN.md 4, "Known deviations": what the reference really does there.  Its producer thread throws "Invalid fastq sequence"
     and the pool swallows it together with the buffer being filled (here the whole 4 KB file): no k-mers, exit status 0.  The
@@ -317,13 +306,12 @@ def test_documented_deviations_on_truncated_fastq(ko, tmp_path):
     assert ei.value.code == 4
 
 
-def ref_kmers_trim(paths, k, canonical, trims):
-    rc, out = ref(JF_REF, ["kmerst", k, int(canonical), ",".join(map(str, trims))] + list(paths))
+def ref_kmers_trim(paths, k, canonical, trims, rebuild=None):
+    rc, out = ref(JF_REF, ["kmerst", k, int(canonical), ",".join(map(str, trims))] + list(paths), rebuild=rebuild)
     assert rc == 0
     return out
 
 
-@have_ref
 def test_five_prime_trim_against_the_reference_parser(ko, tmp_path):
     """--5ptrim through the trim5p_list constructor KAT added to the vendored parser.  FASTQ: identical.  FASTA: identical while
     the file fits one of the parser's 4096-byte buffers; beyond that the reference re-applies the trim at EVERY buffer fill, in the
@@ -342,9 +330,9 @@ def test_five_prime_trim_against_the_reference_parser(ko, tmp_path):
         return "".join("%s %d\n" % (ko.decode(int(a), k), int(b)) for a, b in zip(keys, counts)).encode()
     for trim in (1, 3, 10):
         for k, c in ((7, True), (21, False)):
-            assert oracle([str(fq)], k, c, [trim]) == ref_kmers_trim([str(fq)], k, c, [trim])
-            assert oracle([str(small)], k, c, [trim]) == ref_kmers_trim([str(small)], k, c, [trim])
-            assert oracle([str(fq), str(small)], k, c, [trim, 0]) == ref_kmers_trim([str(fq), str(small)], k, c, [trim, 0])
+            for paths, trims in (([str(fq)], [trim]), ([str(small)], [trim]), ([str(fq), str(small)], [trim, 0])):
+                got = oracle(paths, k, c, trims)
+                assert got == ref_kmers_trim(paths, k, c, trims, rebuild=lambda: got), (paths, k, c, trims)
     mine, theirs = oracle([str(big)], 7, True, [3]), ref_kmers_trim([str(big)], 7, True, [3])
     assert mine != theirs                                               # the documented deviation, as the real parser shows it
     total = lambda b: sum(int(l.split()[1]) for l in b.splitlines())

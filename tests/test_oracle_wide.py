@@ -1,6 +1,6 @@
 """oracle/koracle_wide.c (k-mers of up to 64 bases in one 128-bit word) against three independent statements:
-koracle.c entry by entry for k <= 32, the naive string counter (tests/naive.py) for k > 32, and -- where oracle/_ref is built --
-the reference's own parser + mer_iterator + mer_dna (jf_ref kmers), whose multi-word mer_dna is what KAT runs at k > 32."""
+koracle.c entry by entry for k <= 32, the naive string counter (tests/naive.py) for k > 32, and
+the reference's own parser + mer_iterator + mer_dna (jf_ref kmers, run or replayed: tests/refcalls.py), whose multi-word mer_dna is what KAT runs at k > 32."""
 import os
 
 import numpy as np
@@ -9,9 +9,6 @@ import pytest
 from tests import naive
 from tests.test_oracle_vs_naive import write_messy_fasta, write_messy_fastq
 from tests.test_oracle_vs_reference import JF_REF, ref
-
-have_jf_ref = pytest.mark.skipif(not os.access(JF_REF, os.X_OK), reason="oracle/_ref not built (no /root/reference)")
-
 
 def wide_dict(t):
     hi, lo, c = t.dump_sorted()
@@ -64,15 +61,14 @@ def test_wide_against_naive_strings(ko, tmp_path, k, canonical):
     assert got == {naive.pack(s): c for s, c in want.items()}
 
 
-@have_jf_ref
 @pytest.mark.parametrize("k,canonical", [(33, True), (48, True), (48, False), (63, True), (64, False)])
 def test_wide_against_the_reference_parser_and_mer_dna(ko, tmp_path, refdata, k, canonical):
-    """jf_ref kmers = mer_overlap_sequence_parser + mer_iterator + multi-word mer_dna compiled from /root/reference."""
+    """jf_ref kmers = mer_overlap_sequence_parser + mer_iterator + multi-word mer_dna compiled from the reference's sources."""
     for paths in (_files(tmp_path, k), [os.path.join(refdata, f) for f in ("ecoli_r1.1K.fastq", "ecoli_r2.1K.fastq", "sect_length_test.fa")]):
-        rc, out = ref(JF_REF, ["kmers", k, int(canonical)] + paths)
-        assert rc == 0
         hi, lo, c = ko.WideTable(k, canonical).count_files(paths).dump_sorted()
         got = "".join("%s %d\n" % (decode((int(a) << 64) | int(b), k), int(n)) for a, b, n in zip(hi, lo, c)).encode()
+        rc, out = ref(JF_REF, ["kmers", k, int(canonical)] + paths, rebuild=lambda: got)
+        assert rc == 0
         assert got == out and out.count(b"\n") > 1000
 
 

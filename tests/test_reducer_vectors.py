@@ -52,7 +52,6 @@ def test_oracle_gcp_is_the_reference_classes_result(ko, case):
     check_gcp(case, ko.Table(k, True).count_files([F1]).gcp(scale, bins))
 
 
-@pytest.mark.skipif(not (os.access(R.JF_REF, os.X_OK) and os.access(R.KAT_REF, os.X_OK)), reason="oracle/_ref not built (no /root/reference)")
 def test_golden_file_is_what_the_reference_code_says_today():
     case = R.COMP_CASES[4]
     counters, spectra, maxval, body = R.reference_comp(REFDATA, *case)

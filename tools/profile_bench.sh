@@ -2,7 +2,7 @@
 # Collect the rocprofv3 evidence behind bench.py's numbers on the GPU box (run through gpurun from the repo root):
 #   tools/profile_bench.sh <tag>      ->  gpurun_out/<tag>_bench.json, _kernel_stats.csv, _pmc_fetch_write.json,
 #                                         <tag>_{hist,gcp,comp-rr}_bench.json / _kernel_stats.csv, <tag>_sq_counters.txt
-# The default workload (config 4) runs three ways: plain (the JSON line, with the CPU baseline and the end-to-end leg),
+# The default workload (config 4) runs three ways: --full (the JSON line, with the CPU baseline and the end-to-end leg),
 # --kernel-trace --stats (per-kernel durations), and two --pmc passes (FETCH_SIZE, WRITE_SIZE; counters are collected in their own
 # runs, with --kernel-trace only).  The other workloads: plain, --kernel-trace --stats, and the same two --pmc passes (tools/profile_pmc_workload.sh: the two
 # counters cannot be collected in one pass on gfx950 -- rocprofv3 aborts with "exceeds the capabilities of the hardware" and then hangs).
@@ -43,7 +43,7 @@ json.dump(agg, open(sys.argv[1], "w"), indent=1)
 PY
 # the plain line comes after the counters: its roofline.traffic is read from the profile that was just taken (same sources: bench.py checks)
 mkdir -p "$root/profiles" && cp "$out/${tag}_pmc_fetch_write.json" "$root/profiles/${tag}_pmc_fetch_write.json"
-timeout 900 python "$root/bench.py" --steps 3 --warmup 1 > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
+timeout 900 python "$root/bench.py" --steps 3 --warmup 1 --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
 fi
 [ "${ONLY_MAIN:-0}" = 1 ] && { ls -la "$out" | grep "$tag"; exit 0; }
 for w in hist gcp comp-rr; do
@@ -52,7 +52,7 @@ for w in hist gcp comp-rr; do
   find /tmp/prof_w -name '*kernel_stats.csv' -exec cp {} "$out/${tag}_${w}_kernel_stats.csv" \;
   bash "$root/tools/profile_pmc_workload.sh" "$tag" $w
   cp "$out/${tag}_${w}_pmc_fetch_write.json" "$root/profiles/${tag}_${w}_pmc_fetch_write.json"
-  timeout 600 python "$root/bench.py" --workload $w --steps 3 --warmup 1 --no-e2e --no-cpu-baseline > "$out/${tag}_${w}_bench.json" 2> "$out/${tag}_${w}_bench.err"
+  timeout 600 python "$root/bench.py" --workload $w --steps 3 --warmup 1 --full --no-e2e --no-cpu-baseline > "$out/${tag}_${w}_bench.json" 2> "$out/${tag}_${w}_bench.err"
 done
 # (config 4 from files to files at full size is part of the plain line above since round 5: end_to_end, with its result_check)
 # SQ view of the stage kernels (one partition round of a reduced config): wave cycles, waits, issue, LDS conflicts
