@@ -164,6 +164,23 @@ int katgpu_table_get(katgpu_table* t, const uint64_t* keys, size_t n, int canoni
  * context's stream. */
 int katgpu_table_profile_host(katgpu_table* t, const char* bases, size_t n, int canonicalise, uint64_t* counts);
 int katgpu_table_profile_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, int canonicalise, uint64_t* dev_counts);
+/* `kat filter kmer`: FilterKmer::filterSlice + inBounds (src/filter_kmer.cc:251-307).  A k-mer is in bounds when
+ * low_count <= count <= high_count and low_gc <= #G+#C <= high_gc.  Without `separate`, *keep receives the k-mers with
+ * in_bounds != invert; with it, *keep receives the in-bounds k-mers and *drop the others, and `invert` is ignored, as in
+ * the reference.  *keep / *drop are new tables (free them with katgpu_table_free) of the input's capacity and geometry;
+ * the input is left as it is.  drop may be NULL unless `separate`.  counters[6] = distinct, total of the input, of the
+ * kept and of the dropped k-mers (FilterKmer::merge, src/filter_kmer.cc:228-249), all from the same device pass. */
+int katgpu_table_filter(katgpu_table* t, uint64_t low_count, uint64_t high_count, uint32_t low_gc, uint32_t high_gc,
+                        int invert, int separate, katgpu_table** keep, katgpu_table** drop, uint64_t counters[6]);
+/* `kat filter seq`: FilterSeq::getProfile (src/filter_sequence.cc:398-430) with the nbFound sum of processSeq
+ * (:345-353).  Record r is bases[rec_start[r], rec_start[r] + rec_len[r]); records are in increasing order and
+ * disjoint.  hits[r] = the number of k-windows inside record r that hold only ACGTacgt and whose k-mer the table counts
+ * (canonicalised when `canonicalise`).  The record's number of windows, max(0, len - k + 1), is the caller's.  The
+ * _device form takes device pointers and is asynchronous on the context's stream. */
+int katgpu_table_seq_hits_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                               size_t n_rec, int canonicalise, uint64_t* hits);
+int katgpu_table_seq_hits_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                 const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, uint64_t* dev_hits);
 /* All (key,count) pairs in unspecified order (the eager_iterator walk, JF/.../large_hash_iterator.hpp:28-65).
  * Pass cap = 0 to query *n_out only. */
 int katgpu_table_export(katgpu_table* t, uint64_t* keys, uint64_t* counts, size_t cap, size_t* n_out);

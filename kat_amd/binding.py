@@ -39,6 +39,7 @@ EXPORTS = (
     "katgpu_count_files_sharded", "katgpu_table_slot_bytes", "katgpu_comm_unique_id", "katgpu_comm_init", "katgpu_comm_free", "katgpu_comm_rank", "katgpu_comm_world", "katgpu_comm_transport",
     "katgpu_comm_transport_note", "katgpu_comm_distinct_devices", "katgpu_comm_barrier", "katgpu_exchange_merge", "katgpu_allreduce_u64", "katgpu_comm_stats",
     "katgpu_table_packed_records", "katgpu_table_extract_packed", "katgpu_table_merge_regions_packed", "katgpu_comm_wire", "katgpu_exchange_begin", "katgpu_exchange_finish",
+    "katgpu_table_filter", "katgpu_table_seq_hits_host", "katgpu_table_seq_hits_device",
 )
 
 
@@ -109,6 +110,9 @@ def load_library():
     L.katgpu_table_profile_host.argtypes = [vp, vp, sz, C.c_int, vp]
     L.katgpu_table_profile_device.argtypes = [vp, vp, sz, C.c_int, vp]
     L.katgpu_table_export.argtypes = [vp, vp, vp, sz, C.POINTER(sz)]
+    L.katgpu_table_filter.argtypes = [vp, u64, u64, u32, u32, C.c_int, C.c_int, pp, pp, vp]
+    L.katgpu_table_seq_hits_host.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp]
+    L.katgpu_table_seq_hits_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp]
     L.katgpu_hist.argtypes = [vp, u64, u64, u64, vp, sz]
     L.katgpu_gcp.argtypes = [vp, C.c_double, u32, vp]
     L.katgpu_comp.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, u32, u32, vp, vp, vp]
@@ -520,6 +524,39 @@ class Table:
         pb = getattr(dev_bases, "ptr", dev_bases)
         pc = getattr(dev_counts, "ptr", dev_counts)
         self.engine._chk(self.engine.L.katgpu_table_profile_device(self.h, pb, n, int(bool(canon)), pc))
+
+    # ---- kat filter ----
+    FILTER_COUNTERS = ("all_distinct", "all_total", "keep_distinct", "keep_total", "drop_distinct", "drop_total")
+
+    def filter(self, low_count=1, high_count=10000, low_gc=1, high_gc=100, invert=False, separate=False):
+        """`kat filter kmer` on this table (katgpu_table_filter): (keep, drop or None, counters dict).  The defaults are
+        FilterKmer::main's.  This table is left as it is."""
+        keep, drop = C.c_void_p(), C.c_void_p()
+        ctr = np.zeros(6, np.uint64)
+        self.engine._chk(self.engine.L.katgpu_table_filter(self.h, int(low_count), int(high_count), int(low_gc), int(high_gc), int(bool(invert)),
+                                                           int(bool(separate)), C.byref(keep), C.byref(drop) if separate else None, ctr.ctypes.data))
+        tk = Table(self.engine, self.k, self.canonical, _handle=keep.value)
+        td = Table(self.engine, self.k, self.canonical, _handle=drop.value) if separate else None
+        return tk, td, dict(zip(self.FILTER_COUNTERS, (int(x) for x in ctr)))
+
+    def seq_hits(self, bases, rec_start, rec_len, canonicalise=None):
+        """Per-record hit counts (katgpu_table_seq_hits_host): u64[n_rec], the windows of each record that are valid and found."""
+        if isinstance(bases, str):
+            bases = bases.encode()
+        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
+        st, ln = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_len, np.uint64)
+        assert st.size == ln.size
+        out = np.zeros(st.size, np.uint64)
+        canon = self.canonical if canonicalise is None else canonicalise
+        self.engine._chk(self.engine.L.katgpu_table_seq_hits_host(self.h, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size,
+                                                                  int(bool(canon)), out.ctypes.data))
+        return out
+
+    def seq_hits_device(self, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, dev_hits, canonicalise=None):
+        """Device-resident form: DeviceBuffers or raw device addresses; asynchronous on the engine's stream."""
+        canon = self.canonical if canonicalise is None else canonicalise
+        p = [getattr(x, "ptr", x) for x in (dev_bases, dev_rec_start, dev_rec_len, dev_hits)]
+        self.engine._chk(self.engine.L.katgpu_table_seq_hits_device(self.h, p[0], n, p[1], p[2], n_rec, int(bool(canon)), p[3]))
 
     def export(self):
         n = C.c_size_t()

@@ -51,6 +51,8 @@ struct HistogramException : KatException { using KatException::KatException; };
 struct CompException : KatException { using KatException::KatException; };
 struct FileSystemException : KatException { using KatException::KatException; };
 struct SectException : KatException { using KatException::KatException; };
+struct FilterKmerException : KatException { using KatException::KatException; };
+struct FilterSeqException : KatException { using KatException::KatException; };
 
 // One process-wide engine context (katgpu_init / katgpu_shutdown), and -- under `katgpu <mode> --gpus N` -- this process's place among
 // the N that share the run: one per GPU, forked by kat_main.cc before any of them touches the device.  The reference has nothing to
@@ -280,7 +282,9 @@ public:
     ~SeqRecordReader();
     bool atEnd();
     void readRecord(std::string& name, std::string& seq);
+    void readRecord(std::string& name, std::string& seq, std::string& qual);   // readRecord(meta, seq, qual): FASTQ qualities, newlines dropped ("" for FASTA)
 private:
+    void read(std::string& name, std::string& seq, std::string* qual);
     struct Impl;
     std::unique_ptr<Impl> impl;
     enum { FASTA, FASTQ, RAW } format = FASTA;
@@ -367,6 +371,72 @@ private:
     uint16_t gcBins = 1001, cvgBins = 1001, threads = 1;
     bool verbose = false;
 };
+
+// src/filter_kmer.hpp: the k-mers of a hash inside (or outside) a count x GC box, written as .jf.  Defaults are FilterKmer::main's
+// (src/filter_kmer.cc:333-346), which differ from the DEFAULT_FILT_KMER_* constants of the header.
+class FilterKmer {
+public:
+    explicit FilterKmer(const std::vector<std::string>& inputs);
+    void setOutput_prefix(const std::string& p) { output_prefix = p; }
+    void setThreads(uint16_t t) { threads = t; }
+    void setLow_count(uint64_t v) { low_count = v; }
+    void setHigh_count(uint64_t v) { high_count = v; }
+    void setLow_gc(uint16_t v) { low_gc = v; }
+    void setHigh_gc(uint16_t v) { high_gc = v; }
+    void setInvert(bool v) { invert = v; }
+    void setSeparate(bool v) { separate = v; }
+    void setCanonical(bool c) { input.canonical = c; }
+    void setMerLen(uint16_t m) { input.merLen = m; }
+    void setHashSize(uint64_t h) { input.hashSize = h; }
+    void setVerbose(bool v) { verbose = v; }
+    void execute();
+    static int main(int argc, char* argv[]);
+private:
+    void filter();
+    void merge();
+    void dump(const std::string& path, katgpu_table* hash);
+    InputHandler input;
+    std::string output_prefix = "kat.filter-kmer";
+    uint16_t threads = 1;
+    uint64_t low_count = 1, high_count = 10000;
+    uint16_t low_gc = 1, high_gc = 100;
+    bool invert = false, separate = false, verbose = false;
+    katgpu_table* in_hash = nullptr;            // inCounter / outCounter
+    katgpu_table* out_hash = nullptr;
+    uint64_t counters[6] = {};                  // all / in / out: distinct, total (ThreadedCounter::merge)
+};
+
+// src/filter_sequence.hpp: the records (or pairs) of a sequence file whose k-mers are found in a hash, as FASTA / FASTQ
+class FilterSeq {
+public:
+    FilterSeq(const std::string& seq_file_1, const std::string& seq_file_2, const std::vector<std::string>& inputs);
+    ~FilterSeq();
+    void setOutput_prefix(const std::string& p) { output_prefix = p; }
+    void setThreads(uint16_t t) { threads = t; }
+    void setThreshold(double v) { threshold = v; }
+    void setFrequency(double v) { frequency = v; }
+    void setInvert(bool v) { invert = v; }
+    void setSeparate(bool v) { separate = v; }
+    void setDoStats(bool v) { doStats = v; }
+    void setCanonical(bool c) { input.canonical = c; }
+    void setMerLen(uint16_t m) { input.merLen = m; }
+    void setHashSize(uint64_t h) { input.hashSize = h; }
+    void setVerbose(bool v) { verbose = v; }
+    bool isPaired() const { return !seq_file_2.empty(); }
+    void execute();
+    static int main(int argc, char* argv[]);
+private:
+    void processSeqFile();
+    InputHandler input;
+    std::string seq_file_1, seq_file_2, output_prefix = "kat.filter-kmer";
+    uint16_t threads = 1;
+    double threshold = 0.1, frequency = 0.0;
+    bool invert = false, separate = false, doStats = false, verbose = false;
+    uint64_t keepers = 0, total = 0;
+};
+
+// src/filter.cc: `kat filter kmer|seq`
+struct Filter { static int main(int argc, char* argv[]); };
 
 // ---- command-line helper shared by the three tools (stands in for boost::program_options) ----
 struct OptSpec { const char* lng; char sht; bool takes_value; };

@@ -1,4 +1,4 @@
-// kat_main.cc -- `katgpu hist|gcp|comp|sect|cold ...`: the dispatcher for the KAT modes on the path, with KAT's exit codes
+// kat_main.cc -- `katgpu hist|gcp|comp|sect|cold|filter ...`: the dispatcher for the KAT modes on the path, with KAT's exit codes
 // (src/kat.cc:178-305: option errors 1, KAT/boost exceptions 4, std::exception 5, const char* 6, anything else 7).
 #include "kat_host.hpp"
 
@@ -13,7 +13,7 @@
 #include <unistd.h>
 
 static void usage() {
-    std::cout << "The K-mer Analysis Toolkit, MI355X engine (katgpu): hist | gcp | comp | sect | cold\n"
+    std::cout << "The K-mer Analysis Toolkit, MI355X engine (katgpu): hist | gcp | comp | sect | cold | filter\n"
                  "Usage: katgpu <mode> [options] <inputs>   (same options as `kat <mode>`; see INTEGRATION.md)\n";
 }
 
@@ -26,7 +26,8 @@ static int run_mode(const std::string& mode, int argc, char* argv[]) {
     if (mode == "comp") return kat::Comp::main(argc, argv);
     if (mode == "sect") return kat::Sect::main(argc, argv);
     if (mode == "cold") return kat::Cold::main(argc, argv);
-    throw kat::OptionError("Could not recognise mode string: " + mode + " (this build carries hist, gcp, comp, sect and cold)");
+    if (mode == "filter") return kat::Filter::main(argc, argv);
+    throw kat::OptionError("Could not recognise mode string: " + mode + " (this build carries hist, gcp, comp, sect, cold and filter)");
 }
 
 static int guarded(const std::string& mode, int argc, char* argv[]) {

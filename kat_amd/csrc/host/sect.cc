@@ -96,8 +96,12 @@ void SeqRecordReader::line(string* into) {      // readLine / skipLine (seqan/st
     if (peek() == '\n') impl->pos++;
 }
 
-void SeqRecordReader::readRecord(string& name, string& seq) {
+void SeqRecordReader::readRecord(string& name, string& seq) { read(name, seq, nullptr); }
+void SeqRecordReader::readRecord(string& name, string& seq, string& qual) { read(name, seq, &qual); }
+
+void SeqRecordReader::read(string& name, string& seq, string* qual) {
     name.clear(); seq.clear();
+    if (qual) qual->clear();
     if (format == RAW) { line(&seq); return; }                                                  // every line a nameless record
     const bool fastq = format == FASTQ;
     const int begin = fastq ? '@' : '>', stop = fastq ? '+' : '>';
@@ -123,7 +127,7 @@ void SeqRecordReader::readRecord(string& name, string& seq) {
     impl->pos++;
     line(nullptr);                                                                              // optional second id
     size_t left = seq.size();                                                                   // CountDownFunctor over non-newline characters
-    while (left && (c = peek()) >= 0) { if (c != '\n' && c != '\r') left--; impl->pos++; }
+    while (left && (c = peek()) >= 0) { if (c != '\n' && c != '\r') { left--; if (qual) qual->push_back((char)c); } impl->pos++; }
     while ((c = peek()) >= 0 && c != '@') impl->pos++;
 }
 

@@ -1,8 +1,10 @@
 // kg_table.hip -- the HBM-resident count table behind katgpu_table: geometry and layout choice, allocation, regrow
-// (hash_counter::double_size), statistics, batch lookups and per-position profiles, record export / merge.
+// (hash_counter::double_size), statistics, batch lookups and per-position profiles, record export / merge, the k-mer filter and the
+// per-record hit counts of `kat filter`.
 #include "kg_host.hpp"
 #include "kg_kernels.hpp"
 #include "kg_wide.hpp"
+#include "kg_filter.hpp"
 
 static const uint32_t g_region_slots = (uint32_t)hook_u64("KATGPU_TEST_REGION_SLOTS", REGION_SLOTS);
 static const bool g_no_packed = hook("KATGPU_NO_PACKED") != nullptr;   // tests / A-B: every table in the KV12 layout
@@ -527,3 +529,135 @@ extern "C" int katgpu_table_get_wide(katgpu_table* t, const uint64_t* keys_hi, c
     return KATGPU_OK;
 }
 
+
+// ------------------------------------------------------------------ kat filter ----
+
+// FilterKmer::execute + filterSlice (src/filter_kmer.cc:136-288): the reference adds the chosen k-mers of the input hash into one or two
+// new hashes of the input's size.  Here the new tables take the input's capacity and region grid (as regrow does), so one pass of K9 over
+// the input's slots fills them region by region, and the six counters come back from the same pass.
+extern "C" int katgpu_table_filter(katgpu_table* t, uint64_t low_count, uint64_t high_count, uint32_t low_gc, uint32_t high_gc,
+                                   int invert, int separate, katgpu_table** keep, katgpu_table** drop, uint64_t counters[6]) {
+    if (!t || !keep || (separate && !drop) || !counters) return KATGPU_ERR_INVALID_ARG;
+    *keep = nullptr;
+    if (drop) *drop = nullptr;
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    const DevTable src = t->dev();
+    const bool grid = src.n_regions > 1;
+    katgpu_table* out[2] = {nullptr, nullptr};
+    for (int i = 0; i < (separate ? 2 : 1); ++i) {
+        out[i] = new katgpu_table();
+        out[i]->ctx = c; out[i]->disable_grow = t->disable_grow;
+        rc = alloc_dev_table(c, src.k, (int)src.canonical, src.cap, &out[i]->dv, grid ? src.p1 : 0, grid ? src.p2 : 0);
+        if (rc) { delete out[i]; out[i] = nullptr; break; }
+    }
+    if (!rc) {
+        unsigned long long* ctr = (unsigned long long*)&src.ctrs[CTR_SCRATCH];
+        const FilterBox box{low_count, high_count, low_gc, high_gc};
+        const DevTable& dk = out[0]->dv;
+        const DevTable& dd = separate ? out[1]->dv : out[0]->dv;   // (not written without `separate`)
+        const dim3 g(grid_for(c, src.cap, 256, 8));
+        hipError_t e = hipMemsetAsync(ctr, 0, FC_N * sizeof(uint64_t), c->stream);
+        if (e == hipSuccess) {
+            if (src.keys_b && separate) hipLaunchKernelGGL(k_filter_w<true>, g, dim3(256), 0, c->stream, dk, dd, src, t->n_ovf, box, invert, ctr);
+            else if (src.keys_b) hipLaunchKernelGGL(k_filter_w<false>, g, dim3(256), 0, c->stream, dk, dd, src, t->n_ovf, box, invert, ctr);
+            else if (separate) hipLaunchKernelGGL(k_filter<true>, g, dim3(256), 0, c->stream, dk, dd, src, t->n_ovf, box, invert, ctr);
+            else hipLaunchKernelGGL(k_filter<false>, g, dim3(256), 0, c->stream, dk, dd, src, t->n_ovf, box, invert, ctr);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(counters, ctr, FC_N * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) rc = fail(c, KATGPU_ERR_DEVICE, "filter: %s", hipGetErrorString(e));
+        for (int i = 0; i < 2 && !rc; ++i) if (out[i]) rc = refresh_counters(out[i]);
+        if (!rc && (out[0]->distinct != counters[FC_KEEP_D] || (separate && out[1]->distinct != counters[FC_DROP_D])))
+            rc = fail(c, KATGPU_ERR_DEVICE, "filter: the new tables hold %llu / %llu distinct k-mers, the pass routed %llu / %llu",
+                      (unsigned long long)out[0]->distinct, (unsigned long long)(separate ? out[1]->distinct : 0),
+                      (unsigned long long)counters[FC_KEEP_D], (unsigned long long)counters[FC_DROP_D]);
+    }
+    if (rc) { katgpu_table_free(out[0]); katgpu_table_free(out[1]); return rc; }
+    *keep = out[0];
+    if (separate) *drop = out[1];
+    return KATGPU_OK;
+}
+
+static int launch_seq_hits(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec,
+                           int canonicalise, uint64_t* dev_hits) {
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipMemsetAsync(dev_hits, 0, n_rec * sizeof(uint64_t), c->stream));
+    const uint32_t k = t->dev().k;
+    if (n < k || !n_rec) return KATGPU_OK;
+    const bool wide = t->dev().keys_b != nullptr;
+    const uint64_t n_out = n - k + 1;
+    const uint64_t per_chunk = wide ? WIDE_CHUNK_STARTS : CHUNK_STARTS;
+    const uint64_t n_chunks = (n_out + per_chunk - 1) / per_chunk;
+    const int grid = (int)std::min<uint64_t>(n_chunks, (uint64_t)c->n_cu * 8);
+    const bool aligned = (reinterpret_cast<uintptr_t>(dev_bases) & 15) == 0;
+    unsigned long long* h = (unsigned long long*)dev_hits;
+    ScopedTimer tm(c, KATGPU_K_PROFILE, n_out);
+    if (wide && aligned) hipLaunchKernelGGL((k_seq_hits<true, true>), dim3(grid), dim3(COUNT_BLOCK), 0, c->stream, t->dev(), t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, h);
+    else if (wide) hipLaunchKernelGGL((k_seq_hits<false, true>), dim3(grid), dim3(COUNT_BLOCK), 0, c->stream, t->dev(), t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, h);
+    else if (aligned) hipLaunchKernelGGL((k_seq_hits<true, false>), dim3(grid), dim3(COUNT_BLOCK), 0, c->stream, t->dev(), t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, h);
+    else hipLaunchKernelGGL((k_seq_hits<false, false>), dim3(grid), dim3(COUNT_BLOCK), 0, c->stream, t->dev(), t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, h);
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+extern "C" int katgpu_table_seq_hits_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                            const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, uint64_t* dev_hits) {
+    if (!t || (n_rec && (!dev_rec_start || !dev_rec_len || !dev_hits)) || (n && !dev_bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!n_rec) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    return launch_seq_hits(t, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, canonicalise, dev_hits);
+}
+
+// Host form: the records go through the device in batches of at most SEQ_HITS_BATCH bases and SEQ_HITS_RECS records (a record longer
+// than that is a batch of its own), so any input fits next to the table.
+extern "C" int katgpu_table_seq_hits_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                                          size_t n_rec, int canonicalise, uint64_t* hits) {
+    if (!t || (n_rec && (!rec_start || !rec_len || !hits)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!n_rec) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    for (size_t r = 0; r < n_rec; ++r) {
+        if (rec_start[r] > n || rec_len[r] > n - rec_start[r]) return fail(c, KATGPU_ERR_INVALID_ARG, "record %zu lies beyond the %zu bases", r, n);
+        if (r && rec_start[r] < rec_start[r - 1] + rec_len[r - 1]) return fail(c, KATGPU_ERR_INVALID_ARG, "record %zu starts before record %zu ends: records must be in order and disjoint", r, r - 1);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    const size_t SEQ_HITS_BATCH = (size_t)64 << 20, SEQ_HITS_RECS = (size_t)1 << 20;
+    uint8_t* db = nullptr; uint64_t* dr = nullptr;
+    size_t db_bytes = 0;
+    HIPCHK(c, pool_alloc(c, (void**)&dr, SEQ_HITS_RECS * 3 * sizeof(uint64_t)));
+    std::vector<uint64_t> st(SEQ_HITS_RECS), ln(SEQ_HITS_RECS);
+    hipError_t e = hipSuccess;
+    for (size_t r0 = 0; r0 < n_rec && !rc && e == hipSuccess;) {
+        const uint64_t base = rec_start[r0];
+        size_t r1 = r0 + 1;
+        while (r1 < n_rec && r1 - r0 < SEQ_HITS_RECS && rec_start[r1] + rec_len[r1] - base <= SEQ_HITS_BATCH) ++r1;
+        const size_t nb = rec_start[r1 - 1] + rec_len[r1 - 1] - base;
+        if (nb + 64 > db_bytes) {
+            pool_release(c, db); db = nullptr;
+            db_bytes = std::max(nb + 64, std::min(SEQ_HITS_BATCH, n) + 64);
+            e = pool_alloc(c, (void**)&db, db_bytes);
+            if (e != hipSuccess) { db_bytes = 0; break; }
+        }
+        for (size_t r = r0; r < r1; ++r) { st[r - r0] = rec_start[r] - base; ln[r - r0] = rec_len[r]; }
+        const size_t m = r1 - r0;
+        if (nb) e = hipMemcpyAsync(db, bases + base, nb, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dr, st.data(), m * 8, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dr + SEQ_HITS_RECS, ln.data(), m * 8, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) break;
+        rc = launch_seq_hits(t, db, nb, dr, dr + SEQ_HITS_RECS, m, canonicalise, dr + 2 * SEQ_HITS_RECS);
+        if (rc) break;
+        e = hipMemcpyAsync(hits + r0, dr + 2 * SEQ_HITS_RECS, m * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        r0 = r1;
+    }
+    hipStreamSynchronize(c->stream);
+    pool_release(c, db); pool_release(c, dr);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "seq hits: %s", hipGetErrorString(e));
+    return KATGPU_OK;
+}
