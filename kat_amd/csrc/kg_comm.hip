@@ -28,6 +28,7 @@
 // KATGPU_COMM_TIMEOUT_S (default 60 s): a peer that died, not one that is busy.  KATGPU_COMM_MAX_WAIT_S (default: none) bounds a
 // single wait by the clock for harnesses that prefer an error to a wedged link (bench.py sets it).
 #include "kg_host.hpp"
+#include "kg_exchange_layout.hpp"
 
 #include <rccl/rccl.h>
 
@@ -587,12 +588,8 @@ extern "C" int katgpu_allreduce_u64(katgpu_comm* m, uint64_t* buf, size_t n) {
 
 // ------------------------------------------------------------------ the exchange ----------------------
 
-static size_t xalign(size_t n, size_t a = 256) { return (n + a - 1) / a * a; }
-// (sized for key + count records; packed records -- 4 + 1 + 4 bytes -- are carved out of the same room)
-static size_t exchange_bytes(uint64_t total_send, uint64_t set_records) {
-    return xalign(8 * std::max<uint64_t>(total_send, 1)) + xalign(4 * std::max<uint64_t>(total_send, 1)) +
-           2 * (xalign(8 * std::max<uint64_t>(set_records, 1)) + xalign(4 * std::max<uint64_t>(set_records, 1))) + 256;
-}
+// the pipelined shape's buffer: the send list and two receive sets (kg_exchange_layout.hpp: either wire form fits it)
+static size_t exchange_bytes(uint64_t total_send, uint64_t set_records) { return exchange_layout_pipelined(total_send, set_records).bytes; }
 static const bool g_comm_trace = getenv("KATGPU_COMM_TRACE") != nullptr;      // one stderr line per stage of katgpu_exchange_merge, per rank: where a run of many ranks stands
 #define CTRACE(m, ...) do { if (g_comm_trace) { fprintf(stderr, "[katgpu comm %d/%d +%.0f ms] ", (m)->rank, (m)->world, wall_ms() - t_begin); fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); } } while (0)
 static const bool g_wire_packed = !getenv("KATGPU_COMM_PACKED_RECORDS") || atoi(getenv("KATGPU_COMM_PACKED_RECORDS")) != 0;   // A/B + tests: 0 = key + count records (12 bytes) even between ranks that share the grid
@@ -792,8 +789,9 @@ struct Exchange {
         uint8_t* a = nullptr;
         if (want_split) {                                         // a buffer of the exchange's own: the send list + a receive set per chunk
             cut(C0);
-            size_t bytes = xalign(8 * std::max<uint64_t>(total_send, 1)) + xalign(4 * std::max<uint64_t>(total_send, 1)) + 256;
-            for (uint32_t i = 0; i < C; ++i) bytes += xalign(8 * std::max<uint64_t>(chunk_in(i), 1)) + xalign(4 * std::max<uint64_t>(chunk_in(i), 1));
+            std::vector<uint64_t> set_n(C);
+            for (uint32_t i = 0; i < C; ++i) set_n[i] = chunk_in(i);
+            const size_t bytes = exchange_layout(total_send, set_n.data(), set_n.size()).bytes;
             const bool got = !hook("KATGPU_TEST_EXCHANGE_NO_SPLIT") && hipMalloc(&own_buf, bytes) == hipSuccess;
             if (!got) { (void)hipGetLastError(); own_buf = nullptr; }
             bool all = false;
@@ -845,15 +843,17 @@ struct Exchange {
         if (rc) return rc;
         m->wire_packed = packed;
         CTRACE(m, "%u chunks (%s), records of %d bytes", C, split ? "all on the wire at once" : "one travels while one is applied", packed ? 9 : 12);
-        skeys = (uint64_t*)a;           a += xalign(8 * std::max<uint64_t>(total_send, 1));     // (packed: the low words, then the high bytes, in the same room)
-        scounts = (uint32_t*)a;         a += xalign(4 * std::max<uint64_t>(total_send, 1));
-        srem_lo = (uint32_t*)skeys;
-        srem_hi = (uint8_t*)skeys + xalign(4 * std::max<uint64_t>(total_send, 1));
-        sets.resize(split ? C : 2);
-        for (size_t i = 0; i < sets.size(); ++i) {
-            const uint64_t n = split ? std::max<uint64_t>(chunk_in((uint32_t)i), 1) : set_records;
-            sets[i].keys = (uint64_t*)a; sets[i].rem_lo = (uint32_t*)a; sets[i].rem_hi = a + xalign(4 * n); a += xalign(8 * n);
-            sets[i].counts = (uint32_t*)a; a += xalign(4 * n);
+        {                                                         // (packed: the low words, then the high bytes, in the keys' room)
+            std::vector<uint64_t> set_n(split ? C : 2, set_records);
+            if (split) for (uint32_t i = 0; i < C; ++i) set_n[i] = chunk_in(i);
+            const XLayout xl = exchange_layout(total_send, set_n.data(), set_n.size());
+            skeys = (uint64_t*)(a + xl.send.keys); scounts = (uint32_t*)(a + xl.send.counts);
+            srem_lo = (uint32_t*)(a + xl.send.rem_lo); srem_hi = a + xl.send.rem_hi;
+            sets.resize(set_n.size());
+            for (size_t i = 0; i < sets.size(); ++i) {
+                const XGroup& g = xl.sets[i];
+                sets[i] = Set{(uint64_t*)(a + g.keys), (uint32_t*)(a + g.rem_lo), a + g.rem_hi, (uint32_t*)(a + g.counts)};
+            }
         }
         rc = packed ? katgpu_table_extract_packed(t, (uint32_t)world, d_cnt, srem_lo, srem_hi, scounts, big_keys.data(), big_counts.data(), BIG, &n_big)
                     : katgpu_table_extract(t, (uint32_t)world, d_cnt, skeys, scounts, big_keys.data(), big_counts.data(), BIG, &n_big);
