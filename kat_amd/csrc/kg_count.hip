@@ -80,8 +80,6 @@ static const uint64_t g_test_round_items = hook("KATGPU_TEST_ROUND_ITEMS") ? str
 // share of the free HBM the partition arena may take (multi-GPU runs may lower it; bench.py sets 0.75 there)
 static const double g_arena_fraction = getenv("KATGPU_ARENA_FRACTION") ? std::min(0.95, std::max(0.05, atof(getenv("KATGPU_ARENA_FRACTION")))) : 0.85;
 static const uint32_t g_p1_wgs = hook("KATGPU_P1_WGS") ? std::max<uint32_t>(1, (uint32_t)strtoul(hook("KATGPU_P1_WGS"), nullptr, 10)) : 3;   // level-1 workgroups per CU
-static const bool g_apply_noinline = hook("KATGPU_APPLY_NOINLINE") != nullptr;   // A/B: no inline claims in a table's first round
-static const uint32_t g_apply_block = hook("KATGPU_APPLY_BLOCK") ? (uint32_t)strtoul(hook("KATGPU_APPLY_BLOCK"), nullptr, 10) : 0;   // 0: by region size
 // level 2 without its histogram pass (kg_partition.hpp: k_p2_fast): 0 = never, 1 = when the mean run is long enough for the
 // capacity slack to cover the noise, 2 = always (tests).  KATGPU_TEST_P2_OVF_CAP shrinks the overflow list (tests: forces the
 // fall back to the exact kernel).
@@ -90,26 +88,21 @@ static const uint32_t g_apply_block = hook("KATGPU_APPLY_BLOCK") ? (uint32_t)str
 static const uint32_t g_test_l1_cpb = hook("KATGPU_TEST_L1_CPB") ? (uint32_t)strtoul(hook("KATGPU_TEST_L1_CPB"), nullptr, 10) : 0;   // tests: segment capacity (forces overflow)
 static const bool g_l1_lean = hook_u64("KATGPU_L1_LEAN", 1) != 0;   // A/B: 0 = level 1's ranking sweep in its 64-bit form (kg_l1_lean.hpp is the 32-bit one)
 static const uint32_t g_l1_fast = hook("KATGPU_L1_FAST") ? (uint32_t)strtoul(hook("KATGPU_L1_FAST"), nullptr, 10) : 1;
-static const bool g_l1_blocks = hook_u64("KATGPU_L1_BLOCKS", 1) != 0;   // A/B: 0 = the group edition of the segmented level 1 where the block edition (kg_l1_blocks.hpp) would run
 static const uint32_t g_p2_fast = hook("KATGPU_P2_FAST") ? (uint32_t)strtoul(hook("KATGPU_P2_FAST"), nullptr, 10) : 1;
 static const uint64_t g_test_p2_ovf_cap = hook("KATGPU_TEST_P2_OVF_CAP") ? strtoull(hook("KATGPU_TEST_P2_OVF_CAP"), nullptr, 10) : 0;
 static const uint32_t g_test_spill_mod = hook("KATGPU_TEST_SPILL_MOD") ? (uint32_t)strtoul(hook("KATGPU_TEST_SPILL_MOD"), nullptr, 10) : 0;
 static const uint64_t g_test_ap_seg = hook_u64("KATGPU_TEST_AP_SEG", 0) & ~3ULL;   // tests: k-mers per walk segment of the apply kernels (several segments per run)
-static const uint32_t g_apply_nr = (uint32_t)hook_u64("KATGPU_APPLY_NR", 2);            // A/B: probe rounds of the packed apply at the bench's shape (1, 2 or 3)
-static const uint32_t g_apply_min_q = (uint32_t)hook_u64("KATGPU_APPLY_MIN_Q", 72);     // A/B: queue entries per wave the SECOND workgroup of a CU must leave (>= 72)
 static const uint32_t g_apply_per_cu = (uint32_t)hook_u64("KATGPU_APPLY_PER_CU", 0);   // A/B: packed apply workgroups per CU (0: as many as the LDS holds)
 static const bool g_l1b_stamp = hook_u64("KATGPU_L1B_STAMP", 0) != 0;   // diagnostic: level 1's block edition with cycle stamps (printed per round)
-static const bool g_p2x = hook_u64("KATGPU_P2X", 1) != 0;   // A/B: 0 = k_p2_fast's block edition where kg_l2_blocks.hpp's kernel would run
-static const bool g_p2x_stamp = hook_u64("KATGPU_P2X_STAMP", 0) != 0;   // diagnostic: that kernel with cycle stamps (printed per pass)
-static const bool g_p2_stamp = hook_u64("KATGPU_P2_STAMP", 0) != 0;   // diagnostic: the bench-shape one-pass level 2 with cycle stamps (printed per pass)
+static const bool g_p2x_stamp = hook_u64("KATGPU_P2X_STAMP", 0) != 0;   // diagnostic: kg_l2_blocks.hpp's kernel with cycle stamps (printed per pass)
+static const bool g_p2_stamp = hook_u64("KATGPU_P2_STAMP", 0) != 0;   // diagnostic: the one-pass level 2 of 5-byte items from groups with cycle stamps (printed per pass)
 static const bool g_apply_stamp = hook_u64("KATGPU_APPLY_STAMP", 0) != 0;              // diagnostic: the bench-shape apply with cycle stamps (printed per pass)
 
-static const uint32_t g_test_hb = hook("KATGPU_TEST_HB") ? (uint32_t)strtoul(hook("KATGPU_TEST_HB"), nullptr, 10) : 0;   // A/B: wider level-2 items than needed (1, 2, 4)
 static bool part_geometry(const DevTable& d, PartGeom* g) {
     g->R = d.n_regions; g->S = d.region_slots; g->P1 = d.p1; g->P2 = d.p2; g->l2 = d.l2;
     g->b_lo = 0; g->b_hi = d.p1;
     g->pl = place_make(d.k, d.p1, d.n1, d.l2);
-    g->hb = std::max(l2_hi_bytes(g->pl.rb), g_test_hb);
+    g->hb = l2_hi_bytes(g->pl.rb);
     g->hb1 = l2_hi_bytes(g->pl.n1);
     g->cbits = d.cbits;
     if (d.cbits && g->hb > 2) g->hb = 2;                       // (a packed table's remainder has at most 44 bits)
@@ -130,12 +123,19 @@ static double arena_bytes_per_item(uint32_t hb, uint32_t passes) { return 8.0 * 
 
 static const bool g_test_grow_nomem = hook("KATGPU_TEST_GROW_NOMEM") != nullptr;   // tests: table growth "fails" while the arena is busy
 
+// keys that found no slot (8 bytes each; 16 for wide tables), in device memory, go in through the direct path
+static void insert_keys(katgpu_table* t, const void* keys, uint64_t n, size_t key_bytes) {
+    katgpu_ctx* c = t->ctx;
+    ScopedTimer tm(c, KATGPU_K_COUNT, n);
+    if (key_bytes == 16) hipLaunchKernelGGL(k_insert_keys_w, dim3(grid_for(c, n, 256, 6)), dim3(256), 0, c->stream, t->dev(), (const u64x2*)keys, n);
+    else hipLaunchKernelGGL(k_insert_keys, dim3(grid_for(c, n, 256, 6)), dim3(256), 0, c->stream, t->dev(), (const uint64_t*)keys, n);
+}
 // Growth while a partition call holds the arena.  First with the arena protected; when the device cannot hold the old
-// table, the new one and the arena at once, `stash` (spilled keys that live in the arena, may be null) is parked in host
-// memory, the arena is given up, the growth retried and the keys re-inserted from the host.  *arena_lost tells the
+// table, the new one and the arena at once, `stash` (spilled keys of key_bytes each that live in the arena, may be empty) is parked
+// in host memory, the arena is given up, the growth retried and the keys re-inserted from the host.  *arena_lost tells the
 // caller that its carve of the arena is gone.
-typedef std::vector<std::pair<const uint64_t*, uint64_t>> KeyLists;
-static int grow_beside_arena(katgpu_table* t, uint64_t incoming, uint64_t min_cap, const KeyLists& stash, bool* arena_lost) {
+typedef std::vector<std::pair<const void*, uint64_t>> KeyLists;
+static int grow_beside_arena(katgpu_table* t, uint64_t incoming, uint64_t min_cap, const KeyLists& stash, size_t key_bytes, bool* arena_lost) {
     uint64_t n_stash = 0;
     for (auto& l : stash) n_stash += l.second;
     katgpu_ctx* c = t->ctx;
@@ -151,11 +151,11 @@ static int grow_beside_arena(katgpu_table* t, uint64_t incoming, uint64_t min_ca
     int rc = g_test_grow_nomem ? KATGPU_ERR_NOMEM : grow();
     if (rc != KATGPU_ERR_NOMEM) return rc;
     (void)hipGetLastError();
-    std::vector<uint64_t> host;
+    std::vector<uint8_t> host;
     if (n_stash) {
-        try { host.resize(n_stash); } catch (...) { return fail(c, KATGPU_ERR_NOMEM, "no host memory to park %llu spilled k-mers", (unsigned long long)n_stash); }
+        try { host.resize(n_stash * key_bytes); } catch (...) { return fail(c, KATGPU_ERR_NOMEM, "no host memory to park %llu spilled k-mers", (unsigned long long)n_stash); }
         uint64_t at = 0;
-        for (auto& l : stash) { HIPCHK(c, hipMemcpy(host.data() + at, l.first, l.second * 8, hipMemcpyDeviceToHost)); at += l.second; }
+        for (auto& l : stash) { HIPCHK(c, hipMemcpy(host.data() + at * key_bytes, l.first, l.second * key_bytes, hipMemcpyDeviceToHost)); at += l.second; }
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     release_arena(c);
@@ -164,14 +164,13 @@ static int grow_beside_arena(katgpu_table* t, uint64_t incoming, uint64_t min_ca
     rc = grow();
     if (rc) return rc;
     if (n_stash) {
-        const size_t chunk = std::min<size_t>(n_stash, (size_t)32 << 20);
-        uint64_t* d = nullptr;
-        HIPCHK(c, pool_alloc(c, (void**)&d, chunk * 8));
+        const size_t chunk = std::min<size_t>(n_stash, ((size_t)256 << 20) / key_bytes);
+        uint8_t* d = nullptr;
+        HIPCHK(c, pool_alloc(c, (void**)&d, chunk * key_bytes));
         for (size_t i = 0; i < n_stash && rc == KATGPU_OK; i += chunk) {
             const size_t m = std::min(chunk, (size_t)n_stash - i);
-            if (hipMemcpyAsync(d, host.data() + i, m * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = fail(c, KATGPU_ERR_DEVICE, "spill upload"); break; }
-            ScopedTimer tm(c, KATGPU_K_COUNT, m);
-            hipLaunchKernelGGL(k_insert_keys, dim3(grid_for(c, m, 256, 6)), dim3(256), 0, c->stream, t->dev(), (const uint64_t*)d, (uint64_t)m);
+            if (hipMemcpyAsync(d, host.data() + i * key_bytes, m * key_bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = fail(c, KATGPU_ERR_DEVICE, "spill upload"); break; }
+            insert_keys(t, d, m, key_bytes);
             if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, KATGPU_ERR_DEVICE, "spill insert");
         }
         pool_release(c, d);
@@ -179,26 +178,123 @@ static int grow_beside_arena(katgpu_table* t, uint64_t incoming, uint64_t min_ca
     return rc;
 }
 
-#define KG_FOR_HB_APPLY(M) M(0) M(1) M(2) M(4)
-// the dynamic-LDS ceiling of a kernel is raised once per device (c->lds_attr holds the kernels done)
-static int ensure_lds_attr(katgpu_ctx* c, const void* fn, size_t bytes) {
-    if (c->lds_attr.count(fn)) return KATGPU_OK;
-    HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    c->lds_attr.insert(fn);
+// The partition arena (katgpu_ctx::arena, kept across calls) for a call that could use want_bytes: small_bytes of histograms and counters +
+// item_bytes per k-mer of a round (want_items of them, at most; item_bytes is a rounded-up figure for the "useful round" thresholds below -- 18 for
+// 8-byte keys, 32 for wide ones -- not the carve's exact bytes per item).  It is re-allocated only for a substantially larger one (fewer rounds):
+// a fresh hipMalloc of this size is not free.  *usable = false: no room for a useful round -- the direct path.
+static int ensure_arena(katgpu_ctx* c, size_t small_bytes, size_t item_bytes, size_t want_items, size_t want_bytes, const char* note, bool* usable) {
+    *usable = false;
+    if (c->arena_limit) want_bytes = std::min(want_bytes, std::max(c->arena_limit, small_bytes + item_bytes * ((size_t)64 << 20)));      // (the file feeders: more rounds, less to allocate)
+    if (c->arena_bytes < want_bytes) {                                           // the arena could be more useful than it is
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
+        free_b += c->arena_bytes;
+        const size_t bytes = std::min<size_t>(want_bytes, (size_t)(g_arena_fraction * (double)free_b));
+        if (bytes > c->arena_bytes + c->arena_bytes / 2 || c->arena_bytes < small_bytes + item_bytes * std::min<size_t>(want_items, (size_t)64 << 20)) {
+            if (c->arena) { HIPCHK(c, hipFree(c->arena)); c->arena = nullptr; c->arena_bytes = 0; }
+            if (!g_test_round_items && bytes < small_bytes + item_bytes * ((size_t)1 << 20)) return KATGPU_OK;
+            const double t_ar = now_ms();
+            if (hipMalloc((void**)&c->arena, bytes) != hipSuccess) { (void)hipGetLastError(); c->arena = nullptr; return KATGPU_OK; }
+            c->arena_bytes = bytes;
+            if (g_trace) fprintf(stderr, "[katgpu +%.0f ms] partition arena of %.1f GB%s: %.0f ms\n", since_load(), bytes / 1e9, note, now_ms() - t_ar);
+        }
+    }
+    *usable = true;
     return KATGPU_OK;
 }
-#define KG_LDS_ATTR(K, BYTES) do { int rc__ = ensure_lds_attr(c, reinterpret_cast<const void*>(K), (BYTES)); if (rc__) return rc__; } while (0)
+// a partition call is using the arena: pool_alloc must not free it to satisfy a table growth
+struct ArenaBusy { katgpu_ctx* c; explicit ArenaBusy(katgpu_ctx* c_) : c(c_) { c->arena_busy = true; } ~ArenaBusy() { c->arena_busy = false; } };
+template <typename T> static T* carve(uint8_t*& a, size_t bytes) { T* p = (T*)a; a += align_up(bytes, 256); return p; }      // (the arena's small arrays: 256-byte steps)
+
+// A launch with dynamic LDS: the kernel's ceiling is raised once per device (c->lds_attr holds the kernels done).
 constexpr size_t LDS_BYTES = 160 * 1024, LDS_GRANULE = 1280;     // gfx950: 160 KB per CU, allocated in 320-dword granules
+template <typename K, typename... Args>
+static int launch_lds(katgpu_ctx* c, K kern, dim3 grid, dim3 block, size_t lds, size_t ceiling, Args... args) {
+    if (!c->lds_attr.count(reinterpret_cast<const void*>(kern))) {
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ceiling));
+        c->lds_attr.insert(reinterpret_cast<const void*>(kern));
+    }
+    hipLaunchKernelGGL(kern, grid, block, lds, c->stream, args...);
+    return KATGPU_OK;
+}
+
+// The cycle-stamp diagnostics (KATGPU_L1B_STAMP, _P2X_STAMP, _P2_STAMP, _APPLY_STAMP): a kernel's STAMP instantiation adds its cycles per phase
+// into n counters of the arena's small area (`dev`, behind spill_n; the last of the n counts tiles).  They are zeroed in front of the launch,
+// fetched after it (a synchronisation: these are diagnostics) and every phase's share of phases [0, n_sum) is printed.  line == nullptr: the
+// apply's seven ([0] fill, [1] walk, [2] of it drains, [3] wait for the other waves + sweep, [4] write-back, [5] regions, [6] chunks).
+struct StampLine { const char* head; int n_shown, n_sum; const char* phase[9]; /* a phase's text around its "%.*f" */ int digits; };
+static const StampLine STAMPS_L1B = {"[katgpu] level-1 (blocks) stamps (wave 0 of every workgroup, cycles summed):", 9, 9,
+    {" codes %.*f %%", "  blocks out %.*f %%", " (+ barrier %.*f %%)", "  sweep %.*f %%", " (+ %.*f %%)", "  per bucket %.*f %%", " (+ %.*f %%)", "  placing %.*f %%", " (+ %.*f %%)"}, 1};
+static const StampLine STAMPS_P2X = {"[katgpu] level-2 (blocks in, blocks out) stamps (wave 0 of every workgroup, cycles summed):", 7, 9,
+    {" wait for the tile %.*f %%", " (+ barrier %.*f %%)", "  ranking + blocks out %.*f %%", " (+ %.*f %%)", "  per sub-bucket %.*f %%", " (+ %.*f %%)", "  placing %.*f %%"}, 1};
+static const StampLine STAMPS_P2 = {"[katgpu] level-2 stamps (lane 0 of every workgroup, cycles summed):", 5, 5,
+    {" wait for the tile %.*f %%", "  digit + rank %.*f %%", "  scan %.*f %%", "  staging %.*f %%", "  copy-out %.*f %%"}, 0};
+constexpr int STAMP_AT_APPLY = 8, STAMP_AT = 16;             // where they lie, in counters behind spill_n: the apply's seven, the others' (at most ten)
+template <typename Launch>
+static int with_stamps(katgpu_ctx* c, unsigned long long* dev, int n, const StampLine* line, Launch launch) {
+    unsigned long long st[10];
+    HIPCHK(c, hipMemsetAsync(dev, 0, n * sizeof(unsigned long long), c->stream));
+    int rc = launch(dev);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(st, dev, n * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    double tot = line ? 0 : (double)(st[0] + st[1] + st[3] + st[4]);
+    if (!line && st[5])
+        fprintf(stderr, "[katgpu] apply stamps (wave 0 of every workgroup, cycles summed): fill %.3g (%.0f %%)  walk %.3g (%.0f %%; drains %.0f %% of the walk)  barrier + sweep %.3g (%.0f %%)  write-back %.3g (%.0f %%); %llu regions, %.1f chunks per wave and region, %.0f cycles per region\n",
+                (double)st[0], 100 * st[0] / tot, (double)st[1], 100 * st[1] / tot, 100.0 * st[2] / std::max(1.0, (double)st[1]), (double)st[3], 100 * st[3] / tot, (double)st[4], 100 * st[4] / tot, st[5], (double)st[6] / st[5], tot / st[5]);
+    if (!line || !st[n - 1]) return KATGPU_OK;
+    for (int i = 0; i < line->n_sum; ++i) tot += (double)st[i];
+    char buf[768];
+    int at = snprintf(buf, sizeof buf, "%s", line->head);
+    for (int i = 0; i < line->n_shown; ++i) at += snprintf(buf + at, sizeof buf - at, line->phase[i], line->digits, 100 * st[i] / tot);
+    fprintf(stderr, "%s; %llu tiles, %.0f cycles per tile\n", buf, st[n - 1], tot / st[n - 1]);
+    return KATGPU_OK;
+}
 
 // Level 3 of a pass: one workgroup per region of buckets [g.b_lo, g.b_hi) -- region into LDS, its run applied, region written back
 // (kg_partition.hpp: k_p3_apply_pk for packed tables, k_p3_apply2 for KV12).  A table's first round claims its new k-mers inside
 // the probe rounds (INLINE_CLAIM); the test suite's spill hook has its own instantiations.
+struct ApplyLaunch {                                         // what every instantiation is launched with
+    katgpu_table* t; const PartGeom& g; const uint64_t* off2; const uint8_t* l2_buf; uint64_t* spill_buf; unsigned long long* spill_n; const uint32_t* run_len; const uint64_t* bucket_end;
+    dim3 grid; size_t lds; uint32_t qcap; uint64_t seg_len; uint32_t zero_fill;
+};
+template <int B, int KP, int HB, bool INL, bool HK, bool PF, int NR, bool STAMP = false>
+static int apply_pk(const ApplyLaunch& a) {
+    return launch_lds(a.t->ctx, k_p3_apply_pk<B, KP, HB, INL, HK, PF, NR, STAMP>, a.grid, dim3(B), a.lds, LDS_BYTES - 256, a.t->dv, a.g, a.off2, a.l2_buf, a.spill_buf, a.spill_n, a.run_len, a.bucket_end,
+                      a.qcap, a.seg_len, g_test_spill_mod, a.zero_fill);
+}
+// probe rounds before the queue: 2 (measured at the bench size, same box: 163 ms per step against 177 with 3 and 198 with inline
+// claims in every round); a table's first round claims inline and keeps 3
+template <int HB>
+static int apply_pk_shape(const ApplyLaunch& a, uint32_t blk, bool fresh, bool hooked) {
+    if (hooked) return apply_pk<1024, 5, HB, false, true, true, 3>(a);
+    if (blk == 1024) return fresh ? apply_pk<1024, 5, HB, true, false, true, 3>(a) : apply_pk<1024, 5, HB, false, false, true, 2>(a);
+    if (a.g.S <= 4096) return fresh ? apply_pk<512, 4, HB, true, false, true, 3>(a) : apply_pk<512, 4, HB, false, false, true, 2>(a);
+    if (HB == 1 && g_apply_stamp && !fresh)                  // diagnostic: the bench's shape with cycle stamps (the kernel adds them at spill_n + STAMP_AT_APPLY)
+        return with_stamps(a.t->ctx, a.spill_n + STAMP_AT_APPLY, 7, nullptr, [&](unsigned long long*) { return apply_pk<512, 10, 1, false, false, false, 2, true>(a); });
+    return fresh ? apply_pk<512, 10, HB, true, false, false, 3>(a) : apply_pk<512, 10, HB, false, false, false, 2>(a);
+}
+template <int B, int KP, int HB, bool INL, int QC, bool HK>
+static int apply_kv12(const ApplyLaunch& a) {
+    return launch_lds(a.t->ctx, k_p3_apply2<B, KP, 4, 3, HB, false, INL, true, QC, HK>, a.grid, dim3(B), a.lds, LDS_BYTES - 256, a.t->dev(), a.g, a.off2, a.l2_buf, a.spill_buf, a.spill_n, a.run_len, a.bucket_end,
+                      (unsigned long long*)nullptr, g_test_spill_mod, a.seg_len);
+}
+template <int HB>
+static int apply_kv12_shape(const ApplyLaunch& a, uint32_t blk, bool big, bool fresh, bool hooked) {
+    if (hooked) return apply_kv12<1024, 5, HB, false, AP2_QCAP_BIG, true>(a);
+    if (blk == 512 && a.g.S <= 2048) return fresh ? apply_kv12<512, 2, HB, true, AP2_QCAP, false>(a) : apply_kv12<512, 2, HB, false, AP2_QCAP, false>(a);
+    if (blk == 512) return fresh ? apply_kv12<512, 4, HB, true, AP2_QCAP, false>(a) : apply_kv12<512, 4, HB, false, AP2_QCAP, false>(a);
+    if (big) return fresh ? apply_kv12<1024, 5, HB, true, AP2_QCAP_BIG, false>(a) : apply_kv12<1024, 5, HB, false, AP2_QCAP_BIG, false>(a);
+    return fresh ? apply_kv12<1024, 4, HB, true, AP2_QCAP, false>(a) : apply_kv12<1024, 4, HB, false, AP2_QCAP, false>(a);
+}
 static int launch_apply(katgpu_table* t, const PartGeom& g, const uint64_t* off2, const uint8_t* l2_buf, uint64_t* spill_buf, unsigned long long* spill_n,
                         const uint32_t* run_len, const uint64_t* bucket_end) {
     katgpu_ctx* c = t->ctx;
     const uint32_t n_cu = (uint32_t)c->n_cu, regions = (g.b_hi - g.b_lo) * g.P2;
-    const bool fresh = t->distinct == 0 && !g_apply_noinline;
+    const bool fresh = t->distinct == 0;                     // (inline claims in a table's first round)
     const bool hooked = g_test_spill_mod != 0;
+    ApplyLaunch a{t, g, off2, l2_buf, spill_buf, spill_n, run_len, bucket_end, dim3(1), 0, 0, 0, 0};
+    int rc = KATGPU_OK;
     if (g.cbits) {
         // 512-thread workgroups, as many per CU as the LDS holds next to their queues (two at the bench's 9344-slot regions, four for
         // small regions); one of 1024 threads when a region leaves no room for a second
@@ -207,69 +303,364 @@ static int launch_apply(katgpu_table* t, const PartGeom& g, const uint64_t* off2
         uint32_t per_cu = 4;
         // room for the queues of eight waves: 96 entries each for a third and fourth workgroup, 72 for the second -- a second workgroup is worth
         // short queues (config 5's 9656-slot regions leave exactly 72: apply 103.5 -> 98.2 ms per step against one 1024-thread workgroup)
-        auto min_q = [&](uint32_t wgs) -> long { return 8L * 8 * (wgs == 2 ? std::max<uint32_t>(g_apply_min_q, 72) : 96); };
+        auto min_q = [&](uint32_t wgs) -> long { return 8L * 8 * (wgs == 2 ? 72 : 96); };
         while (per_cu > 1 && room(per_cu) < min_q(per_cu)) --per_cu;
         if (g_apply_per_cu) per_cu = std::min(per_cu, g_apply_per_cu);
         uint32_t blk = per_cu == 1 ? 1024 : 512;
-        if (g_apply_block == 512 || g_apply_block == 1024) blk = g_apply_block;
         if (hooked) { blk = 1024; per_cu = 1; }
         per_cu = std::min<uint32_t>(per_cu, 2048 / blk);
         const uint32_t nw = blk / 64;
         while (per_cu > 1 && room(per_cu) < (long)(nw * 72 * 8)) --per_cu;
-        const uint32_t qcap = (uint32_t)std::min<long>(256, room(per_cu) / (long)(nw * 8));
-        if (qcap < 72) return fail(c, KATGPU_ERR_DEVICE, "a region of %u packed slots leaves no room for the apply kernel's queues", g.S);
-        const size_t lds = region_b + (size_t)nw * qcap * 8;
+        a.qcap = (uint32_t)std::min<long>(256, room(per_cu) / (long)(nw * 8));
+        if (a.qcap < 72) return fail(c, KATGPU_ERR_DEVICE, "a region of %u packed slots leaves no room for the apply kernel's queues", g.S);
+        a.lds = region_b + (size_t)nw * a.qcap * 8;
         const uint64_t seg_cap = (pk_half(g.cbits) - 1) & ~3ULL;                              // a walk adds less than half the count range
-        const uint64_t seg_len = g_test_ap_seg ? std::min<uint64_t>(g_test_ap_seg, seg_cap) : std::min<uint64_t>(AP2_SEGMENT, seg_cap);
-        const dim3 grid(std::min<uint32_t>(regions, n_cu * per_cu));
+        a.seg_len = g_test_ap_seg ? std::min<uint64_t>(g_test_ap_seg, seg_cap) : std::min<uint64_t>(AP2_SEGMENT, seg_cap);
+        a.grid = dim3(std::min<uint32_t>(regions, n_cu * per_cu));
         // A table whose slots have not been cleared yet (katgpu_table::zero_from): this pass is their first sweep when its regions are the
         // next in line -- the kernel starts every region of the pass from zeros and writes every one back; else they are cleared now.
         const uint64_t r_lo = (uint64_t)g.b_lo * g.P2, r_hi = (uint64_t)g.b_hi * g.P2;
-        uint32_t zero_fill = 0;
-        if (t->zero_from != ~0ULL) { if (t->zero_from == r_lo) zero_fill = 1; else t->zero_rest(); }
-#define KG_APK(B, KP, HB, INL, HK, PF, NR) do { KG_LDS_ATTR((k_p3_apply_pk<B, KP, HB, INL, HK, PF, NR>), LDS_BYTES - 256); \
-            hipLaunchKernelGGL((k_p3_apply_pk<B, KP, HB, INL, HK, PF, NR>), grid, dim3(B), lds, c->stream, t->dv, g, off2, l2_buf, spill_buf, spill_n, run_len, bucket_end, \
-                               qcap, seg_len, g_test_spill_mod, zero_fill); } while (0)
-        // probe rounds before the queue: 2 (measured at the bench size, same box: 163 ms per step against 177 with 3 and 198 with inline
-        // claims in every round); a table's first round claims inline and keeps 3
-#define KG_APK_SHAPE(HB) case HB: \
-            if (hooked) KG_APK(1024, 5, HB, false, true, true, 3); \
-            else if (blk == 1024) { if (fresh) KG_APK(1024, 5, HB, true, false, true, 3); else KG_APK(1024, 5, HB, false, false, true, 2); } \
-            else if (g.S <= 4096) { if (fresh) KG_APK(512, 4, HB, true, false, true, 3); else KG_APK(512, 4, HB, false, false, true, 2); } \
-            else if (HB == 1 && g_apply_nr == 1 && !fresh) KG_APK(512, 10, 1, false, false, false, 1); \
-            else if (HB == 1 && g_apply_nr == 3 && !fresh) KG_APK(512, 10, 1, false, false, false, 3); \
-            else if (HB == 1 && g_apply_stamp && !fresh) { KG_LDS_ATTR((k_p3_apply_pk<512, 10, 1, false, false, false, 2, true>), LDS_BYTES - 256); \
-                hipLaunchKernelGGL((k_p3_apply_pk<512, 10, 1, false, false, false, 2, true>), grid, dim3(512), lds, c->stream, t->dv, g, off2, l2_buf, spill_buf, spill_n, run_len, bucket_end, qcap, seg_len, g_test_spill_mod, zero_fill); } \
-            else { if (fresh) KG_APK(512, 10, HB, true, false, false, 3); else KG_APK(512, 10, HB, false, false, false, 2); } \
-            break;
-        switch (g.hb) { KG_APK_SHAPE(0) KG_APK_SHAPE(1) KG_APK_SHAPE(2) default: return fail(c, KATGPU_ERR_DEVICE, "packed apply: item width %u", g.hb); }
-#undef KG_APK_SHAPE
-#undef KG_APK
+        if (t->zero_from != ~0ULL) { if (t->zero_from == r_lo) a.zero_fill = 1; else t->zero_rest(); }
+        switch (g.hb) {
+        case 0: rc = apply_pk_shape<0>(a, blk, fresh, hooked); break;
+        case 1: rc = apply_pk_shape<1>(a, blk, fresh, hooked); break;
+        case 2: rc = apply_pk_shape<2>(a, blk, fresh, hooked); break;
+        default: return fail(c, KATGPU_ERR_DEVICE, "packed apply: item width %u", g.hb);
+        }
+        if (rc) return rc;
         HIPCHK(c, hipGetLastError());
-        if (zero_fill) t->zero_from = r_hi >= t->dv.n_regions ? ~0ULL : r_hi;      // (regions [r_lo, r_hi) have had their first sweep)
+        if (a.zero_fill) t->zero_from = r_hi >= t->dv.n_regions ? ~0ULL : r_hi;      // (regions [r_lo, r_hi) have had their first sweep)
         return KATGPU_OK;
     }
     // KV12: as many workgroups per CU as the regions' LDS footprint (and the 2048-thread limit) admits
-    const uint32_t blk = hooked ? 1024 : g_apply_block ? g_apply_block : (g.S <= 4096 ? 512 : 1024);
+    const uint32_t blk = hooked ? 1024 : (g.S <= 4096 ? 512 : 1024);
     const bool big = g.S > 8192 || hooked;
-    const size_t lds = (size_t)g.S * 12 + (size_t)(blk / 64) * (big ? AP2_QCAP_BIG : AP2_QCAP) * 12;
-    const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(LDS_BYTES / (lds + 512), 2048 / blk));
-    const dim3 grid(std::min<uint32_t>(regions, n_cu * per_cu));
-    const uint64_t seg_len = g_test_ap_seg ? std::min<uint64_t>(g_test_ap_seg, AP2_SEGMENT) : AP2_SEGMENT;
-#define KG_AP2(B, KP, HB, INL, QC, HK) do { KG_LDS_ATTR((k_p3_apply2<B, KP, 4, 3, HB, false, INL, true, QC, HK>), LDS_BYTES - 256); \
-        hipLaunchKernelGGL((k_p3_apply2<B, KP, 4, 3, HB, false, INL, true, QC, HK>), grid, dim3(B), lds, c->stream, t->dev(), g, off2, l2_buf, spill_buf, spill_n, run_len, bucket_end, \
-                           (unsigned long long*)nullptr, g_test_spill_mod, seg_len); } while (0)
-#define KG_AP2_SHAPE(HB) case HB: \
-        if (hooked) KG_AP2(1024, 5, HB, false, AP2_QCAP_BIG, true); \
-        else if (blk == 512) { if (g.S <= 2048) { if (fresh) KG_AP2(512, 2, HB, true, AP2_QCAP, false); else KG_AP2(512, 2, HB, false, AP2_QCAP, false); } \
-                               else { if (fresh) KG_AP2(512, 4, HB, true, AP2_QCAP, false); else KG_AP2(512, 4, HB, false, AP2_QCAP, false); } } \
-        else if (big) { if (fresh) KG_AP2(1024, 5, HB, true, AP2_QCAP_BIG, false); else KG_AP2(1024, 5, HB, false, AP2_QCAP_BIG, false); } \
-        else { if (fresh) KG_AP2(1024, 4, HB, true, AP2_QCAP, false); else KG_AP2(1024, 4, HB, false, AP2_QCAP, false); } \
-        break;
-    switch (g.hb) { KG_FOR_HB_APPLY(KG_AP2_SHAPE) }
-#undef KG_AP2_SHAPE
-#undef KG_AP2
+    a.lds = (size_t)g.S * 12 + (size_t)(blk / 64) * (big ? AP2_QCAP_BIG : AP2_QCAP) * 12;
+    const uint32_t per_cu = (uint32_t)std::max<size_t>(1, std::min<size_t>(LDS_BYTES / (a.lds + 512), 2048 / blk));
+    a.grid = dim3(std::min<uint32_t>(regions, n_cu * per_cu));
+    a.seg_len = g_test_ap_seg ? std::min<uint64_t>(g_test_ap_seg, AP2_SEGMENT) : AP2_SEGMENT;
+    switch (g.hb) {
+    case 0: rc = apply_kv12_shape<0>(a, blk, big, fresh, hooked); break;
+    case 1: rc = apply_kv12_shape<1>(a, blk, big, fresh, hooked); break;
+    case 2: rc = apply_kv12_shape<2>(a, blk, big, fresh, hooked); break;
+    case 4: rc = apply_kv12_shape<4>(a, blk, big, fresh, hooked); break;
+    }
+    if (rc) return rc;
     HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+// ---- the arena of a call: [hist1 | offs | l1_off | off2 | cnt2 | bend | spill_n, ovf_n | L1 buffer | L2 buffer | overflow list] ----
+// L1 buffer: a round's k-mers + 1/24 + 64 per workgroup and bucket (segment slack of k_p1v2_scatter<true>);
+// L2 buffer: items of 4 + hb bytes in groups of four (kg_partition.hpp "the level-2 buffer"): the L1 count + 1/16 + 16 per region
+// (capacity slack of k_p2_fast) + two items per tile and region (group padding); overflow list: 1/32.
+// 14.8 bytes per k-mer of a round at hb = 1 (k = 27 at the bench size), 18.5 at hb = 4 -- with one pass; the level-2 buffer
+// holds one PASS of level 2 + apply (a CU-full of buckets, see level2_and_apply): 11.7 bytes with two passes.
+constexpr size_t SEG_PAD = 64;
+struct PartArena {
+    // sizes, from the table's geometry (the constructor): item width the level-2 buffer is carved for (a table that grows has more regions: never more
+    // remainder bits), passes of a round (rounded down: the buffer never too small), bytes per k-mer of a round, the fixed parts
+    uint32_t hb, passes; double per_item; size_t fixed_l1, small_bytes;
+    // the carve (carve_from) of an arena for rounds of at most want_items k-mers; the stamp diagnostics' counters lie behind spill_n, ovf_n
+    uint32_t* hist1; uint64_t* offs; uint64_t* l1_off; uint64_t* off2; uint32_t* cnt2; uint64_t* bend; unsigned long long* spill_n; unsigned long long* ovf_n;
+    uint8_t* l1_buf;             // level-1 items, groups of 4, 8 bytes of room per item (kg_partition.hpp "the level-1 buffer")
+    uint8_t* l2_buf;             // level-2 items, groups of 4 (5-byte items: 64-byte blocks of 12)
+    uint64_t* ovf_buf; uint64_t ovf_cap;
+    size_t round_items, l1_items, l2_items;
+    PartArena(const PartGeom& g0, uint32_t W, uint32_t n_cu) : hb(g0.hb), passes(std::max<uint32_t>(1, g0.P1 / pass_buckets(g0.P1, n_cu))), per_item(arena_bytes_per_item(hb, passes)) {
+        fixed_l1 = (size_t)W * MAX_PARTS * SEG_PAD;
+        const size_t fixed_l2 = (size_t)((double)fixed_l1 * l2_items_per_l1_item(hb) / passes) + (size_t)MAX_PARTS * MAX_PARTS * P2_RUN_SLACK + 8192;
+        small_bytes = align_up((size_t)W * MAX_PARTS * 4, 256) + align_up((size_t)W * MAX_PARTS * 8, 256) +   /* W <= 4 * CUs */
+                      align_up((MAX_PARTS + 1) * 8, 256) + align_up(((size_t)MAX_PARTS * MAX_PARTS + 1) * 8, 256) +
+                      align_up((size_t)MAX_PARTS * MAX_PARTS * 4, 256) + align_up((size_t)MAX_PARTS * 8, 256) + align_up((size_t)MAX_PARTS * 4, 256) + 256 +
+                      (fixed_l1 + fixed_l2 + 4096) * 8 + 4096;
+    }
+    void carve_from(uint8_t* a, size_t arena_bytes, uint32_t W, size_t want_items) {
+        hist1 = carve<uint32_t>(a, (size_t)W * MAX_PARTS * 4);
+        offs = carve<uint64_t>(a, (size_t)W * MAX_PARTS * 8);
+        l1_off = carve<uint64_t>(a, (MAX_PARTS + 1) * 8);
+        off2 = carve<uint64_t>(a, ((size_t)MAX_PARTS * MAX_PARTS + 1) * 8);
+        cnt2 = carve<uint32_t>(a, (size_t)MAX_PARTS * MAX_PARTS * 4);
+        bend = carve<uint64_t>(a, (size_t)MAX_PARTS * 8);
+        carve<uint32_t>(a, (size_t)MAX_PARTS * 4);
+        spill_n = carve<unsigned long long>(a, 256);
+        ovf_n = spill_n + 1;
+        round_items = std::min<size_t>(want_items, (size_t)((double)(arena_bytes - small_bytes) / per_item));
+        l1_items = (round_items + round_items / 24 + fixed_l1 + 15) & ~(size_t)15;      // (a multiple of 16: the level-2 buffer starts on a 128-byte boundary)
+        l2_items = ((size_t)((double)l1_items * l2_items_per_l1_item(hb) / passes) + (size_t)MAX_PARTS * MAX_PARTS * P2_RUN_SLACK + 4096 + 11) / 12 * 12;
+        l1_buf = a;
+        l2_buf = l1_buf + l1_items * 8;
+        ovf_buf = (uint64_t*)(l2_buf + align_up(l2_buffer_bytes(hb, l2_items), 16));
+        ovf_cap = g_test_p2_ovf_cap ? g_test_p2_ovf_cap : round_items / 32 + 1024;
+    }
+};
+// level 1 tallies the all-ones key of what it reads (k = 32, not canonical; the segmented editions always write the counter): a round that is
+// abandoned or repeated puts the table's own tally back
+static int restore_ones(katgpu_table* t) { katgpu_ctx* c = t->ctx; HIPCHK(c, hipMemcpyAsync(&t->dv.ctrs[CTR_ONES], &t->ones, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream)); return KATGPU_OK; }
+// Rounds are sized in ITEMS (valid k-mers), not window starts: a cheap pre-count of a prefix measures items/starts
+// (0.82 for 150 bp reads at k=27) so that the buffers are filled and the table is swept as few times as possible.
+static int probe_items_per_start(katgpu_table* t, const PartGeom& g, const PartArena& A, uint32_t W, const uint8_t* p, size_t left, double* items_per_start) {
+    katgpu_ctx* c = t->ctx;
+    const size_t probe_m = std::min<size_t>(left, (size_t)64 << 20) / P1_TILE_STARTS * P1_TILE_STARTS;
+    const uint64_t pt = probe_m / P1_TILE_STARTS, ptw = (pt + W - 1) / W;
+    hipLaunchKernelGGL(k_p1v2_count, dim3(W), dim3(P1_BLOCK), 0, c->stream, t->dv, g, p, (uint64_t)(probe_m + t->dv.k - 1), pt, ptw, A.hist1);
+    hipLaunchKernelGGL(k_p1_scan, dim3(1), dim3(PART_BLOCK), 0, c->stream, g, W, A.hist1, A.offs, A.l1_off);
+    uint64_t probe_items = 0;
+    HIPCHK(c, hipMemcpyAsync(&probe_items, &A.l1_off[g.P1], sizeof probe_items, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *items_per_start = std::max(0.05, (double)probe_items / (double)probe_m);
+    // (the probe's all-ones tally must not count twice: the real count pass over the same prefix follows)
+    return t->dv.k == 32 && !t->dv.canonical ? restore_ones(t) : KATGPU_OK;
+}
+// window starts of the next round, of `left`: what fills the buffers, the remaining rounds balanced
+static size_t round_starts(size_t left, size_t round_items, double items_per_start) {
+    size_t m = left;                                                           // items <= starts: this always fits
+    if (m > round_items) m = std::min(m, (size_t)((double)round_items / items_per_start * 0.98));
+    if (m < left) {
+        const size_t rounds_left = (left + m - 1) / m;
+        m = (left + rounds_left - 1) / rounds_left;
+        m += P1_TILE_STARTS - m % P1_TILE_STARTS;                              // whole tiles, keeps the next round 16-byte aligned
+        m = std::min(m, left);
+    }
+    return m;
+}
+
+// ---- level 1 ----
+// Segmented editions (one pass, fixed-capacity segments) when the round is big enough for their fixed costs; the exact editions
+// (count + scan + scatter) otherwise, and for the rest of the call once a segmented round overflowed.  The segmented edition's BLOCK
+// form (kg_l1_blocks.hpp): 6-byte items in 64-byte blocks of ten, one 1024-thread workgroup per CU, 16 K-base tiles.
+enum class L1Edition { Blocks, SegLean512, SegLean1024, SegPlain512, SegPlain1024, ExactLean, ExactPlain };
+struct L1Plan {
+    L1Edition edition; bool seg /* a segmented edition: level 2 reads segments (blocks of ten from Blocks, else groups) */; uint32_t wgs /* workgroups (<= W: the small arrays hold them) */; uint64_t n_tiles, tiles_per_wg;
+    uint64_t seg_cap, cap_plain, stride64;   // segmented: slots of a segment; k-mers it is expected to take at most (what the spill list must hold: 8 bytes each); bytes of a bucket (l1_bucket_base's + 32)
+};
+static L1Plan plan_level1(const PartGeom& g, uint32_t k, size_t m, uint64_t est_items, uint32_t W, uint32_t n_cu, size_t l1_items, bool seg_wanted) {
+    const bool lean = g_l1_lean && lean_applies(k, g.pl.n1);
+    const bool pb512 = g.P1 <= 512;
+    const bool l1b = lean && pb512 && g.hb1 == 2;
+    const uint64_t n_tiles = (m + P1_TILE_STARTS - 1) / P1_TILE_STARTS;
+    L1Plan pl;
+    pl.wgs = l1b ? n_cu : W;
+    pl.n_tiles = l1b ? (m + L1B_TILE_STARTS - 1) / L1B_TILE_STARTS : n_tiles;
+    uint64_t seg_cap = est_items / ((uint64_t)pl.wgs * g.P1);
+    seg_cap += seg_cap / 24 + SEG_PAD;
+    if (g_test_l1_cpb) seg_cap = std::min<uint64_t>(seg_cap, g_test_l1_cpb);
+    if (l1b) seg_cap = (seg_cap + L1B_ITEMS - 1) / L1B_ITEMS * L1B_ITEMS;       // whole blocks: every slot may hold a k-mer
+    pl.cap_plain = seg_cap;
+    // groups (kg_partition.hpp: k_p1v2_scatter): a bucket's k-mers of a tile are padded to whole groups, 1.5 items per tile and bucket on average
+    if (!l1b && g.hb1 != 4 && !g_test_l1_cpb) seg_cap += std::min<uint64_t>(3 * seg_cap, 2 * ((pl.n_tiles + pl.wgs - 1) / pl.wgs));
+    if (!l1b) seg_cap = (seg_cap + 3) & ~3ULL;                                  // whole groups
+    pl.seg_cap = seg_cap;
+    pl.stride64 = l1b ? align_up(8 * (uint64_t)pl.wgs * pl.cap_plain + 32, 64)      // (blocks start on 64-byte boundaries; 6.4 bytes per item lie inside the 8)
+                      : std::max<uint64_t>(8 * (uint64_t)pl.wgs * pl.cap_plain, (uint64_t)(4 + g.hb1) * pl.wgs * seg_cap) + 32;
+    pl.seg = seg_wanted && pl.stride64 * g.P1 <= (uint64_t)l1_items * 8 &&
+             seg_cap < (1u << 24) && pl.stride64 <= 0xFFFFFFFFULL /* the kernel's segment arithmetic: 24 x 8 and 32 x 32 -> 64 bits */;
+    if (pl.seg) pl.edition = l1b ? L1Edition::Blocks : lean ? (pb512 ? L1Edition::SegLean512 : L1Edition::SegLean1024) : (pb512 ? L1Edition::SegPlain512 : L1Edition::SegPlain1024);
+    else { pl.edition = lean ? L1Edition::ExactLean : L1Edition::ExactPlain; pl.wgs = W; pl.n_tiles = n_tiles; }
+    pl.tiles_per_wg = (pl.n_tiles + pl.wgs - 1) / pl.wgs;
+    return pl;
+}
+static int launch_l1_scatter(katgpu_table* t, const PartGeom& g, const L1Plan& l1, const PartArena& A, const uint8_t* p, uint64_t nb) {
+    katgpu_ctx* c = t->ctx;
+    auto blocks = [&](auto kern, unsigned long long* stamps) {
+        return launch_lds(c, kern, dim3(l1.wgs), dim3(L1B_THREADS), sizeof(P1BLds), sizeof(P1BLds), t->dv, g, p, nb, l1.n_tiles, l1.tiles_per_wg,
+                          A.l1_buf, (uint32_t)(l1.seg_cap / L1B_ITEMS), (uint32_t)l1.stride64, A.ovf_buf, A.ovf_n, A.ovf_cap, stamps);
+    };
+    auto segmented = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(l1.wgs), dim3(P1_BLOCK), 0, c->stream, t->dv, g, p, nb, l1.n_tiles, l1.tiles_per_wg, (const uint64_t*)nullptr, (const uint64_t*)nullptr, A.l1_buf,
+                           (uint32_t)l1.seg_cap, (uint32_t)l1.stride64, (uint32_t)l1.cap_plain, A.ovf_buf, A.ovf_n, A.ovf_cap);
+        return KATGPU_OK;
+    };
+    auto exact = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(l1.wgs), dim3(P1_BLOCK), 0, c->stream, t->dv, g, p, nb, l1.n_tiles, l1.tiles_per_wg, (const uint64_t*)A.offs, (const uint64_t*)A.l1_off, A.l1_buf,
+                           0u, 0u, 0u, (uint64_t*)nullptr, (unsigned long long*)nullptr, (uint64_t)0);
+        return KATGPU_OK;
+    };
+    switch (l1.edition) {
+    case L1Edition::Blocks:
+        if (!g_l1b_stamp) return blocks(k_p1b_scatter<false>, nullptr);
+        return with_stamps(c, A.spill_n + STAMP_AT, 10, &STAMPS_L1B, [&](unsigned long long* st) { return blocks(k_p1b_scatter<true>, st); });
+    case L1Edition::SegLean512:   return segmented(k_p1v2_scatter<true, true, 512>);
+    case L1Edition::SegLean1024:  return segmented(k_p1v2_scatter<true, true, MAX_PARTS>);
+    case L1Edition::SegPlain512:  return segmented(k_p1v2_scatter<true, false, 512>);
+    case L1Edition::SegPlain1024: return segmented(k_p1v2_scatter<true, false, MAX_PARTS>);
+    case L1Edition::ExactLean:    return exact(k_p1v2_scatter<false, true, MAX_PARTS>);
+    case L1Edition::ExactPlain:   return exact(k_p1v2_scatter<false, false, MAX_PARTS>);
+    }
+    return KATGPU_OK;
+}
+// Level 1 of a round of m starts.  A segmented edition: one launch; how many k-mers it wrote is not needed (and not known: *items stays the
+// estimate).  An exact edition: count, scan, scatter; *items = the round's k-mers, and when they are more than the buffers hold (denser than
+// the prefix suggested) nothing is scattered: the caller repeats the round smaller.
+static int level1(katgpu_table* t, const PartGeom& g, const L1Plan& l1, const PartArena& A, const uint8_t* p, size_t m, double items_per_start, uint64_t* items) {
+    katgpu_ctx* c = t->ctx;
+    const uint64_t nb = m + t->dv.k - 1;
+    if (l1.seg) {
+        int rc;
+        { ScopedTimer tm(c, KATGPU_K_PART_L1S, *items); rc = launch_l1_scatter(t, g, l1, A, p, nb); }
+        if (!rc && g_trace) fprintf(stderr, "[katgpu] partition round (segmented level 1%s): %zu starts, ~%llu items, %llu k-mers per segment (arena %.1f GB)\n", l1.edition == L1Edition::Blocks ? ", blocks of ten" : "", m,
+                                    (unsigned long long)*items, (unsigned long long)l1.seg_cap, c->arena_bytes / 1e9);
+        return rc;
+    }
+    {
+        ScopedTimer tm(c, KATGPU_K_PART_L1, m);
+        hipLaunchKernelGGL(k_p1v2_count, dim3(l1.wgs), dim3(P1_BLOCK), 0, c->stream, t->dv, g, p, nb, l1.n_tiles, l1.tiles_per_wg, A.hist1);
+        hipLaunchKernelGGL(k_p1_scan, dim3(1), dim3(PART_BLOCK), 0, c->stream, g, l1.wgs, A.hist1, A.offs, A.l1_off);
+    }
+    HIPCHK(c, hipMemcpyAsync(items, &A.l1_off[g.P1], sizeof *items, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (g_trace) fprintf(stderr, "[katgpu] partition round: %zu starts -> %llu items (buffer %zu items, arena %.1f GB, ratio %.3f)\n", m, (unsigned long long)*items, A.round_items, c->arena_bytes / 1e9, items_per_start);
+    if (*items > A.round_items) return t->dv.k == 32 && !t->dv.canonical ? restore_ones(t) : KATGPU_OK;
+    if (!*items) return KATGPU_OK;
+    ScopedTimer tm(c, KATGPU_K_PART_L1S, *items);
+    return launch_l1_scatter(t, g, l1, A, p, nb);
+}
+
+// ---- level 2 ----
+// One pass over the bucket when the runs are predictable (k_p2_fast, k_p2x_fast: fixed-capacity runs, an overflow list), else -- or when
+// that list did not hold -- the exact two-pass kernel (k_p2).  Which instantiation: the item width g.hb and what level 1 wrote.
+enum class L1Items { Groups /* of four items of at most 48 bits */, WideGroups /* g.hb1 == 4 */, Blocks /* of ten (kg_l1_blocks.hpp) */ };
+struct L2Pass { katgpu_ctx* c; const PartGeom& g; const PartArena& A; uint32_t grid; L1Items src; uint64_t seg_slots; };
+template <typename K>
+static int p2_one_pass(const L2Pass& x, K kern, size_t lds, unsigned long long* stamps = nullptr) {
+    return launch_lds(x.c, kern, dim3(x.grid), dim3(PART_BLOCK), lds, lds, x.g, x.A.l1_off, x.A.l1_buf, x.A.l2_buf, x.A.off2, x.A.cnt2, x.A.ovf_buf, x.A.ovf_n, x.A.ovf_cap, x.seg_slots, stamps);
+}
+template <typename K>
+static int p2_exact(const L2Pass& x, K kern, size_t lds) {
+    return launch_lds(x.c, kern, dim3(x.grid), dim3(PART_BLOCK), lds, lds, x.g, x.A.l1_off, x.A.l1_buf, x.A.l2_buf, x.A.off2, x.seg_slots, x.A.bend);
+}
+template <int HB>
+static int launch_l2_hb(const L2Pass& x, bool one_pass) {
+    constexpr size_t lds_e = sizeof(P2Lds<HB>), lds_f = sizeof(typename P2FastLds<HB>::type);
+    unsigned long long* const stamps = x.A.spill_n + STAMP_AT;
+    switch (x.src) {
+    case L1Items::Blocks:
+        if constexpr (HB == 4) break;
+        else if (!one_pass) return p2_exact(x, k_p2<HB, false, true>, lds_e);
+        else if constexpr (HB != 1) return p2_one_pass(x, k_p2_fast<HB, false, false, true>, lds_f);
+        else if (!g_p2x_stamp) return p2_one_pass(x, k_p2x_fast<false>, sizeof(P2XLds));             // the bench's shape: kg_l2_blocks.hpp
+        else return with_stamps(x.c, stamps, 10, &STAMPS_P2X, [&](unsigned long long* st) { return p2_one_pass(x, k_p2x_fast<true>, sizeof(P2XLds), st); });
+    case L1Items::WideGroups: return one_pass ? p2_one_pass(x, k_p2_fast<HB, true>, lds_f) : p2_exact(x, k_p2<HB, true>, lds_e);
+    case L1Items::Groups:
+        if constexpr (HB == 1) if (one_pass && g_p2_stamp) return with_stamps(x.c, stamps, 6, &STAMPS_P2, [&](unsigned long long* st) { return p2_one_pass(x, k_p2_fast<1, false, true>, lds_f, st); });
+        return one_pass ? p2_one_pass(x, k_p2_fast<HB, false>, lds_f) : p2_exact(x, k_p2<HB, false>, lds_e);
+    }
+    return fail(x.c, KATGPU_ERR_DEVICE, "level 2 from blocked level-1 items: item width %u", x.g.hb);
+}
+static int launch_l2(const L2Pass& x, bool one_pass) {
+    switch (x.g.hb) {
+    case 0: return launch_l2_hb<0>(x, one_pass);
+    case 1: return launch_l2_hb<1>(x, one_pass);
+    case 2: return launch_l2_hb<2>(x, one_pass);
+    case 4: return launch_l2_hb<4>(x, one_pass);
+    }
+    return fail(x.c, KATGPU_ERR_DEVICE, "level 2: item width %u", x.g.hb);
+}
+// What the overflow counter says once a pass's one-pass level 2 is through (tried_fast) -- and, in a segmented round's first pass, level 1.
+// *overflowed = entries of the overflow list that are valid now (*ovf_before: those of level 1 and the earlier passes).
+enum class L2Next { UseCnt2 /* the one-pass kernel's runs stand */, Exact /* it did not run */, FallBackExact /* its list did not hold: this pass and all later ones exactly */,
+                    RedoRound /* level 1's list did not hold: the level-1 buffer is incomplete */ };
+static int read_overflow(katgpu_table* t, const PartArena& A, bool seg, bool tried_fast, unsigned long long ovf_l1, const unsigned long long* ovf_before, unsigned long long* overflowed, L2Next* next) {
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipMemcpyAsync(overflowed, A.ovf_n, sizeof *overflowed, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (seg && ovf_l1 > A.ovf_cap) {             // (only ever in the first pass: nothing has been applied yet)
+        if (g_trace) fprintf(stderr, "[katgpu] segmented level 1: %llu k-mers beyond their segments (list holds %llu): exact level 1 from here on\n", ovf_l1, (unsigned long long)A.ovf_cap);
+        *next = L2Next::RedoRound;
+        return restore_ones(t);                  // the scatter tallied the all-ones key
+    }
+    *next = !tried_fast ? L2Next::Exact : *overflowed <= A.ovf_cap ? L2Next::UseCnt2 : L2Next::FallBackExact;
+    if (*next == L2Next::FallBackExact) {
+        if (g_trace) fprintf(stderr, "[katgpu] k_p2_fast: %llu k-mers beyond their runs (list holds %llu): exact level 2 from here on\n", *overflowed, (unsigned long long)A.ovf_cap);
+        *overflowed = *ovf_before;               // what was on the list before this pass is still there and still valid
+        HIPCHK(c, hipMemcpyAsync(A.ovf_n, ovf_before, sizeof *ovf_before, hipMemcpyHostToDevice, c->stream));
+    }
+    return KATGPU_OK;
+}
+
+// Level 2 + apply of a round, in passes over sets of buckets: the level-2 buffer holds one pass (PartArena), a pass is a whole number of
+// CU-fulls of buckets where the geometry allows (alloc_dev_table).  *lists: the k-mers that found no place (in parts of the arena that are dead).
+enum class RoundEnd { Done, RedoExactL1 /* nothing was applied: the round again with an exact level 1 */, DirectPath /* a single bucket beyond the buffer */ };
+static int level2_and_apply(katgpu_table* t, PartGeom& g, const L1Plan& l1, const PartArena& A, uint64_t items, bool* p2_fast_ok, KeyLists* lists, RoundEnd* end) {
+    katgpu_ctx* c = t->ctx;
+    const bool seg = l1.seg;
+    const uint64_t seg_slots = seg ? (uint64_t)l1.wgs * l1.seg_cap : 0;        // items of one bucket
+    const L1Items src = seg && l1.edition == L1Edition::Blocks ? L1Items::Blocks : g.hb1 == 4 ? L1Items::WideGroups : L1Items::Groups;
+    *end = RoundEnd::Done;
+    std::vector<uint64_t> h_l1_off;                                            // where bucket b starts in the level-1 buffer (exact level 1)
+    unsigned long long ovf_l1 = 0;                                             // k-mers beyond their segments (segmented level 1)
+    if (!seg) {
+        h_l1_off.resize(g.P1 + 1);
+        HIPCHK(c, hipMemcpyAsync(h_l1_off.data(), A.l1_off, (g.P1 + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    } else HIPCHK(c, hipMemcpyAsync(&ovf_l1, A.ovf_n, sizeof ovf_l1, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    auto lbeg = [&](uint32_t b) -> uint64_t { return seg ? (uint64_t)b * g.l1_real : h_l1_off[b]; };      // k-mers before bucket b (segmented: their bound)
+    const uint32_t tile2 = l2_tile_items(g.hb);
+    auto pass_extent = [&](uint32_t b_lo, uint32_t b_hi) -> uint64_t {       // bound of what level 2 writes for these buckets, in items (either edition)
+        const uint64_t nn = lbeg(b_hi) - lbeg(b_lo);
+        return nn + nn / 16 + 2ULL * g.P2 * (nn / tile2 + 1) + (uint64_t)(b_hi - b_lo) * g.P2 * P2_RUN_SLACK + 64;
+    };
+    uint32_t step = pass_buckets(g.P1, (uint32_t)c->n_cu);
+    auto fits = [&](uint32_t st) { for (uint32_t b = 0; b < g.P1; b += st) if (pass_extent(b, std::min(g.P1, b + st)) > A.l2_items) return false; return true; };
+    while (step > 1 && !fits(step)) step = (step + 1) / 2;
+    if (!fits(step)) {
+        *end = RoundEnd::DirectPath;
+        // this round's level 1 (either edition) has tallied the all-ones key of its starts, which the direct kernel will count again
+        return seg || (t->dv.k == 32 && !t->dv.canonical) ? restore_ones(t) : KATGPU_OK;
+    }
+    const bool try_fast0 = *p2_fast_ok && (g_p2_fast == 2 || items / g.R >= 1024);
+    unsigned long long ovf_total = ovf_l1;                                 // entries of the overflow list so far (level 1's, then every pass's)
+    if (g_trace && g.P1 > step) fprintf(stderr, "[katgpu]   level 2 + apply in %u passes of %u buckets (level-2 buffer: %zu items)\n", (g.P1 + step - 1) / step, step, A.l2_items);
+    for (uint32_t b_lo = 0; b_lo < g.P1; b_lo += step) {
+        g.b_lo = b_lo; g.b_hi = std::min(g.P1, b_lo + step);
+        const uint64_t pass_items = std::max<uint64_t>(1, (uint64_t)((double)items * (g.b_hi - g.b_lo) / g.P1));
+        // this pass's part of the level-1 buffer, dead once its level 2 is through: the pass's spill list (room for 8 bytes per k-mer)
+        auto l1_at = [&](uint32_t b) -> uint64_t { return seg ? (uint64_t)b * g.l1_stride : l1_bucket_base(lbeg(b), b); };
+        uint64_t* spill_buf = (uint64_t*)(A.l1_buf + l1_at(b_lo));
+        g.spill_cap = (l1_at(g.b_hi) - l1_at(b_lo)) / 8;
+        const bool try_fast = try_fast0 && *p2_fast_ok;
+        const L2Pass x{c, g, A, std::min<uint32_t>(g.b_hi - g.b_lo, (uint32_t)c->n_cu), src, seg_slots};      // one workgroup per CU
+        HIPCHK(c, hipMemsetAsync(A.spill_n, 0, sizeof(unsigned long long), c->stream));
+        int rc = KATGPU_OK;
+        if (try_fast) { ScopedTimer tm(c, KATGPU_K_PART_L2, pass_items); rc = launch_l2(x, true); }
+        if (rc) return rc;
+        L2Next next = L2Next::Exact;
+        unsigned long long overflowed = ovf_total;
+        if (try_fast || (seg && b_lo == 0)) {
+            rc = read_overflow(t, A, seg, try_fast, ovf_l1, &ovf_total, &overflowed, &next);
+            if (rc) return rc;
+            if (next == L2Next::RedoRound) { *end = RoundEnd::RedoExactL1; return KATGPU_OK; }
+            if (next == L2Next::FallBackExact) *p2_fast_ok = false;
+        }
+        const bool runs = next == L2Next::UseCnt2;                             // the one-pass kernel's runs have their lengths in cnt2
+        if (!runs) { ScopedTimer tm(c, KATGPU_K_PART_L2, pass_items); rc = launch_l2(x, false); }
+        if (rc) return rc;
+        ovf_total = overflowed;
+        {   // (exact level 2: a bucket's runs stop short of the next bucket's -- bend)
+            ScopedTimer tm(c, KATGPU_K_PART_APPLY, pass_items);
+            rc = launch_apply(t, g, A.off2, A.l2_buf, spill_buf, A.spill_n, runs ? A.cnt2 : nullptr, runs ? nullptr : A.bend);
+        }
+        if (rc) return rc;
+        HIPCHK(c, hipGetLastError());
+        unsigned long long spilled = 0;
+        HIPCHK(c, hipMemcpyAsync(&spilled, A.spill_n, sizeof spilled, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (spilled > g.spill_cap)       // (more k-mers without a slot than the pass's segments were sized for: a table far too small, met by a 5-sigma round)
+            return fail(c, KATGPU_ERR_TABLE_FULL, "Hash full: %llu k-mers of a partition pass found no slot (the list holds %llu); raise the size hint", spilled, (unsigned long long)g.spill_cap);
+        if (spilled) lists->push_back({spill_buf, spilled});
+    }
+    if (ovf_total) lists->push_back({A.ovf_buf, ovf_total});                // what level 1 / level 2 could not place
+    return KATGPU_OK;
+}
+// regions that ran out of slots, runs beyond their capacity: make room, then the direct path
+static int insert_spilled(katgpu_table* t, const KeyLists& lists, bool* arena_lost) {
+    *arena_lost = false;
+    if (lists.empty()) return KATGPU_OK;
+    uint64_t total = 0;
+    for (auto& l : lists) total += l.second;
+    int rc = grow_beside_arena(t, total, 0, lists, 8, arena_lost);
+    if (rc || *arena_lost) return rc;          // (lost: the lists went in from the host)
+    for (auto& l : lists) insert_keys(t, l.first, l.second, 8);
     return KATGPU_OK;
 }
 
@@ -277,7 +668,7 @@ static int launch_apply(katgpu_table* t, const PartGeom& g, const uint64_t* off2
 // (all of them unless the geometry stops fitting, in which case the caller finishes with the direct kernel).
 static int count_partitioned(katgpu_table* t, const uint8_t* dev_bases, size_t n, size_t* done) {
     katgpu_ctx* c = t->ctx;
-    const uint32_t k = t->dv.k;
+    const uint32_t k = t->dv.k, n_cu = (uint32_t)c->n_cu;
     const size_t n_starts = n - k + 1;
     *done = 0;
     c->arena_borrowed = false;                    // a borrowed arena is only promised until the next count call
@@ -289,363 +680,68 @@ static int count_partitioned(katgpu_table* t, const uint8_t* dev_bases, size_t n
         int grc = regrow(t, nc);
         if (grc) return grc;
     }
-    const uint32_t W = (uint32_t)c->n_cu * std::min<uint32_t>(g_p1_wgs, 4);                     // level-1 workgroups (rows of hist1 / offs)
-    const uint32_t W2 = (uint32_t)c->n_cu;                                                      // level-2 / apply: one per CU
-    const size_t tile_starts = P1_TILE_STARTS;
-#define KG_FOR_HB(M) M(0) M(1) M(2) M(4)
-    if (!c->part_attr_set) {
-#define KG_ATTR_HB(HB) KG_LDS_ATTR((k_p2<HB, false>), sizeof(P2Lds<HB>)); KG_LDS_ATTR((k_p2_fast<HB, false>), sizeof(P2FastLds<HB>::type)); \
-                       KG_LDS_ATTR((k_p2<HB, true>), sizeof(P2Lds<HB>)); KG_LDS_ATTR((k_p2_fast<HB, true>), sizeof(P2FastLds<HB>::type));
-        KG_FOR_HB(KG_ATTR_HB)
-#undef KG_ATTR_HB
-        c->part_attr_set = true;
-    }
-    // ---- arena: [hist1 | offs | l1_off | off2 | cnt2 | bend | spill_n, ovf_n | L1 buffer | L2 buffer | overflow list] ----
-    // L1 buffer: a round's k-mers + 1/24 + 64 per workgroup and bucket (segment slack of k_p1v2_scatter<true>);
-    // L2 buffer: items of 4 + hb bytes in groups of four (kg_partition.hpp "the level-2 buffer"): the L1 count + 1/16 + 16 per region
-    // (capacity slack of k_p2_fast) + two items per tile and region (group padding); overflow list: 1/32.
-    // 14.8 bytes per k-mer of a round at hb = 1 (k = 27 at the bench size), 18.5 at hb = 4 -- with one pass; the level-2 buffer
-    // holds one PASS of level 2 + apply (a CU-full of buckets, see the rounds below): 11.7 bytes with two passes.
+    const uint32_t W = n_cu * std::min<uint32_t>(g_p1_wgs, 4);                     // level-1 workgroups (rows of hist1 / offs)
     PartGeom g0;
     if (!part_geometry(t->dv, &g0)) return KATGPU_OK;                              // direct path
-    const uint32_t hb0 = g0.hb;                                                  // a table that grows has more regions: never more remainder bits
-    const uint32_t passes0 = std::max<uint32_t>(1, g0.P1 / pass_buckets(g0.P1, (uint32_t)c->n_cu));   // (rounded down: the buffer never too small)
-    const double per_item = arena_bytes_per_item(hb0, passes0);
-    constexpr size_t SEG_PAD = 64;
-    const size_t fixed_l1 = (size_t)W * MAX_PARTS * SEG_PAD;
-    const size_t fixed_l2 = (size_t)((double)fixed_l1 * l2_items_per_l1_item(hb0) / passes0) + (size_t)MAX_PARTS * MAX_PARTS * P2_RUN_SLACK + 8192;
-    const size_t small_bytes = align_up((size_t)W * MAX_PARTS * 4, 256) + align_up((size_t)W * MAX_PARTS * 8, 256) +   /* W <= 4 * CUs */
-                               align_up((MAX_PARTS + 1) * 8, 256) + align_up(((size_t)MAX_PARTS * MAX_PARTS + 1) * 8, 256) +
-                               align_up((size_t)MAX_PARTS * MAX_PARTS * 4, 256) + align_up((size_t)MAX_PARTS * 8, 256) + align_up((size_t)MAX_PARTS * 4, 256) + 256 +
-                               (fixed_l1 + fixed_l2 + 4096) * 8 + 4096;
+    PartArena A(g0, W, n_cu);
     size_t want_items = n_starts;
     if (g_test_round_items) want_items = std::min<size_t>(want_items, g_test_round_items);
-    size_t want_bytes = small_bytes + (size_t)((per_item + 0.5) * (double)want_items);
-    if (c->arena_limit) want_bytes = std::min(want_bytes, std::max(c->arena_limit, small_bytes + 18 * ((size_t)64 << 20)));      // (the file feeders: more rounds, less to allocate)
-    if (c->arena_bytes < want_bytes) {                                           // the arena could be more useful than it is
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-        free_b += c->arena_bytes;
-        size_t bytes = std::min<size_t>(want_bytes, (size_t)(g_arena_fraction * (double)free_b));
-        // re-allocate only for a substantially larger arena (fewer rounds): a fresh hipMalloc of this size is not free
-        if (bytes > c->arena_bytes + c->arena_bytes / 2 || c->arena_bytes < small_bytes + 18 * std::min<size_t>(want_items, (size_t)64 << 20)) {
-            if (c->arena) { HIPCHK(c, hipFree(c->arena)); c->arena = nullptr; c->arena_bytes = 0; }
-            if (!g_test_round_items && bytes < small_bytes + 18 * ((size_t)1 << 20)) return KATGPU_OK;   // no room for a useful round: direct path
-            const double t_ar = now_ms();
-            if (hipMalloc((void**)&c->arena, bytes) != hipSuccess) { (void)hipGetLastError(); c->arena = nullptr; return KATGPU_OK; }   // direct path
-            c->arena_bytes = bytes;
-            if (g_trace) fprintf(stderr, "[katgpu +%.0f ms] partition arena of %.1f GB: %.0f ms\n", since_load(), bytes / 1e9, now_ms() - t_ar);
-        }
-    }
-    struct Busy { katgpu_ctx* c; explicit Busy(katgpu_ctx* c_) : c(c_) { c->arena_busy = true; } ~Busy() { c->arena_busy = false; } } busy(c);
-    uint8_t* a = c->arena;
-    uint32_t* hist1 = (uint32_t*)a;               a += align_up((size_t)W * MAX_PARTS * 4, 256);
-    uint64_t* offs = (uint64_t*)a;                a += align_up((size_t)W * MAX_PARTS * 8, 256);
-    uint64_t* l1_off = (uint64_t*)a;              a += align_up((MAX_PARTS + 1) * 8, 256);
-    uint64_t* off2 = (uint64_t*)a;                a += align_up(((size_t)MAX_PARTS * MAX_PARTS + 1) * 8, 256);
-    uint32_t* cnt2 = (uint32_t*)a;                a += align_up((size_t)MAX_PARTS * MAX_PARTS * 4, 256);
-    uint64_t* bend = (uint64_t*)a;                a += align_up((size_t)MAX_PARTS * 8, 256);
-    a += align_up((size_t)MAX_PARTS * 4, 256);
-    unsigned long long* spill_n = (unsigned long long*)a;
-    unsigned long long* ovf_n = spill_n + 1;      a += 256;
-    if (g_apply_stamp) HIPCHK(c, hipMemset(spill_n + 8, 0, 7 * sizeof(unsigned long long)));
-    const size_t round_items = std::min<size_t>(want_items, (size_t)((double)(c->arena_bytes - small_bytes) / per_item));
-    const size_t l1_items = (round_items + round_items / 24 + fixed_l1 + 15) & ~(size_t)15;      // (a multiple of 16: the level-2 buffer starts on a 128-byte boundary)
-    const size_t l2_items = ((size_t)((double)l1_items * l2_items_per_l1_item(hb0) / passes0) + (size_t)MAX_PARTS * MAX_PARTS * P2_RUN_SLACK + 4096 + 11) / 12 * 12;
-    uint8_t* l1_buf = a;                                                            // level-1 items, groups of 4, 8 bytes of room per item (kg_partition.hpp "the level-1 buffer")
-    uint8_t* l2_buf = l1_buf + l1_items * 8;                                        // level-2 items, groups of 4 (5-byte items: 64-byte blocks of 12)
-    uint64_t* ovf_buf = (uint64_t*)(l2_buf + align_up(l2_buffer_bytes(hb0, l2_items), 16));
-    const uint64_t ovf_cap = g_test_p2_ovf_cap ? g_test_p2_ovf_cap : round_items / 32 + 1024;
+    bool usable = false;
+    int rc = ensure_arena(c, A.small_bytes, 18, want_items, A.small_bytes + (size_t)((A.per_item + 0.5) * (double)want_items), "", &usable);
+    if (rc || !usable) return rc;                                                  // (no arena: direct path)
+    ArenaBusy busy(c);
+    A.carve_from(c->arena, c->arena_bytes, W, want_items);
+    if (!g_test_round_items && A.round_items < ((size_t)1 << 20) && A.round_items < n_starts) return KATGPU_OK;
     bool p2_fast_ok = g_p2_fast != 0, l1_fast_ok = g_l1_fast != 0;
-    if (!g_test_round_items && round_items < ((size_t)1 << 20) && round_items < n_starts) return KATGPU_OK;
-
-    // Rounds are sized in ITEMS (valid k-mers), not window starts: a cheap pre-count of a prefix measures items/starts
-    // (0.82 for 150 bp reads at k=27) so that the buffers are filled and the table is swept as few times as possible.
     double items_per_start = 1.0;
     size_t pos = 0;
     bool ratio_known = false;
     while (pos < n_starts) {
-        int rc = refresh_counters(t);
+        rc = refresh_counters(t);
         if (rc) return rc;
         if ((double)t->distinct > 0.6 * (double)t->dv.cap) {
             bool lost = false;
-            rc = grow_beside_arena(t, 0, t->dv.cap * 2, KeyLists(), &lost);
+            rc = grow_beside_arena(t, 0, t->dv.cap * 2, KeyLists(), 8, &lost);
             if (rc) return rc;
             if (lost) break;                                                      // the caller re-enters with a fresh arena
         }
         PartGeom g;
         if (!part_geometry(t->dv, &g)) break;                                      // table too large for two levels: direct path
-        if (g.hb > hb0) break;                                                    // (cannot happen: see hb0) the level-2 carve would not hold these items
+        if (g.hb > A.hb) break;                                                   // (cannot happen: see PartArena::hb) the level-2 carve would not hold these items
+        const size_t left = n_starts - pos;
+        const uint8_t* p = dev_bases + pos;
         // (the segmented level 1 sizes its segments from this ratio, so it wants it even when one round takes everything)
-        if (!ratio_known && !g_test_round_items && (n_starts - pos > round_items || (l1_fast_ok && n_starts - pos >= ((size_t)64 << 20)))) {
-            const size_t probe_m = std::min<size_t>(n_starts - pos, (size_t)64 << 20) / tile_starts * tile_starts;
-            const uint64_t pt = probe_m / tile_starts, ptw = (pt + W - 1) / W;
-            hipLaunchKernelGGL(k_p1v2_count, dim3(W), dim3(P1_BLOCK), 0, c->stream, t->dv, g, dev_bases + pos, (uint64_t)(probe_m + k - 1), pt, ptw, hist1);
-            hipLaunchKernelGGL(k_p1_scan, dim3(1), dim3(PART_BLOCK), 0, c->stream, g, W, hist1, offs, l1_off);
-            uint64_t probe_items = 0;
-            HIPCHK(c, hipMemcpyAsync(&probe_items, &l1_off[g.P1], sizeof probe_items, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            // (the probe's all-ones tally must not count twice: the real count pass over the same prefix follows)
-            if (t->dv.k == 32 && !t->dv.canonical) HIPCHK(c, hipMemcpyAsync(&t->dv.ctrs[CTR_ONES], &t->ones, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-            items_per_start = std::max(0.05, (double)probe_items / (double)probe_m);
+        if (!ratio_known && !g_test_round_items && (left > A.round_items || (l1_fast_ok && left >= ((size_t)64 << 20)))) {
+            rc = probe_items_per_start(t, g, A, W, p, left, &items_per_start);
+            if (rc) return rc;
             ratio_known = true;
         }
-        size_t m = n_starts - pos;                                                 // items <= starts: this always fits
-        if (m > round_items) m = std::min(m, (size_t)((double)round_items / items_per_start * 0.98));
-        if (m < n_starts - pos) {
-            const size_t rounds_left = (n_starts - pos + m - 1) / m;               // balance the remaining rounds
-            m = (n_starts - pos + rounds_left - 1) / rounds_left;
-            m += tile_starts - m % tile_starts;                                    // whole tiles, keeps the next round 16-byte aligned
-            m = std::min(m, n_starts - pos);
-        }
-        const size_t nb = m + k - 1;
-        const uint8_t* p = dev_bases + pos;
+        const size_t m = round_starts(left, A.round_items, items_per_start);
         t->count_bound = 0xFFFFFFFFULL;          // the apply kernel chains its own carries; a later direct launch sweeps first
-        const uint64_t n_tiles = (m + tile_starts - 1) / tile_starts;
-        const uint64_t tiles_per_wg = (n_tiles + W - 1) / W;
-        // Level 1.  Segmented edition (one pass, fixed-capacity segments) when the round is big enough for its fixed costs; the
-        // exact edition (count + scan + scatter) otherwise, and for the rest of the call once a segmented round overflowed.
         const uint64_t est_items = (uint64_t)((double)m * items_per_start);
-        const bool lean = g_l1_lean && lean_applies(k, g.pl.n1);
-        const bool pb512 = g.P1 <= 512;
-        // The segmented edition's BLOCK form (kg_l1_blocks.hpp): 6-byte items in 64-byte blocks of ten, one 1024-thread workgroup per CU, 16 K-base tiles.
-        const bool l1b = g_l1_blocks && lean && pb512 && g.hb1 == 2;
-        const uint32_t Ws = l1b ? (uint32_t)c->n_cu : W;                            // workgroups of the segmented edition (<= W: the small arrays hold them)
-        const uint64_t n_tiles_s = l1b ? (m + L1B_TILE_STARTS - 1) / L1B_TILE_STARTS : n_tiles;
-        const uint64_t tiles_per_wg_s = (n_tiles_s + Ws - 1) / Ws;
-        uint64_t seg_cap = est_items / ((uint64_t)Ws * g.P1);
-        seg_cap += seg_cap / 24 + SEG_PAD;
-        if (g_test_l1_cpb) seg_cap = std::min<uint64_t>(seg_cap, g_test_l1_cpb);
-        if (l1b) seg_cap = (seg_cap + L1B_ITEMS - 1) / L1B_ITEMS * L1B_ITEMS;       // whole blocks: every slot may hold a k-mer
-        const uint64_t cap_plain = seg_cap;                                         // k-mers a segment is expected to take at most (what the spill list must hold: 8 bytes each)
-        // groups (kg_partition.hpp: k_p1v2_scatter): a bucket's k-mers of a tile are padded to whole groups, 1.5 items per tile and bucket on average
-        if (!l1b && g.hb1 != 4 && !g_test_l1_cpb) seg_cap += std::min<uint64_t>(3 * seg_cap, 2 * tiles_per_wg_s);
-        if (!l1b) seg_cap = (seg_cap + 3) & ~3ULL;                                  // whole groups
-        const uint64_t stride64 = l1b ? align_up(8 * (uint64_t)Ws * cap_plain + 32, 64)      // (blocks start on 64-byte boundaries; 6.4 bytes per item lie inside the 8)
-                                      : std::max<uint64_t>(8 * (uint64_t)Ws * cap_plain, (uint64_t)(4 + g.hb1) * Ws * seg_cap) + 32;   // bytes of a bucket (l1_bucket_base's + 32)
-        const bool seg = l1_fast_ok && (g_l1_fast == 2 || (ratio_known && est_items >= ((uint64_t)64 << 20))) && stride64 * g.P1 <= (uint64_t)l1_items * 8 &&
-                         seg_cap < (1u << 24) && stride64 <= 0xFFFFFFFFULL /* the kernel's segment arithmetic: 24 x 8 and 32 x 32 -> 64 bits */;
-        const uint64_t seg_slots = seg ? (uint64_t)Ws * seg_cap : 0;               // items of one bucket
-        const uint32_t bucket_stride = (uint32_t)stride64;
-        g.l1_stride = seg ? stride64 : 0;
-        g.l1_real = seg ? (uint64_t)Ws * cap_plain : 0;
-        const bool l1_blocked = seg && l1b;                                         // what level 2 reads this round: blocks of ten, or groups
-        uint64_t items = 0;
-        unsigned long long ovf_l1 = 0;
-        HIPCHK(c, hipMemsetAsync(spill_n, 0, 2 * sizeof(unsigned long long), c->stream));          // spill_n, ovf_n
-        if (seg) {
-            items = est_items;                                                    // the exact number is not needed (and not known)
-            {
-                ScopedTimer tm(c, KATGPU_K_PART_L1S, items);
-#define KG_L1S(LEAN, PB) hipLaunchKernelGGL((k_p1v2_scatter<true, LEAN, PB>), dim3(Ws), dim3(P1_BLOCK), 0, c->stream, t->dv, g, p, (uint64_t)nb, n_tiles_s, tiles_per_wg_s, \
-                                               (const uint64_t*)nullptr, (const uint64_t*)nullptr, l1_buf, (uint32_t)seg_cap, bucket_stride, (uint32_t)cap_plain, ovf_buf, ovf_n, ovf_cap)
-                if (l1b) {
-                    if (g_l1b_stamp) {                                             // diagnostic: wave 0's cycles per phase
-                        unsigned long long* stamps = spill_n + 16;
-                        HIPCHK(c, hipMemsetAsync(stamps, 0, 10 * sizeof(unsigned long long), c->stream));
-                        KG_LDS_ATTR(k_p1b_scatter<true>, sizeof(P1BLds));
-                        hipLaunchKernelGGL(k_p1b_scatter<true>, dim3(Ws), dim3(L1B_THREADS), sizeof(P1BLds), c->stream, t->dv, g, p, (uint64_t)nb, n_tiles_s, tiles_per_wg_s,
-                                           l1_buf, (uint32_t)(seg_cap / L1B_ITEMS), bucket_stride, ovf_buf, ovf_n, ovf_cap, stamps);
-                        unsigned long long st[10];
-                        HIPCHK(c, hipMemcpyAsync(st, stamps, sizeof st, hipMemcpyDeviceToHost, c->stream));
-                        HIPCHK(c, hipStreamSynchronize(c->stream));
-                        double tot = 0;
-                        for (int i = 0; i < 9; ++i) tot += (double)st[i];
-                        if (st[9]) fprintf(stderr, "[katgpu] level-1 (blocks) stamps (wave 0 of every workgroup, cycles summed): codes %.1f %%  blocks out %.1f %% (+ barrier %.1f %%)  sweep %.1f %% (+ %.1f %%)  per bucket %.1f %% (+ %.1f %%)  placing %.1f %% (+ %.1f %%); %llu tiles, %.0f cycles per tile\n",
-                                           100 * st[0] / tot, 100 * st[1] / tot, 100 * st[2] / tot, 100 * st[3] / tot, 100 * st[4] / tot, 100 * st[5] / tot, 100 * st[6] / tot, 100 * st[7] / tot, 100 * st[8] / tot, st[9], tot / st[9]);
-                    } else {
-                        KG_LDS_ATTR(k_p1b_scatter<false>, sizeof(P1BLds));
-                        hipLaunchKernelGGL(k_p1b_scatter<false>, dim3(Ws), dim3(L1B_THREADS), sizeof(P1BLds), c->stream, t->dv, g, p, (uint64_t)nb, n_tiles_s, tiles_per_wg_s,
-                                           l1_buf, (uint32_t)(seg_cap / L1B_ITEMS), bucket_stride, ovf_buf, ovf_n, ovf_cap, (unsigned long long*)nullptr);
-                    }
-                } else
-                if (lean) { if (pb512) KG_L1S(true, 512); else KG_L1S(true, MAX_PARTS); }
-                else { if (pb512) KG_L1S(false, 512); else KG_L1S(false, MAX_PARTS); }
-#undef KG_L1S
-            }
-            HIPCHK(c, hipMemcpyAsync(&ovf_l1, ovf_n, sizeof ovf_l1, hipMemcpyDeviceToHost, c->stream));      // read at the next synchronisation
-            if (g_trace) fprintf(stderr, "[katgpu] partition round (segmented level 1%s): %zu starts, ~%llu items, %llu k-mers per segment (arena %.1f GB)\n", l1b ? ", blocks of ten" : "", m, (unsigned long long)items, (unsigned long long)seg_cap, c->arena_bytes / 1e9);
-        } else {
-            {
-                ScopedTimer tm(c, KATGPU_K_PART_L1, m);
-                hipLaunchKernelGGL(k_p1v2_count, dim3(W), dim3(P1_BLOCK), 0, c->stream, t->dv, g, p, (uint64_t)nb, n_tiles, tiles_per_wg, hist1);
-                hipLaunchKernelGGL(k_p1_scan, dim3(1), dim3(PART_BLOCK), 0, c->stream, g, W, hist1, offs, l1_off);
-            }
-            HIPCHK(c, hipMemcpyAsync(&items, &l1_off[g.P1], sizeof items, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (g_trace) fprintf(stderr, "[katgpu] partition round: %zu starts -> %llu items (buffer %zu items, arena %.1f GB, ratio %.3f)\n", m, (unsigned long long)items, round_items, c->arena_bytes / 1e9, items_per_start);
-            if (items > round_items) {                      // denser than the prefix suggested: redo this round smaller
-                if (t->dv.k == 32 && !t->dv.canonical) HIPCHK(c, hipMemcpyAsync(&t->dv.ctrs[CTR_ONES], &t->ones, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-                items_per_start = std::min(1.0, (double)items / (double)m * 1.02);
-                continue;
-            }
-            if (items) {
-                ScopedTimer tm(c, KATGPU_K_PART_L1S, items);
-                if (lean)
-                    hipLaunchKernelGGL((k_p1v2_scatter<false, true>), dim3(W), dim3(P1_BLOCK), 0, c->stream, t->dv, g, p, (uint64_t)nb, n_tiles, tiles_per_wg, (const uint64_t*)offs, (const uint64_t*)l1_off, l1_buf,
-                                       0u, 0u, 0u, (uint64_t*)nullptr, (unsigned long long*)nullptr, (uint64_t)0);
-                else
-                    hipLaunchKernelGGL((k_p1v2_scatter<false, false>), dim3(W), dim3(P1_BLOCK), 0, c->stream, t->dv, g, p, (uint64_t)nb, n_tiles, tiles_per_wg, (const uint64_t*)offs, (const uint64_t*)l1_off, l1_buf,
-                                       0u, 0u, 0u, (uint64_t*)nullptr, (unsigned long long*)nullptr, (uint64_t)0);
-            }
+        const bool seg_wanted = l1_fast_ok && (g_l1_fast == 2 || (ratio_known && est_items >= ((uint64_t)64 << 20)));
+        const L1Plan l1 = plan_level1(g, k, m, est_items, W, n_cu, A.l1_items, seg_wanted);
+        g.l1_stride = l1.seg ? l1.stride64 : 0;
+        g.l1_real = l1.seg ? (uint64_t)l1.wgs * l1.cap_plain : 0;
+        HIPCHK(c, hipMemsetAsync(A.spill_n, 0, 2 * sizeof(unsigned long long), c->stream));          // spill_n, ovf_n
+        uint64_t items = est_items;
+        rc = level1(t, g, l1, A, p, m, items_per_start, &items);
+        if (rc) return rc;
+        if (!l1.seg && items > A.round_items) {   // (exact level 1) denser than the prefix suggested: redo this round smaller
+            items_per_start = std::min(1.0, (double)items / (double)m * 1.02);
+            continue;
         }
         if (items) {
-            // Level 2 + apply, in passes over sets of buckets: the level-2 buffer holds one pass (arena sizing above), a pass is a whole
-            // number of CU-fulls of buckets where the geometry allows (alloc_dev_table).  Where bucket b starts in the level-1 buffer:
-            std::vector<uint64_t> h_l1_off;
-            if (!seg) {
-                h_l1_off.resize(g.P1 + 1);
-                HIPCHK(c, hipMemcpyAsync(h_l1_off.data(), l1_off, (g.P1 + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-            }
-            auto lbeg = [&](uint32_t b) -> uint64_t { return seg ? (uint64_t)b * g.l1_real : h_l1_off[b]; };      // k-mers before bucket b (segmented: their bound)
-            const uint32_t tile2 = l2_tile_items(g.hb);
-            auto pass_extent = [&](uint32_t b_lo, uint32_t b_hi) -> uint64_t {       // bound of what level 2 writes for these buckets, in items (either edition)
-                const uint64_t nn = lbeg(b_hi) - lbeg(b_lo);
-                return nn + nn / 16 + 2ULL * g.P2 * (nn / tile2 + 1) + (uint64_t)(b_hi - b_lo) * g.P2 * P2_RUN_SLACK + 64;
-            };
-            if (seg) HIPCHK(c, hipStreamSynchronize(c->stream));                   // ovf_l1 has arrived
-            uint32_t step = pass_buckets(g.P1, (uint32_t)c->n_cu);
-            auto fits = [&](uint32_t st) { for (uint32_t b = 0; b < g.P1; b += st) if (pass_extent(b, std::min(g.P1, b + st)) > l2_items) return false; return true; };
-            while (step > 1 && !fits(step)) step = (step + 1) / 2;
-            if (!fits(step)) {                                                      // (a single bucket beyond the buffer: direct path)
-                // this round's level 1 (either edition) has tallied the all-ones key of [pos, pos + m), which the direct kernel will count again
-                if (seg || (t->dv.k == 32 && !t->dv.canonical)) HIPCHK(c, hipMemcpyAsync(&t->dv.ctrs[CTR_ONES], &t->ones, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-                break;
-            }
-            // level 2: one pass over the bucket when the runs are predictable (k_p2_fast), else -- or when its overflow list did not
-            // hold -- the exact two-pass kernel
-            const bool try_fast0 = p2_fast_ok && (g_p2_fast == 2 || items / g.R >= 1024);
-            std::vector<std::pair<const uint64_t*, uint64_t>> lists;              // spilled k-mers: in the parts of the level-1 buffer that are dead
-            unsigned long long ovf_total = ovf_l1;                                 // entries of the overflow list so far (level 1's, then every pass's)
-            bool redo_round = false;
-            if (g_trace && g.P1 > step) fprintf(stderr, "[katgpu]   level 2 + apply in %u passes of %u buckets (level-2 buffer: %zu items)\n", (g.P1 + step - 1) / step, step, l2_items);
-            for (uint32_t b_lo = 0; b_lo < g.P1 && !redo_round; b_lo += step) {
-                g.b_lo = b_lo; g.b_hi = std::min(g.P1, b_lo + step);
-                const uint64_t pass_items = std::max<uint64_t>(1, (uint64_t)((double)items * (g.b_hi - g.b_lo) / g.P1));
-                // this pass's part of the level-1 buffer, dead once its level 2 is through: the pass's spill list (room for 8 bytes per k-mer)
-                auto l1_at = [&](uint32_t b) -> uint64_t { return seg ? (uint64_t)b * g.l1_stride : l1_bucket_base(lbeg(b), b); };
-                uint64_t* spill_buf = (uint64_t*)(l1_buf + l1_at(b_lo));
-                g.spill_cap = (l1_at(g.b_hi) - l1_at(b_lo)) / 8;
-                const uint32_t* run_len = nullptr;
-                unsigned long long overflowed = ovf_total;
-                const bool try_fast = try_fast0 && p2_fast_ok;
-                const uint32_t grid_l2 = std::min<uint32_t>(g.b_hi - g.b_lo, W2);
-                HIPCHK(c, hipMemsetAsync(spill_n, 0, sizeof(unsigned long long), c->stream));
-                if (try_fast) {
-                    ScopedTimer tm(c, KATGPU_K_PART_L2, pass_items);
-#define KG_P2F_B(HB) case HB: KG_LDS_ATTR((k_p2_fast<HB, false, false, true>), sizeof(P2FastLds<HB>::type)); \
-                            hipLaunchKernelGGL((k_p2_fast<HB, false, false, true>), dim3(grid_l2), dim3(PART_BLOCK), sizeof(P2FastLds<HB>::type), c->stream, g, l1_off, l1_buf, l2_buf, \
-                                               off2, cnt2, ovf_buf, ovf_n, ovf_cap, seg_slots, (unsigned long long*)nullptr); break;
-#define KG_P2F(HB) case HB: if (g.hb1 == 4) hipLaunchKernelGGL((k_p2_fast<HB, true>), dim3(grid_l2), dim3(PART_BLOCK), sizeof(P2FastLds<HB>::type), c->stream, g, l1_off, l1_buf, l2_buf, \
-                                               off2, cnt2, ovf_buf, ovf_n, ovf_cap, seg_slots, (unsigned long long*)nullptr); \
-                            else hipLaunchKernelGGL((k_p2_fast<HB, false>), dim3(grid_l2), dim3(PART_BLOCK), sizeof(P2FastLds<HB>::type), c->stream, g, l1_off, l1_buf, l2_buf, \
-                                               off2, cnt2, ovf_buf, ovf_n, ovf_cap, seg_slots, (unsigned long long*)nullptr); break;
-                    if (g.hb == 1 && g.hb1 != 4 && g_p2_stamp) {                       // diagnostic: the bench's shape with cycle stamps
-                        unsigned long long* stamps = spill_n + 16;
-                        HIPCHK(c, hipMemsetAsync(stamps, 0, 6 * sizeof(unsigned long long), c->stream));
-                        KG_LDS_ATTR((k_p2_fast<1, false, true>), sizeof(P2FastLds<1>::type));
-                        KG_LDS_ATTR((k_p2_fast<1, false, true, true>), sizeof(P2FastLds<1>::type));
-                        if (l1_blocked) hipLaunchKernelGGL((k_p2_fast<1, false, true, true>), dim3(grid_l2), dim3(PART_BLOCK), sizeof(P2FastLds<1>::type), c->stream, g, l1_off, l1_buf, l2_buf, off2, cnt2, ovf_buf, ovf_n, ovf_cap, seg_slots, stamps);
-                        else
-                        hipLaunchKernelGGL((k_p2_fast<1, false, true>), dim3(grid_l2), dim3(PART_BLOCK), sizeof(P2FastLds<1>::type), c->stream, g, l1_off, l1_buf, l2_buf, off2, cnt2, ovf_buf, ovf_n, ovf_cap, seg_slots, stamps);
-                        unsigned long long st[6];
-                        HIPCHK(c, hipMemcpyAsync(st, stamps, sizeof st, hipMemcpyDeviceToHost, c->stream));
-                        HIPCHK(c, hipStreamSynchronize(c->stream));
-                        const double tot = (double)(st[0] + st[1] + st[2] + st[3] + st[4]);
-                        if (st[5]) fprintf(stderr, "[katgpu] level-2 stamps (lane 0 of every workgroup, cycles summed): wait for the tile %.0f %%  digit + rank %.0f %%  scan %.0f %%  staging %.0f %%  copy-out %.0f %%; %llu tiles, %.0f cycles per tile\n",
-                                           100 * st[0] / tot, 100 * st[1] / tot, 100 * st[2] / tot, 100 * st[3] / tot, 100 * st[4] / tot, st[5], tot / st[5]);
-                    } else if (l1_blocked && g.hb == 1 && g_p2x) {                   // the bench's shape: kg_l2_blocks.hpp
-                        if (g_p2x_stamp) {
-                            unsigned long long* stamps = spill_n + 16;
-                            HIPCHK(c, hipMemsetAsync(stamps, 0, 10 * sizeof(unsigned long long), c->stream));
-                            KG_LDS_ATTR(k_p2x_fast<true>, sizeof(P2XLds));
-                            hipLaunchKernelGGL(k_p2x_fast<true>, dim3(grid_l2), dim3(PART_BLOCK), sizeof(P2XLds), c->stream, g, l1_off, l1_buf, l2_buf, off2, cnt2, ovf_buf, ovf_n, ovf_cap, seg_slots, stamps);
-                            unsigned long long st[10];
-                            HIPCHK(c, hipMemcpyAsync(st, stamps, sizeof st, hipMemcpyDeviceToHost, c->stream));
-                            HIPCHK(c, hipStreamSynchronize(c->stream));
-                            double tot = 0;
-                            for (int i = 0; i < 9; ++i) tot += (double)st[i];
-                            if (st[9]) fprintf(stderr, "[katgpu] level-2 (blocks in, blocks out) stamps (wave 0 of every workgroup, cycles summed): wait for the tile %.1f %% (+ barrier %.1f %%)  ranking + blocks out %.1f %% (+ %.1f %%)  per sub-bucket %.1f %% (+ %.1f %%)  placing %.1f %%; %llu tiles, %.0f cycles per tile\n",
-                                               100 * st[0] / tot, 100 * st[1] / tot, 100 * st[2] / tot, 100 * st[3] / tot, 100 * st[4] / tot, 100 * st[5] / tot, 100 * st[6] / tot, st[9], tot / st[9]);
-                        } else {
-                            KG_LDS_ATTR(k_p2x_fast<false>, sizeof(P2XLds));
-                            hipLaunchKernelGGL(k_p2x_fast<false>, dim3(grid_l2), dim3(PART_BLOCK), sizeof(P2XLds), c->stream, g, l1_off, l1_buf, l2_buf, off2, cnt2, ovf_buf, ovf_n, ovf_cap, seg_slots, (unsigned long long*)nullptr);
-                        }
-                    } else if (l1_blocked) {
-                        switch (g.hb) { KG_P2F_B(0) KG_P2F_B(1) KG_P2F_B(2) default: return fail(c, KATGPU_ERR_DEVICE, "level 2 from blocked level-1 items: item width %u", g.hb); }
-                    } else
-                    switch (g.hb) { KG_FOR_HB(KG_P2F) }
-#undef KG_P2F
-#undef KG_P2F_B
-                }
-                if (try_fast || (seg && b_lo == 0)) {
-                    HIPCHK(c, hipMemcpyAsync(&overflowed, ovf_n, sizeof overflowed, hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    if (seg && ovf_l1 > ovf_cap) {               // the level-1 buffer itself is incomplete: this round again, exactly
-                        if (g_trace) fprintf(stderr, "[katgpu] segmented level 1: %llu k-mers beyond their segments (list holds %llu): exact level 1 from here on\n", ovf_l1, (unsigned long long)ovf_cap);
-                        l1_fast_ok = false;
-                        HIPCHK(c, hipMemcpyAsync(&t->dv.ctrs[CTR_ONES], &t->ones, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));   // the scatter tallied the all-ones key
-                        redo_round = true;                       // (only ever in the first pass: nothing has been applied yet)
-                        break;
-                    }
-                    if (try_fast && overflowed <= ovf_cap) run_len = cnt2;
-                    else if (try_fast) {
-                        if (g_trace) fprintf(stderr, "[katgpu] k_p2_fast: %llu k-mers beyond their runs (list holds %llu): exact level 2 from here on\n", overflowed, (unsigned long long)ovf_cap);
-                        p2_fast_ok = false;
-                        overflowed = ovf_total;                  // what was on the list before this pass is still there and still valid
-                        HIPCHK(c, hipMemcpyAsync(ovf_n, &ovf_total, sizeof ovf_total, hipMemcpyHostToDevice, c->stream));
-                    }
-                }
-                if (!run_len) {
-                    ScopedTimer tm(c, KATGPU_K_PART_L2, pass_items);
-#define KG_P2(HB) case HB: if (g.hb1 == 4) hipLaunchKernelGGL((k_p2<HB, true>), dim3(grid_l2), dim3(PART_BLOCK), sizeof(P2Lds<HB>), c->stream, g, l1_off, l1_buf, l2_buf, off2, seg_slots, bend); \
-                           else hipLaunchKernelGGL((k_p2<HB, false>), dim3(grid_l2), dim3(PART_BLOCK), sizeof(P2Lds<HB>), c->stream, g, l1_off, l1_buf, l2_buf, off2, seg_slots, bend); break;
-#define KG_P2_B(HB) case HB: KG_LDS_ATTR((k_p2<HB, false, true>), sizeof(P2Lds<HB>)); \
-                           hipLaunchKernelGGL((k_p2<HB, false, true>), dim3(grid_l2), dim3(PART_BLOCK), sizeof(P2Lds<HB>), c->stream, g, l1_off, l1_buf, l2_buf, off2, seg_slots, bend); break;
-                    if (l1_blocked) { switch (g.hb) { KG_P2_B(0) KG_P2_B(1) KG_P2_B(2) default: return fail(c, KATGPU_ERR_DEVICE, "level 2 from blocked level-1 items: item width %u", g.hb); } }
-                    else
-                    switch (g.hb) { KG_FOR_HB(KG_P2) }
-#undef KG_P2
-#undef KG_P2_B
-                }
-                ovf_total = overflowed;
-                const uint64_t* bucket_end = !run_len ? bend : nullptr;             // exact level 2: a bucket's runs stop short of the next bucket's
-                {
-                    ScopedTimer tm(c, KATGPU_K_PART_APPLY, pass_items);
-                    rc = launch_apply(t, g, off2, l2_buf, spill_buf, spill_n, run_len, bucket_end);
-                    if (rc) return rc;
-                }
-                HIPCHK(c, hipGetLastError());
-                unsigned long long spilled = 0;
-                HIPCHK(c, hipMemcpyAsync(&spilled, spill_n, sizeof spilled, hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                if (g_apply_stamp) {
-                    unsigned long long st[7];
-                    HIPCHK(c, hipMemcpy(st, spill_n + 8, sizeof st, hipMemcpyDeviceToHost));
-                    HIPCHK(c, hipMemset(spill_n + 8, 0, sizeof st));
-                    const double tot = (double)(st[0] + st[1] + st[3] + st[4]);
-                    if (st[5]) fprintf(stderr, "[katgpu] apply stamps (wave 0 of every workgroup, cycles summed): fill %.3g (%.0f %%)  walk %.3g (%.0f %%; drains %.0f %% of the walk)  barrier + sweep %.3g (%.0f %%)  write-back %.3g (%.0f %%); %llu regions, %.1f chunks per wave and region, %.0f cycles per region\n",
-                                       (double)st[0], 100 * st[0] / tot, (double)st[1], 100 * st[1] / tot, 100.0 * st[2] / std::max(1.0, (double)st[1]), (double)st[3], 100 * st[3] / tot, (double)st[4], 100 * st[4] / tot, st[5], (double)st[6] / st[5], tot / st[5]);
-                }
-                if (spilled > g.spill_cap)       // (more k-mers without a slot than the pass's segments were sized for: a table far too small, met by a 5-sigma round)
-                    return fail(c, KATGPU_ERR_TABLE_FULL, "Hash full: %llu k-mers of a partition pass found no slot (the list holds %llu); raise the size hint", spilled, (unsigned long long)g.spill_cap);
-                if (spilled) lists.push_back({spill_buf, spilled});
-            }
-            if (redo_round) continue;
-            if (ovf_total) lists.push_back({ovf_buf, ovf_total});                  // what level 1 / level 2 could not place
-            if (!lists.empty()) {                      // regions that ran out of slots, runs beyond their capacity: make room, then the direct path
-                uint64_t total = 0;
-                for (auto& l : lists) total += l.second;
-                bool lost = false;
-                rc = grow_beside_arena(t, total, 0, lists, &lost);
-                if (rc) return rc;
-                if (lost) { pos += m; break; }         // the lists went in from the host; the caller re-enters for the rest
-                for (auto& l : lists) {
-                    ScopedTimer tm(c, KATGPU_K_COUNT, l.second);
-                    hipLaunchKernelGGL(k_insert_keys, dim3(grid_for(c, l.second, 256, 6)), dim3(256), 0, c->stream, t->dev(), l.first, (uint64_t)l.second);
-                }
-            }
+            KeyLists lists;
+            RoundEnd end;
+            rc = level2_and_apply(t, g, l1, A, items, &p2_fast_ok, &lists, &end);
+            if (rc) return rc;
+            if (end == RoundEnd::RedoExactL1) { l1_fast_ok = false; continue; }
+            if (end == RoundEnd::DirectPath) break;
+            bool lost = false;
+            rc = insert_spilled(t, lists, &lost);
+            if (rc) return rc;
+            if (lost) { pos += m; break; }         // the caller re-enters for the rest
         }
         pos += m;
     }
@@ -679,28 +775,16 @@ static int count_partitioned_w(katgpu_table* t, const uint8_t* dev_bases, size_t
                                align_up(((size_t)MAX_PARTS * MAX_PARTS + 1) * 8, 256) + 256 + 4096;
     size_t want_items = n_starts;
     if (g_test_round_items) want_items = std::min<size_t>(want_items, g_test_round_items);
-    size_t want_bytes = small_bytes + 32 * (want_items + 64);
-    if (c->arena_limit) want_bytes = std::min(want_bytes, std::max(c->arena_limit, small_bytes + 32 * ((size_t)64 << 20)));
-    if (c->arena_bytes < want_bytes) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-        free_b += c->arena_bytes;
-        const size_t bytes = std::min<size_t>(want_bytes, (size_t)(g_arena_fraction * (double)free_b));
-        if (bytes > c->arena_bytes + c->arena_bytes / 2 || c->arena_bytes < small_bytes + 32 * std::min<size_t>(want_items + 64, (size_t)64 << 20)) {
-            if (c->arena) { HIPCHK(c, hipFree(c->arena)); c->arena = nullptr; c->arena_bytes = 0; }
-            if (!g_test_round_items && bytes < small_bytes + 32 * ((size_t)1 << 20)) return KATGPU_OK;
-            if (hipMalloc((void**)&c->arena, bytes) != hipSuccess) { (void)hipGetLastError(); c->arena = nullptr; return KATGPU_OK; }
-            c->arena_bytes = bytes;
-            if (g_trace) fprintf(stderr, "[katgpu +%.0f ms] partition arena of %.1f GB (wide k-mers)\n", since_load(), bytes / 1e9);
-        }
-    }
-    struct Busy { katgpu_ctx* c; explicit Busy(katgpu_ctx* c_) : c(c_) { c->arena_busy = true; } ~Busy() { c->arena_busy = false; } } busy(c);
+    bool usable = false;
+    int rc = ensure_arena(c, small_bytes, 32, want_items + 64, small_bytes + 32 * (want_items + 64), " (wide k-mers)", &usable);
+    if (rc || !usable) return rc;                                              // (no arena: direct path)
+    ArenaBusy busy(c);
     uint8_t* a = c->arena;
-    uint32_t* hist1 = (uint32_t*)a;               a += align_up((size_t)W * MAX_PARTS * 4, 256);
-    uint64_t* offs = (uint64_t*)a;                a += align_up((size_t)W * MAX_PARTS * 8, 256);
-    uint64_t* l1_off = (uint64_t*)a;              a += align_up((MAX_PARTS + 1) * 8, 256);
-    uint64_t* off2 = (uint64_t*)a;                a += align_up(((size_t)MAX_PARTS * MAX_PARTS + 1) * 8, 256);
-    unsigned long long* spill_n = (unsigned long long*)a; a += 256;
+    uint32_t* hist1 = carve<uint32_t>(a, (size_t)W * MAX_PARTS * 4);
+    uint64_t* offs = carve<uint64_t>(a, (size_t)W * MAX_PARTS * 8);
+    uint64_t* l1_off = carve<uint64_t>(a, (MAX_PARTS + 1) * 8);
+    uint64_t* off2 = carve<uint64_t>(a, ((size_t)MAX_PARTS * MAX_PARTS + 1) * 8);
+    unsigned long long* spill_n = carve<unsigned long long>(a, 256);
     const size_t round_items = std::min<size_t>(want_items, (c->arena_bytes - small_bytes) / 32);
     u64x2* l1_buf = (u64x2*)a;
     u64x2* l2_buf = l1_buf + round_items;
@@ -709,11 +793,11 @@ static int count_partitioned_w(katgpu_table* t, const uint8_t* dev_bases, size_t
 
     size_t pos = 0;
     while (pos < n_starts) {
-        int rc = refresh_counters(t);
+        rc = refresh_counters(t);
         if (rc) return rc;
         if ((double)t->distinct > 0.6 * (double)t->dev().cap) {
             bool lost = false;
-            rc = grow_beside_arena(t, 0, t->dev().cap * 2, KeyLists(), &lost);
+            rc = grow_beside_arena(t, 0, t->dev().cap * 2, KeyLists(), 16, &lost);
             if (rc) return rc;
             if (lost) break;                                                      // the caller re-enters with a fresh arena
         }
@@ -753,11 +837,10 @@ static int count_partitioned_w(katgpu_table* t, const uint8_t* dev_bases, size_t
                 hipLaunchKernelGGL(k_w2, dim3(std::min<uint32_t>(d.p1, (uint32_t)c->n_cu)), dim3(PART_BLOCK), 0, c->stream, d.p1, d.p2, (const uint64_t*)l1_off, (const u64x2*)l1_buf, l2_buf, off2);
             }
             {
-                const size_t lds = (size_t)d.region_slots * 20;
-                KG_LDS_ATTR(k_w3_apply, LDS_BYTES - 256);
                 ScopedTimer tm(c, KATGPU_K_PART_APPLY, items);
-                hipLaunchKernelGGL(k_w3_apply, dim3(std::min<uint32_t>(d.n_regions, (uint32_t)c->n_cu)), dim3(W3_BLOCK), lds, c->stream, d, (const uint64_t*)off2, (const u64x2*)l2_buf,
-                                   l1_buf /* the spill list: the level-1 buffer is dead */, spill_n, g_test_spill_mod);
+                rc = launch_lds(c, k_w3_apply, dim3(std::min<uint32_t>(d.n_regions, (uint32_t)c->n_cu)), dim3(W3_BLOCK), (size_t)d.region_slots * 20, LDS_BYTES - 256, d, (const uint64_t*)off2, (const u64x2*)l2_buf,
+                                l1_buf /* the spill list: the level-1 buffer is dead */, spill_n, g_test_spill_mod);
+                if (rc) return rc;
             }
             HIPCHK(c, hipGetLastError());
             unsigned long long spilled = 0;
@@ -765,33 +848,11 @@ static int count_partitioned_w(katgpu_table* t, const uint8_t* dev_bases, size_t
             HIPCHK(c, hipStreamSynchronize(c->stream));
             if (spilled) {                              // regions that ran out of slots: make room, then the direct path
                 if (g_trace) fprintf(stderr, "[katgpu]   %llu k-mers spilled by full regions\n", spilled);
-                rc = g_test_grow_nomem ? KATGPU_ERR_NOMEM : ensure_room(t, spilled);
-                if (rc == KATGPU_ERR_NOMEM) {           // no room for the larger table beside the arena: park the list on the host, give the arena up
-                    (void)hipGetLastError();
-                    std::vector<uint64_t> host;
-                    try { host.resize((size_t)spilled * 2); } catch (...) { return fail(c, KATGPU_ERR_NOMEM, "no host memory to park %llu spilled k-mers", spilled); }
-                    HIPCHK(c, hipMemcpy(host.data(), l1_buf, (size_t)spilled * 16, hipMemcpyDeviceToHost));
-                    release_arena(c);
-                    rc = ensure_room(t, spilled);
-                    if (rc) return rc;
-                    const size_t chunk = std::min<size_t>(spilled, (size_t)16 << 20);
-                    u64x2* dbuf = nullptr;
-                    HIPCHK(c, pool_alloc(c, (void**)&dbuf, chunk * 16));
-                    for (size_t i = 0; i < spilled && rc == KATGPU_OK; i += chunk) {
-                        const size_t mm = std::min(chunk, (size_t)spilled - i);
-                        if (hipMemcpyAsync(dbuf, host.data() + 2 * i, mm * 16, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = fail(c, KATGPU_ERR_DEVICE, "spill upload"); break; }
-                        ScopedTimer tm(c, KATGPU_K_COUNT, mm);
-                        hipLaunchKernelGGL(k_insert_keys_w, dim3(grid_for(c, mm, 256, 6)), dim3(256), 0, c->stream, t->dev(), (const u64x2*)dbuf, (uint64_t)mm);
-                        if (hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, KATGPU_ERR_DEVICE, "spill insert");
-                    }
-                    pool_release(c, dbuf);
-                    if (rc) return rc;
-                    pos += m;
-                    break;                              // the caller re-enters with a fresh arena
-                }
+                bool lost = false;
+                rc = grow_beside_arena(t, spilled, 0, KeyLists(1, {l1_buf, spilled}), 16, &lost);
                 if (rc) return rc;
-                ScopedTimer tm(c, KATGPU_K_COUNT, spilled);
-                hipLaunchKernelGGL(k_insert_keys_w, dim3(grid_for(c, spilled, 256, 6)), dim3(256), 0, c->stream, t->dev(), (const u64x2*)l1_buf, (uint64_t)spilled);
+                if (lost) { pos += m; break; }          // the list went in from the host; the caller re-enters with a fresh arena
+                insert_keys(t, l1_buf, spilled, 16);
                 HIPCHK(c, hipStreamSynchronize(c->stream));
             }
         }

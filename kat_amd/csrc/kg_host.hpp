@@ -67,7 +67,7 @@ struct katgpu_ctx {
     uint8_t* arena = nullptr;
     size_t arena_bytes = 0;
     std::unordered_set<const void*> lds_attr;   // kernels whose dynamic-LDS ceiling has been raised on this device
-    bool part_attr_set = false, merge_attr_set = false;   // the dynamic-LDS attributes of the partition / merge kernels have been set on this device
+    bool merge_attr_set = false;          // the dynamic-LDS attributes of the merge kernels have been set on this device
     bool arena_busy = false;              // a partition round is using it: pool_alloc must not free it to satisfy a table growth
     // Who allocates first when several threads ask the driver for tens of GB at once.  On some boxes a hipMalloc costs ~1 ms per 40 MB
     // (the driver clears what it hands out) and the driver serves one request at a time: the 9 GB of scan buffers, which the readers

@@ -29,7 +29,7 @@ struct P2XLds {
 static_assert(sizeof(P2XLds) <= 160 * 1024 - 256 && offsetof(P2XLds, img) % 64 == 0, "LDS");
 static_assert(PART_BLOCK == MAX_PARTS, "thread b is sub-bucket b");
 
-template <bool STAMP = false /* diagnostic (KATGPU_P2_STAMP): wave 0's cycles per phase, summed over the workgroups into stamps[0 .. 9] */>
+template <bool STAMP = false /* diagnostic (KATGPU_P2X_STAMP): wave 0's cycles per phase, summed over the workgroups into stamps[0 .. 9] */>
 __global__ void __launch_bounds__(PART_BLOCK)
 k_p2x_fast(PartGeom g, const uint64_t* __restrict__ l1_off, const uint8_t* __restrict__ l1_buf, uint8_t* __restrict__ l2_buf,
            uint64_t* __restrict__ off2, uint32_t* __restrict__ cnt2, uint64_t* __restrict__ ovf_buf, unsigned long long* __restrict__ ovf_n,

@@ -1,7 +1,8 @@
 """Run in a subprocess by tests/test_gpu_bench_geometry.py::test_config4_geometry_prefix_against_the_oracle with
 KATGPU_PART_MIN_STARTS=0 (so that a 600 K-read prefix takes the partitioned counter) and the one-pass level 2 forced: the prefix of
 config 4's read library goes into a table of config 4's size -- the 512 x 1024 grid of 9344-slot regions, packed 8-byte slots, 6-byte
-level-1 items written as groups by the segmented level 1, 5-byte level-2 items, two passes of 256 buckets -- and the table's dump is
+level-1 items in 64-byte blocks of ten from the segmented level 1's block edition (k_p1b_scatter: the prefix's 74.4 M k-mers are above that
+edition's 64 Mi threshold), read by k_p2x_fast into 5-byte level-2 items, two passes of 256 buckets -- and the table's dump is
 compared record by record with the CPU oracle's count of the same bytes.  This is the anchor of the bench geometry that is NOT a
 comparison of the product with itself."""
 import os
