@@ -50,9 +50,9 @@ static int launch_count(katgpu_table* t, const uint8_t* dev_bases, size_t n) {
         const int grid = (int)std::min<uint64_t>(n_chunks, (uint64_t)c->n_cu * 4);
         ScopedTimer tm(c, KATGPU_K_COUNT, n);
         if ((reinterpret_cast<uintptr_t>(dev_bases) & 15) == 0)
-            hipLaunchKernelGGL(k_count_w<true>, dim3(grid), dim3(COUNT_BLOCK), 0, c->stream, t->dev(), dev_bases, (uint64_t)n, n_chunks);
+            hipLaunchKernelGGL((k_count<true, true>), dim3(grid), dim3(COUNT_BLOCK), 0, c->stream, t->dev(), dev_bases, (uint64_t)n, n_chunks);
         else
-            hipLaunchKernelGGL(k_count_w<false>, dim3(grid), dim3(COUNT_BLOCK), 0, c->stream, t->dev(), dev_bases, (uint64_t)n, n_chunks);
+            hipLaunchKernelGGL((k_count<false, true>), dim3(grid), dim3(COUNT_BLOCK), 0, c->stream, t->dev(), dev_bases, (uint64_t)n, n_chunks);
         HIPCHK(c, hipGetLastError());
         return KATGPU_OK;
     }

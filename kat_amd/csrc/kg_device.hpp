@@ -522,6 +522,11 @@ __device__ __forceinline__ uint64_t table_get_w(const DevTable& t, KeyW key, uin
     return 0;
 }
 
+// the same operations under the one-word names, for a kernel body written once over the key type
+__device__ __forceinline__ KeyW kmer_canonical(KeyW x, uint32_t k) { return keyw_canonical(x, k); }
+__device__ __forceinline__ bool table_inc(const DevTable& t, KeyW key, uint32_t& new_distinct) { return table_add_w(t, key, 1, new_distinct); }   // (wide tables have no unit path: the returning add, amount 1)
+__device__ __forceinline__ uint64_t table_get(const DevTable& t, KeyW key, uint32_t n_ovf) { return table_get_w(t, key, n_ovf); }
+
 // A lane's value for the whole wave, the lane wave-uniform (a ballot's first set bit, lane 0 ...): v_readlane_b32, a few cycles --
 // __shfl of a uniform lane is a ds_bpermute through the LDS crossbar, ~200 cycles of latency on gfx950 (tools/ubench_valu.hip).
 __device__ __forceinline__ uint32_t lane_value(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }

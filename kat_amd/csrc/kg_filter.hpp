@@ -9,7 +9,6 @@
 // walk consecutive source slots write the same few destination regions: K2's re-insert (k_regrow), with a predicate in front.
 #pragma once
 #include "kg_kernels.hpp"
-#include "kg_wide.hpp"
 
 namespace kg {
 
@@ -123,17 +122,14 @@ template <bool ALIGNED, bool W>
 __global__ void __launch_bounds__(COUNT_BLOCK)
 k_seq_hits(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
            const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len, uint64_t n_rec, unsigned long long* __restrict__ hits) {
-    constexpr int CS = W ? WIDE_CHUNK_STARTS : CHUNK_STARTS;
-    constexpr int LANES = W ? WIDE_LANES_WITH_STARTS : LANES_WITH_STARTS;
-    constexpr int PAD = W ? 4 : 2;
-    __shared__ uint32_t s_code[COUNT_BLOCK + PAD];
-    __shared__ uint32_t s_bad[COUNT_BLOCK + PAD];
+    constexpr int CS = Chunk<W>::STARTS;
+    __shared__ typename Chunk<W>::Tile s;
     __shared__ uint32_t s_hits[HITS_LDS_RECS];
     __shared__ uint64_t s_r[2];
     const uint32_t tid = threadIdx.x;
     const uint32_t k = t.k;
     const uint64_t n_out = n - k + 1;
-    if (tid < PAD) { s_code[COUNT_BLOCK + tid] = 0; s_bad[COUNT_BLOCK + tid] = 0xFFFF; }
+    s.pad();
     for (uint32_t i = tid; i < HITS_LDS_RECS; i += COUNT_BLOCK) s_hits[i] = 0;
 
     for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
@@ -146,30 +142,14 @@ k_seq_hits(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restri
         }
         const uint64_t off = c0 + (uint64_t)tid * BASES_PER_LANE;
         uint32_t w[4];
-        if (ALIGNED && off + BASES_PER_LANE <= n) {
-            const uint4 q = *reinterpret_cast<const uint4*>(bases + off);
-            w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint32_t x = 0;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const uint64_t i = off + q * 4 + b;
-                    const uint32_t c = i < n ? bases[i] : (uint32_t)'N';
-                    x |= c << (8 * b);
-                }
-                w[q] = x;
-            }
-        }
+        load16<ALIGNED>(bases, n, off, w);
         uint32_t code, bad;
         encode16(w, code, bad);
-        s_code[tid] = code;
-        s_bad[tid] = bad;
+        s.stage(code, bad);
         __syncthreads();
         const uint64_t r_lo = s_r[0], r_hi = s_r[1];
 
-        if (tid < LANES && off < n_out && r_lo < r_hi) {
+        if (tid < Chunk<W>::LANES && off < n_out && r_lo < r_hi) {
             // the record of the first window start: the last one of [r_lo, r_hi) that starts at or before it (none: r = r_lo - 1)
             int64_t r = (int64_t)hits_lower_bound(rec_start, rec_len, r_lo, r_hi, off + 1, false) - 1;
             uint64_t rs = 0, re = 0;
@@ -183,43 +163,15 @@ k_seq_hits(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restri
                 if (idx < HITS_LDS_RECS) atomicAdd(&s_hits[idx], run);
                 else atomicAdd(&hits[cur], (unsigned long long)run);
             };
-            if constexpr (W) {
-                uint64_t hi = ((uint64_t)s_code[tid] << 32) | s_code[tid + 1];
-                uint64_t lo = ((uint64_t)s_code[tid + 2] << 32) | s_code[tid + 3];
-                uint64_t nx = (uint64_t)s_code[tid + 4] << 32;
-                uint64_t m = ((uint64_t)s_bad[tid] << 48) | ((uint64_t)s_bad[tid + 1] << 32) | ((uint64_t)s_bad[tid + 2] << 16) | s_bad[tid + 3];
-                uint64_t mn = (uint64_t)s_bad[tid + 4] << 48;
-                const uint32_t s = 128 - 2 * k, mshift = 64 - k;
-                for (int j = 0; j < BASES_PER_LANE; ++j) {
-                    const uint64_t pos = off + j;
-                    while (pos >= ns) { ++r; rs = ns; re = rs + rec_len[r]; ns = (uint64_t)(r + 1) < r_hi ? rec_start[r + 1] : ~0ULL; }
-                    if (r >= (int64_t)r_lo && pos >= rs && pos + k <= re && (m >> mshift) == 0) {
-                        KeyW key = keyw_from_words(hi >> s, (lo >> s) | (hi << (64 - s)));
-                        if (canonicalise) key = keyw_canonical(key, k);
-                        if (table_get_w(t, key, n_ovf)) { if (r != cur) { flush(); cur = r; run = 0; } ++run; }
-                    }
-                    hi = (hi << 2) | (lo >> 62);
-                    lo = (lo << 2) | (nx >> 62);
-                    nx <<= 2;
-                    m = (m << 1) | (mn >> 63);
-                    mn <<= 1;
-                }
-            } else {
-                uint64_t hi = ((uint64_t)s_code[tid] << 32) | s_code[tid + 1];
-                uint64_t lo = (uint64_t)s_code[tid + 2] << 32;
-                uint64_t m = ((uint64_t)s_bad[tid] << 48) | ((uint64_t)s_bad[tid + 1] << 32) | ((uint64_t)s_bad[tid + 2] << 16);
-                const uint32_t kshift = 64 - 2 * k, mshift = 64 - k;
-                for (int j = 0; j < BASES_PER_LANE; ++j) {
-                    const uint64_t pos = off + j;
-                    while (pos >= ns) { ++r; rs = ns; re = rs + rec_len[r]; ns = (uint64_t)(r + 1) < r_hi ? rec_start[r + 1] : ~0ULL; }
-                    if (r >= (int64_t)r_lo && pos >= rs && pos + k <= re && (m >> mshift) == 0) {
-                        uint64_t key = hi >> kshift;
-                        if (canonicalise) key = kmer_canonical(key, k);
-                        if (table_get(t, key, n_ovf)) { if (r != cur) { flush(); cur = r; run = 0; } ++run; }
-                    }
-                    hi = (hi << 2) | (lo >> 62);
-                    lo <<= 2;
-                    m <<= 1;
+            typename Chunk<W>::Window lw;
+            lw.init(s.code, s.bad, tid, k);
+            for (int j = 0; j < BASES_PER_LANE; ++j, lw.step()) {
+                const uint64_t pos = off + j;
+                while (pos >= ns) { ++r; rs = ns; re = rs + rec_len[r]; ns = (uint64_t)(r + 1) < r_hi ? rec_start[r + 1] : ~0ULL; }
+                if (r >= (int64_t)r_lo && pos >= rs && pos + k <= re && lw.valid()) {
+                    auto key = lw.fwd();
+                    if (canonicalise) key = kmer_canonical(key, k);
+                    if (table_get(t, key, n_ovf)) { if (r != cur) { flush(); cur = r; run = 0; } ++run; }
                 }
             }
             flush();

@@ -3,104 +3,70 @@
 //  K1 k_count          extract + canonicalise + 2-bit pack + hash + insert      (replaces mer_iterator + hash_counter::add)
 //  K2 k_regrow         re-insert a table into a larger one                       (replaces hash_counter::double_size)
 //  K3 k_hist           slot scan -> histogram                                    (replaces Histogram::binSlice)
-//  K4 k_gcp            slot scan -> GC x coverage matrix                         (replaces Gcp::analyseSlice)
-//  K5 k_comp_pass1/2   slot scan + probe of the other table -> matrix, counters  (replaces Comp::compareSlice)
-//  K6 k_part_*         owner-partitioned export for the multi-GPU merge
-//  K7 k_merge          add (key,count) records into a table
+//  K4 k_gcp, k_gcp_pk  slot scan -> GC x coverage matrix                         (replaces Gcp::analyseSlice)
+//  K5 k_comp, k_comp_join, k_comp_seen, k_comp_fused, k_comp3_pass1/3
+//                      slot scan + probe of the other table -> matrix, counters  (replaces Comp::compareSlice)
+//  K6 k_partition, k_extract_count, k_extract_write                              owner-partitioned export for the multi-GPU merge
+//  K7 k_merge, k_merge32, k_merge_apply, k_merge_deferred                        add (key,count) records into a table
+//  K8 k_profile        per-position lookup of a sequence's windows               (replaces the lookups of Sect::processSeq)
+// K1 and K8 are one body for one-word and wide k-mers (k <= 32, 33 <= k <= 63); what else wide tables need is in kg_wide.hpp.
 //
 // All of this is integer / byte work bound by HBM (random 8-16 B slot accesses for K1/K5, streaming for K3/K4);
 // none of it is a contraction, so no MFMA anywhere.
 #pragma once
 #include "kg_device.hpp"
+#include "kg_windows.hpp"
 #include <type_traits>
 
 namespace kg {
 
 constexpr int COUNT_BLOCK = 256;                 // 4 waves
-constexpr int BASES_PER_LANE = 16;               // one 16-byte global load per lane
 constexpr int CHUNK_BYTES = COUNT_BLOCK * BASES_PER_LANE;        // 4096 bytes staged per block iteration
 constexpr int CHUNK_OVERLAP = 32;                // >= k-1 for k <= 32, keeps chunk starts 16-byte aligned
 constexpr int CHUNK_STARTS = CHUNK_BYTES - CHUNK_OVERLAP;        // 4064 window start positions per chunk
 constexpr int LANES_WITH_STARTS = CHUNK_STARTS / BASES_PER_LANE; // 254
+constexpr int WIDE_OVERLAP = 64;                                   // >= k-1 for k <= 63, keeps chunk starts 16-byte aligned
+constexpr int WIDE_CHUNK_STARTS = CHUNK_BYTES - WIDE_OVERLAP;      // 4032 window starts per staged chunk
+constexpr int WIDE_LANES_WITH_STARTS = WIDE_CHUNK_STARTS / BASES_PER_LANE;   // 252
 
-// 16 ASCII bytes -> 16 two-bit codes (MSB-first in a u32) + 16 "not ACGTacgt" flags (MSB-first in the low 16 bits).
-// code = x ^ (x >> 1) with x = (c >> 1) & 3 maps A,C,G,T (either case) to 0,1,2,3 (mer_dna.hpp:46-63).
-// Four bytes at a time (a byte-by-byte form was 200 of level 1's 1750 vector instructions per wave and tile): x per byte; the letter
-// that x stands for, looked up by v_perm_b32 with x as the selector; a byte that is not that letter (case folded) is flagged; the
-// four 2-bit codes / four flags of a word are gathered by one multiply each (the partial products land on distinct bits: no carries).
-__device__ __forceinline__ void encode16(const uint32_t w[4], uint32_t& code, uint32_t& bad) {
-    code = 0; bad = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const uint32_t v = w[q];
-        const uint32_t x = (v >> 1) & 0x03030303u;                                   // A, C, T, G -> 0, 1, 2, 3
-        const uint32_t c2 = x ^ ((x >> 1) & 0x01010101u);                            // A, C, G, T -> 0, 1, 2, 3
-        const uint32_t letter = __builtin_amdgcn_perm(0u, 0x67746361u, x);           // 'a', 'c', 't', 'g' by x
-        const uint32_t diff = (v | 0x20202020u) ^ letter;
-        const uint32_t nz = ((((diff & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | diff) >> 7) & 0x01010101u;    // 1 per byte that is no such letter
-        code = (code << 8) | ((c2 * 0x40100401u) >> 24);                             // byte 0 (the first base) into the top pair
-        bad = (bad << 4) | ((nz * 0x08040201u) >> 24);
-    }
-}
+// a staged chunk of the direct kernels (K1, K8, K10) at either key width.  W: wide k-mers (33 <= k <= 63; kg_device.hpp "wide keys")
+template <bool W>
+struct Chunk {
+    static constexpr int STARTS = W ? WIDE_CHUNK_STARTS : CHUNK_STARTS;
+    static constexpr int LANES = STARTS / BASES_PER_LANE;               // lanes that own window starts
+    typedef StagedTile<COUNT_BLOCK, W ? 4 : 2> Tile;
+    typedef typename std::conditional<W, LaneWindowW, LaneWindow>::type Window;
+};
 
 // K1.  One block iteration stages 4096 consecutive bytes of the base stream: each lane issues one coalesced 16-byte
 // load (1 KiB per wave instruction), packs it to 32 code bits + 16 validity bits and parks both in LDS.  After the
-// barrier lane t owns the 16 window starts [16t, 16t+16): it pulls three consecutive code words (48 bases) from
-// LDS into a 96-bit register window and slides it 16 times -- no per-base loop, no re-reading of HBM.  The
-// reverse complement is recomputed per window with v_bfrev (6 VALU ops) rather than rolled.
-template <bool ALIGNED>
+// barrier lane t owns the 16 window starts [16t, 16t+16) and slides its register window over them (kg_windows.hpp).
+// The direct counter (global atomics): small inputs and whatever the partitioned counters leave.
+template <bool ALIGNED, bool W = false>
 __global__ void __launch_bounds__(COUNT_BLOCK)
 k_count(DevTable t, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks) {
-    __shared__ uint32_t s_code[COUNT_BLOCK + 2];
-    __shared__ uint32_t s_bad[COUNT_BLOCK + 2];
+    __shared__ typename Chunk<W>::Tile s;
     const uint32_t tid = threadIdx.x;
-    const uint32_t k = t.k;
     const bool canonical = t.canonical != 0;
     uint32_t new_distinct = 0;
-    if (tid < 2) { s_code[COUNT_BLOCK + tid] = 0; s_bad[COUNT_BLOCK + tid] = 0xFFFF; }
+    s.pad();
 
     for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        const uint64_t off = chunk * CHUNK_STARTS + (uint64_t)tid * BASES_PER_LANE;
+        const uint64_t off = chunk * Chunk<W>::STARTS + (uint64_t)tid * BASES_PER_LANE;
         uint32_t w[4];
-        if (ALIGNED && off + BASES_PER_LANE <= n) {
-            const uint4 v = *reinterpret_cast<const uint4*>(bases + off);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint32_t x = 0;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    uint64_t i = off + q * 4 + b;
-                    uint32_t c = i < n ? bases[i] : (uint32_t)'N';       // past the end == separator
-                    x |= c << (8 * b);
-                }
-                w[q] = x;
-            }
-        }
+        load16<ALIGNED>(bases, n, off, w);
         uint32_t code, bad;
         encode16(w, code, bad);
-        s_code[tid] = code;
-        s_bad[tid] = bad;
+        s.stage(code, bad);
         __syncthreads();
 
-        if (tid < LANES_WITH_STARTS) {
-            uint64_t hi = ((uint64_t)s_code[tid] << 32) | s_code[tid + 1];   // bases 16t .. 16t+31
-            uint64_t lo = (uint64_t)s_code[tid + 2] << 32;                   // bases 16t+32 .. 16t+47
-            uint64_t m = ((uint64_t)s_bad[tid] << 48) | ((uint64_t)s_bad[tid + 1] << 32) | ((uint64_t)s_bad[tid + 2] << 16);
-            const uint32_t kshift = 64 - 2 * k, mshift = 64 - k;
-#pragma unroll 4
-            for (int j = 0; j < BASES_PER_LANE; ++j) {
-                if ((m >> mshift) == 0) {                                    // k valid bases from this start
-                    uint64_t fwd = hi >> kshift;
-                    uint64_t key = fwd;
-                    if (canonical) { uint64_t rc = kmer_revcomp(fwd, k); key = rc < fwd ? rc : fwd; }
-                    table_inc(t, key, new_distinct);
-                }
-                hi = (hi << 2) | (lo >> 62);
-                lo <<= 2;
-                m <<= 1;
-            }
+        if (tid < Chunk<W>::LANES) {
+            typename Chunk<W>::Window lw;
+            lw.init(s.code, s.bad, tid, t.k);
+            constexpr int UNROLL = W ? 2 : 4;
+#pragma unroll UNROLL
+            for (int j = 0; j < BASES_PER_LANE; ++j, lw.step())
+                if (lw.valid()) table_inc(t, lw.counted(t.k, canonical), new_distinct);
         }
         __syncthreads();
     }
@@ -1017,62 +983,40 @@ k_get(DevTable t, uint32_t n_ovf, const uint64_t* __restrict__ keys, uint64_t n,
 
 // K8.  Per-position coverage of a sequence (kat sect / kat cold; src/sect.cc:516-535): out[i] = count of the k-window
 // starting at base i, 0 when the window holds anything but ACGTacgt.  Same front end as k_count (16-byte loads, packed
-// codes through LDS, a 96-bit register window slid 16 times); the back end is a read-only probe, so the table's
+// codes through LDS, a register window slid 16 times); the back end is a read-only probe, so the table's
 // cache lines are shared between waves and nothing is atomic.  Each lane produces 16 consecutive counts = one 128-byte
 // line of `out`, written as 8 dwordx4 stores.
-template <bool ALIGNED>
+template <bool ALIGNED, bool W>
 __global__ void __launch_bounds__(COUNT_BLOCK)
 k_profile(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
           uint64_t* __restrict__ out) {
-    __shared__ uint32_t s_code[COUNT_BLOCK + 2];
-    __shared__ uint32_t s_bad[COUNT_BLOCK + 2];
+    __shared__ typename Chunk<W>::Tile s;
     const uint32_t tid = threadIdx.x;
     const uint32_t k = t.k;
     const uint64_t n_out = n - k + 1;
-    if (tid < 2) { s_code[COUNT_BLOCK + tid] = 0; s_bad[COUNT_BLOCK + tid] = 0xFFFF; }
+    s.pad();
 
     for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-        const uint64_t off = chunk * CHUNK_STARTS + (uint64_t)tid * BASES_PER_LANE;
+        const uint64_t off = chunk * Chunk<W>::STARTS + (uint64_t)tid * BASES_PER_LANE;
         uint32_t w[4];
-        if (ALIGNED && off + BASES_PER_LANE <= n) {
-            const uint4 v = *reinterpret_cast<const uint4*>(bases + off);
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                uint32_t x = 0;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    uint64_t i = off + q * 4 + b;
-                    uint32_t c = i < n ? bases[i] : (uint32_t)'N';
-                    x |= c << (8 * b);
-                }
-                w[q] = x;
-            }
-        }
+        load16<ALIGNED>(bases, n, off, w);
         uint32_t code, bad;
         encode16(w, code, bad);
-        s_code[tid] = code;
-        s_bad[tid] = bad;
+        s.stage(code, bad);
         __syncthreads();
 
-        if (tid < LANES_WITH_STARTS && off < n_out) {
-            uint64_t hi = ((uint64_t)s_code[tid] << 32) | s_code[tid + 1];
-            uint64_t lo = (uint64_t)s_code[tid + 2] << 32;
-            uint64_t m = ((uint64_t)s_bad[tid] << 48) | ((uint64_t)s_bad[tid + 1] << 32) | ((uint64_t)s_bad[tid + 2] << 16);
-            const uint32_t kshift = 64 - 2 * k, mshift = 64 - k;
+        if (tid < Chunk<W>::LANES && off < n_out) {
+            typename Chunk<W>::Window lw;
+            lw.init(s.code, s.bad, tid, k);
             uint64_t c[BASES_PER_LANE];
 #pragma unroll
-            for (int j = 0; j < BASES_PER_LANE; ++j) {
+            for (int j = 0; j < BASES_PER_LANE; ++j, lw.step()) {           // (unrolled: c[j] stays in registers)
                 c[j] = 0;
-                if ((m >> mshift) == 0) {
-                    uint64_t key = hi >> kshift;
+                if (lw.valid()) {
+                    auto key = lw.fwd();
                     if (canonicalise) key = kmer_canonical(key, k);
                     c[j] = table_get(t, key, n_ovf);
                 }
-                hi = (hi << 2) | (lo >> 62);
-                lo <<= 2;
-                m <<= 1;
             }
             if (off + BASES_PER_LANE <= n_out) {
                 ulonglong2* o = reinterpret_cast<ulonglong2*>(out + off);           // off is a multiple of 16: 128-byte aligned

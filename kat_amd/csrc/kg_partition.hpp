@@ -28,7 +28,7 @@
 namespace kg {
 
 constexpr int PART_BLOCK = 1024;                              // 16 waves, one workgroup per CU
-constexpr int PART_ITEMS = 16;                                // k-mers per lane per tile
+constexpr int PART_ITEMS = BASES_PER_LANE;                    // k-mers per lane per tile
 constexpr int TILE_ITEMS = PART_BLOCK * PART_ITEMS;           // 16384
 constexpr int L1_TILE_BYTES = TILE_ITEMS;                     // bytes staged per tile (16 per lane)
 constexpr int L1_TILE_STARTS = L1_TILE_BYTES - CHUNK_OVERLAP; // 16352 window starts per tile
@@ -286,27 +286,6 @@ static_assert(P1_BLOCK == (int)LEAN_BLOCK, "kg_l1_lean.hpp: the staged entries' 
 constexpr uint32_t P1_RCW = LEAN_RCW;     // LEAN: L.rcode lies this many words behind L.code (code | bad | rcode are one array to the copy-out: lean_entry_*)
 constexpr uint32_t P1_PAD = 0xFFFF0000u;   // "no k-mer" in pos[]: the bucket field of an entry is at most 1023, so the top bit says it; read as an entry it is tile position 0
 
-struct LaneWindow {                       // the 96-bit sliding window of kg_kernels.hpp's K1, as an object
-    uint64_t hi, lo, m;
-    uint32_t kshift, mshift;
-    template <typename BadT>
-    __device__ __forceinline__ void init(const uint32_t* code, const BadT* bad, uint32_t w, uint32_t k) {
-        hi = ((uint64_t)code[w] << 32) | code[w + 1];
-        lo = (uint64_t)code[w + 2] << 32;
-        m = ((uint64_t)bad[w] << 48) | ((uint64_t)bad[w + 1] << 32) | ((uint64_t)bad[w + 2] << 16);
-        kshift = 64 - 2 * k; mshift = 64 - k;
-    }
-    __device__ __forceinline__ bool valid() const { return (m >> mshift) == 0; }
-    __device__ __forceinline__ uint64_t fwd() const { return hi >> kshift; }
-    __device__ __forceinline__ void step() { hi = (hi << 2) | (lo >> 62); lo <<= 2; m <<= 1; }
-};
-
-__device__ __forceinline__ uint64_t canon_if(uint64_t fwd, uint32_t k, bool canonical) {
-    if (!canonical) return fwd;
-    const uint64_t rc = kmer_revcomp(fwd, k);
-    return rc < fwd ? rc : fwd;
-}
-
 // the k-mer whose window starts at tile position p, from the staged codes
 __device__ __forceinline__ uint64_t kmer_at(const uint32_t* code, uint32_t p, uint32_t k, bool canonical) {
     const uint32_t w = p >> 4, o = p & 15;
@@ -329,7 +308,7 @@ __device__ __forceinline__ u32x4 p1_tile_issue(const uint8_t* __restrict__ bases
 __device__ __forceinline__ void p1_tile_fix(const uint8_t* __restrict__ bases, uint64_t n, uint64_t tile_off, const u32x4& v, uint32_t (&w)[4]) {
     const uint64_t off = tile_off + (uint64_t)threadIdx.x * PART_ITEMS;
     w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    if (off + PART_ITEMS > n) {
+    if (off + PART_ITEMS > n) {          // load16_bytes, written out: called from here it is inlined one level deeper and the stage kernels' schedule moves
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             uint32_t x = 0;
@@ -341,19 +320,7 @@ __device__ __forceinline__ void p1_tile_fix(const uint8_t* __restrict__ bases, u
 }
 
 __device__ __forceinline__ void p1_tile_load(const uint8_t* __restrict__ bases, uint64_t n, uint64_t tile_off, uint32_t (&w)[4]) {
-    const uint64_t off = tile_off + (uint64_t)threadIdx.x * PART_ITEMS;
-    if (off + PART_ITEMS <= n) {
-        const uint4 v = *reinterpret_cast<const uint4*>(bases + off);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            uint32_t x = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) { uint64_t i = off + q * 4 + b; x |= (i < n ? (uint32_t)bases[i] : (uint32_t)'N') << (8 * b); }
-            w[q] = x;
-        }
-    }
+    load16<true>(bases, n, tile_off + (uint64_t)threadIdx.x * PART_ITEMS, w);       // (tiles start on 16-byte boundaries)
 }
 
 template <bool LEAN, bool SEG, int PB>
@@ -388,8 +355,7 @@ static __global__ void __launch_bounds__(P1_BLOCK)
 k_p1v2_count(DevTable t, PartGeom g, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_tiles, uint64_t tiles_per_wg,
              uint32_t* __restrict__ hist1) {
     __shared__ uint32_t s_hist[MAX_PARTS];
-    __shared__ uint32_t s_code[P1_BLOCK + 2];
-    __shared__ uint32_t s_bad[P1_BLOCK + 2];
+    __shared__ StagedTile<P1_BLOCK, 2> s;
     const uint32_t tid = threadIdx.x;
     const bool canonical = t.canonical != 0;
     for (uint32_t b = tid; b < MAX_PARTS; b += P1_BLOCK) s_hist[b] = 0;
@@ -403,12 +369,11 @@ k_p1v2_count(DevTable t, PartGeom g, const uint8_t* __restrict__ bases, uint64_t
         lds_barrier();
         uint32_t code, bad;
         encode16(w, code, bad);
-        s_code[tid] = code; s_bad[tid] = bad;
-        if (tid < 2) { s_code[P1_BLOCK + tid] = 0; s_bad[P1_BLOCK + tid] = 0xFFFF; }
+        s.stage(code, bad); s.pad();
         lds_barrier();
         if (tid < P1_LANES_WITH_STARTS) {
             LaneWindow lw;
-            lw.init(s_code, s_bad, tid, t.k);
+            lw.init(s.code, s.bad, tid, t.k);
 #pragma unroll 4
             for (int j = 0; j < PART_ITEMS; ++j, lw.step()) {
                 if (!lw.valid()) continue;

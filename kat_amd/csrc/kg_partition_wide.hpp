@@ -2,7 +2,7 @@
 //
 // The same three steps as kg_partition.hpp -- radix-partition a round's k-mers by the high digit of their region, split every bucket
 // by the low digit, apply every region's run to the region in LDS -- so that a wide k-mer costs streaming traffic instead of the three
-// random accesses and the global atomic of k_count_w (11 G k-mers/s whatever the table).  What differs from the one-word counter:
+// random accesses and the global atomic of the direct kernel (k_count<ALIGNED, true>: 11 G k-mers/s whatever the table).  What differs from the one-word counter:
 //   * the table's hash (keyw_hash) is not one to one, so an item is the k-mer itself at both levels: its two 63-bit halves, 16 bytes;
 //   * a slot is 20 bytes in three arrays (keys, keys_b, counts): a region of 6144 slots fills 120 KB of LDS, one workgroup per CU;
 //   * both levels are the EXACT edition (histogram, scan, scatter): no segment or run capacities, no overflow lists.  A workgroup
@@ -11,11 +11,10 @@
 //     one tile within microseconds of each other and meet in L2.
 // The apply walks a region's run with table_add_w's protocol (claim the first half with a CAS, then the second) on the LDS copy;
 // a region without a free slot spills the k-mer to a list the host inserts through the direct kernel after a regrow.
-// Replaces the same reference code as k_count_w: mer_iterator + multi-word mer_dna (mer_iterator.hpp:59-89, mer_dna.hpp:235-258)
+// Replaces the same reference code as the direct kernel: mer_iterator + multi-word mer_dna (mer_iterator.hpp:59-89, mer_dna.hpp:235-258)
 // and hash_counter::add (hash_counter.hpp:90-113).
 #pragma once
 #include "kg_partition.hpp"
-#include "kg_wide.hpp"
 
 namespace kg {
 
@@ -29,48 +28,27 @@ static_assert(BASES_PER_LANE == 16 && W1_TILE_STARTS % 16 == 0, "tiles start on 
 
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));              // an item: {a, b} of KeyW, one 16-byte access
 
+typedef StagedTile<W1_BLOCK, 4> W1Tile;
+
 // Stage one tile (512 lanes x 16 bytes) as 2-bit codes + validity flags.  Ends with a barrier.
-__device__ __forceinline__ void w1_stage(uint32_t* s_code, uint32_t* s_bad, const uint8_t* __restrict__ bases, uint64_t n, uint64_t tile) {
+__device__ __forceinline__ void w1_stage(W1Tile& s, const uint8_t* __restrict__ bases, uint64_t n, uint64_t tile) {
     uint32_t w[4];
     p1_tile_load(bases, n, tile * W1_TILE_STARTS, w);                      // (bytes past n read as 'N')
     uint32_t code, bad;
     encode16(w, code, bad);
     __syncthreads();                                                      // the previous tile's windows have been read
-    s_code[threadIdx.x] = code;
-    s_bad[threadIdx.x] = bad;
-    if (threadIdx.x < 4) { s_code[W1_BLOCK + threadIdx.x] = 0; s_bad[W1_BLOCK + threadIdx.x] = 0xFFFF; }
+    s.stage(code, bad); s.pad();
     __syncthreads();
 }
 
 // The 16 windows of lane t (starts 16t .. 16t+15 of the tile): f(key) for every valid one, key canonical if the table is.
-// The 160-bit register window of k_count_w.
 template <class F>
-__device__ __forceinline__ void w1_windows(const uint32_t* s_code, const uint32_t* s_bad, uint32_t k, bool canonical, F f) {
-    const uint32_t t = threadIdx.x;
-    uint64_t hi = ((uint64_t)s_code[t] << 32) | s_code[t + 1];
-    uint64_t lo = ((uint64_t)s_code[t + 2] << 32) | s_code[t + 3];
-    uint64_t nx = (uint64_t)s_code[t + 4] << 32;
-    uint64_t m = ((uint64_t)s_bad[t] << 48) | ((uint64_t)s_bad[t + 1] << 32) | ((uint64_t)s_bad[t + 2] << 16) | s_bad[t + 3];
-    uint64_t mn = (uint64_t)s_bad[t + 4] << 48;
-    const uint32_t s = 128 - 2 * k, mshift = 64 - k;                      // s: 2 .. 62, mshift: 1 .. 31
+__device__ __forceinline__ void w1_windows(const W1Tile& s, uint32_t k, bool canonical, F f) {
+    LaneWindowW lw;
+    lw.init(s.code, s.bad, threadIdx.x, k);
 #pragma unroll 2
-    for (int j = 0; j < BASES_PER_LANE; ++j) {
-        if ((m >> mshift) == 0) {
-            const uint64_t fhi = hi >> s, flo = (lo >> s) | (hi << (64 - s));
-            KeyW key = keyw_from_words(fhi, flo);
-            if (canonical) {
-                uint64_t rhi, rlo;
-                revcomp_words(fhi, flo, k, rhi, rlo);
-                if (rhi < fhi || (rhi == fhi && rlo < flo)) key = keyw_from_words(rhi, rlo);
-            }
-            f(key);
-        }
-        hi = (hi << 2) | (lo >> 62);
-        lo = (lo << 2) | (nx >> 62);
-        nx <<= 2;
-        m = (m << 1) | (mn >> 63);
-        mn <<= 1;
-    }
+    for (int j = 0; j < BASES_PER_LANE; ++j, lw.step())
+        if (lw.valid()) f(lw.counted(k, canonical));
 }
 
 // ---- level 1 ----
@@ -80,16 +58,15 @@ template <bool SCATTER>
 __global__ void __launch_bounds__(W1_BLOCK)
 k_w1(DevTable t, uint32_t P1, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_tiles, uint64_t tiles_per_wg,
      uint32_t* __restrict__ hist1, const uint64_t* __restrict__ offs, u64x2* __restrict__ l1_buf) {
-    __shared__ uint32_t s_code[W1_BLOCK + 4];
-    __shared__ uint32_t s_bad[W1_BLOCK + 4];
+    __shared__ W1Tile s;
     __shared__ unsigned long long s_cur[MAX_PARTS];                       // histogram / next free position of this workgroup's share of bucket b
     const uint32_t tid = threadIdx.x;
     for (uint32_t b = tid; b < MAX_PARTS; b += W1_BLOCK) s_cur[b] = SCATTER && b < P1 ? offs[(uint64_t)blockIdx.x * P1 + b] : 0ULL;
     const uint64_t t0 = (uint64_t)blockIdx.x * tiles_per_wg, t1 = min(t0 + tiles_per_wg, n_tiles);
     for (uint64_t tile = t0; tile < t1; ++tile) {
-        w1_stage(s_code, s_bad, bases, n, tile);                           // (its first barrier also covers the initialisation of s_cur)
+        w1_stage(s, bases, n, tile);                                      // (its first barrier also covers the initialisation of s_cur)
         if (tid < W1_LANES_WITH_STARTS)
-            w1_windows(s_code, s_bad, t.k, t.canonical != 0, [&](KeyW key) {
+            w1_windows(s, t.k, t.canonical != 0, [&](KeyW key) {
                 const uint32_t b = digit1_of_hash(keyw_hash(key), P1);
                 const unsigned long long at = atomicAdd(&s_cur[b], 1ULL);
                 if (SCATTER) { u64x2 it; it.x = key.a; it.y = key.b; l1_buf[at] = it; }

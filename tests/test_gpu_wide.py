@@ -173,7 +173,7 @@ def test_cli_hist_gcp_comp_wide(ko, refdata, tmp_path):
 
 @pytest.mark.parametrize("k,canonical", [(33, True), (50, False), (63, True)])
 def test_profile_wide(ko, engine, k, canonical):
-    """katgpu_table_profile_* (k_profile_w) against the oracle's per-position lookups: shared, shuffled and ragged probes, both
+    """katgpu_table_profile_* (k_profile<ALIGNED, true>) against the oracle's per-position lookups: shared, shuffled and ragged probes, both
     canonicalisation choices, the device form at odd alignments, a count above 32 bits."""
     from tests.test_gpu_sect import random_seq
     rng = np.random.default_rng(k)
