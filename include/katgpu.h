@@ -181,6 +181,34 @@ int katgpu_table_seq_hits_host(katgpu_table* t, const char* bases, size_t n, con
                                size_t n_rec, int canonicalise, uint64_t* hits);
 int katgpu_table_seq_hits_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
                                  const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, uint64_t* dev_hits);
+/* `kat sect -n` and `kat cold`: what Sect::processSeq (src/sect.cc:490-589) and Cold::processSeq (src/cold.cc:303-406) keep of a
+ * record's per-position counts, computed on the device.  Records are given as for katgpu_table_seq_hits_*: record r is
+ * bases[rec_start[r], rec_start[r] + rec_len[r]), in increasing order and disjoint; a window belongs to a record when it lies wholly
+ * inside it; nb = rec_len - k + 1 when rec_len >= k, else 0.  Both key widths and both table layouts; a count held in the side table
+ * enters with its full value.  The host form validates the records (KATGPU_ERR_INVALID_ARG, the messages of katgpu_table_seq_hits_host);
+ * no per-position array crosses the bus in either form: sizeof(katgpu_record_stats) per record comes back.
+ * Records of more than 960 windows are "long": their median is selected in passes over their counts in device memory, the others'
+ * in LDS.  Device memory of the host form, beyond the table and from the context's pool: the records go through in batches of at most
+ * B = 2^25 bases and 2^20 records, a record longer than B being a batch of its own: max(B, L) + 64 bytes of bases, with L the longest
+ * record, and 64 bytes per record of a batch.  On top of the batch, only while a batch with long records runs: 8 bytes per window of
+ * its long records -- a batch ends before they would have more than B / 4 = 2^23 windows between them, so this is at most 8 bytes per
+ * window of the longest single record, or 64 MiB where that is more -- 2088 bytes per long record and 4 bytes per record.
+ * KATGPU_ERR_NOMEM, with a message, when that cannot be had.
+ * The _device form takes device pointers; it is asynchronous on the context's stream unless a record is long, in which case it takes
+ * 8 bytes per window of the long records (and the per-record bytes above) from the pool and returns when the work is done. */
+typedef struct katgpu_record_stats {   /* one record; all exact integers */
+    uint64_t sum;        /* sum of the counts of the record's valid windows                         */
+    uint64_t median;     /* sorted(counts of ALL nb windows, an invalid window counting 0)[nb / 2]; */
+                         /* 0 when nb == 0                                                          */
+    uint64_t non_zero;   /* valid windows whose count is not 0                                      */
+    uint64_t invalid;    /* windows holding a byte outside ACGTacgt                                 */
+    uint64_t gc_bases;   /* bytes G g C c in the record                                             */
+    uint64_t n_bases;    /* bytes N n in the record (other junk counts for neither)                 */
+} katgpu_record_stats;
+int katgpu_table_record_stats_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                                   size_t n_rec, int canonicalise, katgpu_record_stats* out);
+int katgpu_table_record_stats_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                     const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, katgpu_record_stats* dev_out);
 /* All (key,count) pairs in unspecified order (the eager_iterator walk, JF/.../large_hash_iterator.hpp:28-65).
  * Pass cap = 0 to query *n_out only. */
 int katgpu_table_export(katgpu_table* t, uint64_t* keys, uint64_t* counts, size_t cap, size_t* n_out);

@@ -40,7 +40,11 @@ EXPORTS = (
     "katgpu_comm_transport_note", "katgpu_comm_distinct_devices", "katgpu_comm_barrier", "katgpu_exchange_merge", "katgpu_allreduce_u64", "katgpu_comm_stats",
     "katgpu_table_packed_records", "katgpu_table_extract_packed", "katgpu_table_merge_regions_packed", "katgpu_comm_wire", "katgpu_exchange_begin", "katgpu_exchange_finish",
     "katgpu_table_filter", "katgpu_table_seq_hits_host", "katgpu_table_seq_hits_device",
+    "katgpu_table_record_stats_host", "katgpu_table_record_stats_device",
 )
+
+# katgpu_record_stats: one record of Table.record_stats
+RECORD_STATS = np.dtype([(f, np.uint64) for f in ("sum", "median", "non_zero", "invalid", "gc_bases", "n_bases")])
 
 
 class Geometry(C.Structure):
@@ -113,6 +117,8 @@ def load_library():
     L.katgpu_table_filter.argtypes = [vp, u64, u64, u32, u32, C.c_int, C.c_int, pp, pp, vp]
     L.katgpu_table_seq_hits_host.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp]
     L.katgpu_table_seq_hits_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp]
+    L.katgpu_table_record_stats_host.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp]
+    L.katgpu_table_record_stats_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp]
     L.katgpu_hist.argtypes = [vp, u64, u64, u64, vp, sz]
     L.katgpu_gcp.argtypes = [vp, C.c_double, u32, vp]
     L.katgpu_comp.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, u32, u32, vp, vp, vp]
@@ -557,6 +563,26 @@ class Table:
         canon = self.canonical if canonicalise is None else canonicalise
         p = [getattr(x, "ptr", x) for x in (dev_bases, dev_rec_start, dev_rec_len, dev_hits)]
         self.engine._chk(self.engine.L.katgpu_table_seq_hits_device(self.h, p[0], n, p[1], p[2], n_rec, int(bool(canon)), p[3]))
+
+    def record_stats(self, bases, rec_start, rec_len, canonicalise=None):
+        """Per-record coverage statistics (katgpu_table_record_stats_host): a structured array (RECORD_STATS) of n_rec entries with the
+        fields sum, median, non_zero, invalid, gc_bases, n_bases."""
+        if isinstance(bases, str):
+            bases = bases.encode()
+        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
+        st, ln = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_len, np.uint64)
+        assert st.size == ln.size
+        out = np.zeros(st.size, RECORD_STATS)
+        canon = self.canonical if canonicalise is None else canonicalise
+        self.engine._chk(self.engine.L.katgpu_table_record_stats_host(self.h, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size,
+                                                                      int(bool(canon)), out.ctypes.data))
+        return out
+
+    def record_stats_device(self, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, dev_out, canonicalise=None):
+        """Device-resident form: DeviceBuffers or raw device addresses; `dev_out` takes n_rec entries of RECORD_STATS (48 bytes each)."""
+        canon = self.canonical if canonicalise is None else canonicalise
+        p = [getattr(x, "ptr", x) for x in (dev_bases, dev_rec_start, dev_rec_len, dev_out)]
+        self.engine._chk(self.engine.L.katgpu_table_record_stats_device(self.h, p[0], n, p[1], p[2], n_rec, int(bool(canon)), p[3]))
 
     def export(self):
         n = C.c_size_t()

@@ -328,6 +328,9 @@ private:
     };
     void processSeqFile();
     void processSeq(Record& r, const uint64_t* counts);
+    void processSeqStats(Record& r, const katgpu_record_stats& st);
+    void recordScalars(Record& r, uint64_t nbNonZero, uint64_t nbInvalid, uint64_t gcBases, uint64_t nBases);
+    void gcText(Record& r, const std::vector<int16_t>& gc);
     void regions(std::string& out, const Record& r, const uint64_t* counts, size_t nb, uint32_t min_count, uint32_t max_count);
     void merge();
     InputHandler input;
@@ -365,7 +368,7 @@ private:
         double mean = 0.0, gc = 0.0, percentInvalid = 0.0, percentNonZero = 0.0, percentNonZeroCorrected = 0.0;
     };
     void processSeqFile();
-    void processSeq(Row& r, const std::string& seq, const uint64_t* readsCounts, const uint64_t* asmCounts);
+    void processSeq(Row& r, const std::string& seq, const katgpu_record_stats& rd, const katgpu_record_stats& as);
     InputHandler reads, assembly;
     std::string outputPrefix;
     uint16_t gcBins = 1001, cvgBins = 1001, threads = 1;

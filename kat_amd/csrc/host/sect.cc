@@ -3,7 +3,8 @@
 // The reference walks each record with substr + validKmer + mer_dna + JellyfishHelper::getCount (src/sect.cc:516-535), one
 // record per std::thread.  Here a batch of records is joined into one base buffer and profiled by a single
 // katgpu_table_profile_host call; what stays on the host is what the reference also does after the lookups: the
-// per-record statistics and the text.  Records are read with the semantics of the vendored SeqAn 2.0.0 reader
+// per-record statistics and the text.  When no per-position output is asked for (-n without -E / -F) the statistics are the
+// device's too (katgpu_table_record_stats_host) and no count comes back.  Records are read with the semantics of the vendored SeqAn 2.0.0 reader
 // (deps/seqan-library-2.0.0/include/seqan/seq_io/fasta_fastq.h:306-380, CharString target).
 #include "kat_host.hpp"
 
@@ -184,6 +185,67 @@ void Sect::printContaminationMatrix(std::ostream& out, const string& seq_file) {
     contamination_mx.printMatrix(out);
 }
 
+// The scalars of a record that follow from its length and four tallies (src/sect.cc:544-600).
+void Sect::recordScalars(Record& r, uint64_t nbNonZero, uint64_t nbInvalid, uint64_t gcBases, uint64_t nBases) {
+    const uint64_t seqLength = r.seq->size();
+    const int64_t nbCounts = (int64_t)seqLength - input.merLen + 1;
+    r.length = (uint32_t)seqLength;
+    r.nonZero = (uint32_t)nbNonZero;
+    r.percentNonZero = nbNonZero == 0 || nbCounts <= 0 ? 0.0 : ((double)nbNonZero / (double)nbCounts) * 100.0;
+    r.invalid = (uint32_t)nbInvalid;
+    r.percentInvalid = nbInvalid == 0 || nbCounts <= 0 ? 0.0 : ((double)nbInvalid / (double)nbCounts) * 100.0;
+    const uint64_t notInvalid = (uint64_t)nbCounts - nbInvalid;
+    r.percentNonZeroCorrected = nbNonZero == 0 || notInvalid <= 0 ? 0.0 : ((double)nbNonZero / (double)notInvalid) * 100.0;
+
+    volatile double num = (double)gcBases, den = (double)(seqLength - nBases);                  // run-time division: 0/0 is the x86 default NaN ("-nan")
+    r.gc = num / den;
+
+    // src/sect.cc:581-600.  average_cvg is never assigned there, so the coverage bin is 0 with or without
+    // --cvg_logscale (uint16_t(-inf) is 0 on x86, like uint16_t(NaN) for the GC bin of an all-N record).
+    const double xd = r.gc * gcBins;
+    r.mx_x = std::isnan(xd) ? 0 : (uint16_t)xd;
+    r.mx_y = 0;
+}
+
+// printGCCounts, :352-371; gc[j] = G+C of window j, -1 for an invalid one
+void Sect::gcText(Record& r, const vector<int16_t>& gc) {
+    const uint16_t k = input.merLen;
+    vector<string> pct(k + 1);
+    char tmp[32];
+    for (uint16_t g = 0; g <= k; g++) { snprintf(tmp, sizeof tmp, "%.1f", ((double)g / (double)k) * 100.0); pct[g] = tmp; }
+    string& o = r.gc_txt;
+    o += '>'; o += *r.name; o += '\n';
+    if (!gc.empty()) {
+        for (size_t j = 0; j < gc.size(); j++) { if (j) o += ' '; o += gc[j] < 0 ? string("-0.1") : pct[gc[j]]; }
+        o += '\n';
+    } else o += "0.0\n";
+}
+
+// A record from the device's statistics (katgpu_table_record_stats_host): no per-position output was asked for.  The GC line of -g
+// needs the bases only.
+void Sect::processSeqStats(Record& r, const katgpu_record_stats& st) {
+    const uint16_t k = input.merLen;
+    const string& seq = *r.seq;
+    const uint64_t seqLength = seq.size();
+    const int64_t nbCounts = (int64_t)seqLength - k + 1;
+    r.median = 0; r.mean = 0.0;
+    if (nbCounts > 0) {
+        r.median = (uint32_t)(double)st.median;
+        r.mean = (double)st.sum / (double)nbCounts;
+    }
+    recordScalars(r, st.non_zero, st.invalid, st.gc_bases, st.n_bases);
+    if (outputGCStats) {
+        vector<int16_t> gc(nbCounts > 0 ? (size_t)nbCounts : 0);
+        uint32_t bad = 0, g = 0;
+        if (!gc.empty()) for (size_t i = 0; i < seqLength; i++) {
+            bad += !isBase(seq[i]); g += isGC(seq[i]);
+            if (i >= k) { bad -= !isBase(seq[i - k]); g -= isGC(seq[i - k]); }
+            if (i + 1 >= k) gc[i + 1 - k] = bad ? (int16_t)-1 : (int16_t)g;
+        }
+        gcText(r, gc);
+    }
+}
+
 // Everything the reference's processSeq + print* produce for one record, from the device's per-position counts.
 void Sect::processSeq(Record& r, const uint64_t* cnt) {                                         // src/sect.cc:486-603
     const uint16_t k = input.merLen;
@@ -213,28 +275,13 @@ void Sect::processSeq(Record& r, const uint64_t* cnt) {                         
         r.median = (uint32_t)(double)sorted[nb / 2];
         r.mean = (double)sum / (double)nbCounts;
     }
-    r.length = (uint32_t)seqLength;
-    r.nonZero = (uint32_t)nbNonZero;
-    r.percentNonZero = nbNonZero == 0 || nbCounts <= 0 ? 0.0 : ((double)nbNonZero / (double)nbCounts) * 100.0;
-    r.invalid = (uint32_t)nbInvalid;
-    r.percentInvalid = nbInvalid == 0 || nbCounts <= 0 ? 0.0 : ((double)nbInvalid / (double)nbCounts) * 100.0;
-    const uint64_t notInvalid = (uint64_t)nbCounts - nbInvalid;
-    r.percentNonZeroCorrected = nbNonZero == 0 || notInvalid <= 0 ? 0.0 : ((double)nbNonZero / (double)notInvalid) * 100.0;
-
     uint64_t gs = 0, cs = 0, ns = 0;
     for (char c : seq) {
         if (c == 'G' || c == 'g') gs++;
         else if (c == 'C' || c == 'c') cs++;
         else if (c == 'N' || c == 'n') ns++;
     }
-    volatile double num = (double)(gs + cs), den = (double)(seqLength - ns);                    // run-time division: 0/0 is the x86 default NaN ("-nan")
-    r.gc = num / den;
-
-    // src/sect.cc:581-600.  average_cvg is never assigned there, so the coverage bin is 0 with or without
-    // --cvg_logscale (uint16_t(-inf) is 0 on x86, like uint16_t(NaN) for the GC bin of an all-N record).
-    const double xd = r.gc * gcBins;
-    r.mx_x = std::isnan(xd) ? 0 : (uint16_t)xd;
-    r.mx_y = 0;
+    recordScalars(r, nbNonZero, nbInvalid, gs + cs, ns);
 
     if (!noCountStats) {                                                                        // printCounts, :328-346
         string& o = r.cvg_txt;
@@ -246,17 +293,7 @@ void Sect::processSeq(Record& r, const uint64_t* cnt) {                         
             o += '\n';
         } else o += "0\n";
     }
-    if (outputGCStats) {                                                                        // printGCCounts, :352-371
-        vector<string> pct(k + 1);
-        char tmp[32];
-        for (uint16_t g = 0; g <= k; g++) { snprintf(tmp, sizeof tmp, "%.1f", ((double)g / (double)k) * 100.0); pct[g] = tmp; }
-        string& o = r.gc_txt;
-        o += '>'; o += *r.name; o += '\n';
-        if (nb) {
-            for (size_t j = 0; j < nb; j++) { if (j) o += ' '; o += gc[j] < 0 ? string("-0.1") : pct[gc[j]]; }
-            o += '\n';
-        } else o += "0.0\n";
-    }
+    if (outputGCStats) gcText(r, gc);
     if (extractNR) regions(r.nr_txt, r, cnt, nb, 1, minRepeat);
     if (extractR) regions(r.r_txt, r, cnt, nb, minRepeat, maxRepeat);
 }
@@ -319,8 +356,16 @@ void Sect::processSeqFile() {                                                   
     vector<string> names, seqs;
     vector<Record> recs;
     string joined;
-    vector<uint64_t> counts;
-    vector<size_t> offs;
+    vector<uint64_t> counts, offs, lens;
+    vector<katgpu_record_stats> stats;
+    const bool stats_only = noCountStats && !extractNR && !extractR;
+    // KATGPU_TIMING: where the phase's wall time goes (reader | joined buffer | device call | per-record host work | text), one line on stderr
+    double t_part[5] = {0, 0, 0, 0, 0};
+    auto lap = [&, t = std::chrono::steady_clock::now()](int part) mutable {
+        const auto now = std::chrono::steady_clock::now();
+        t_part[part] += std::chrono::duration<double>(now - t).count();
+        t = now;
+    };
     while (!reader.atEnd()) {
         if (verbose) std::cerr << "Loading Batch of sequences... ";
         names.clear(); seqs.clear();
@@ -331,19 +376,30 @@ void Sect::processSeqFile() {                                                   
             bases += seqs.back().size() + 1;
         }
         const size_t n = names.size();
+        lap(0);
         if (verbose) std::cerr << "Loaded " << n << " records.  Processing batch... ";
 
         // analyseBatch(): one device call for every window of every record of the batch
         joined.clear(); joined.reserve(bases);
         offs.assign(n, 0);
         for (size_t i = 0; i < n; i++) { offs[i] = joined.size(); joined += seqs[i]; joined += '\n'; }   // a newline can never be in a record
-        if (counts.size() < joined.size()) counts.resize(joined.size());
-        Engine::check(katgpu_table_profile_host(input.hash, joined.data(), joined.size(), input.canonical ? 1 : 0, counts.data()));
+        lap(1);
+        if (stats_only) {                                     // nothing per position is written: the device reduces the counts per record
+            lens.resize(n); stats.resize(n);
+            for (size_t i = 0; i < n; i++) lens[i] = seqs[i].size();
+            Engine::check(katgpu_table_record_stats_host(input.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, input.canonical ? 1 : 0, stats.data()));
+        } else {
+            if (counts.size() < joined.size()) counts.resize(joined.size());
+            Engine::check(katgpu_table_profile_host(input.hash, joined.data(), joined.size(), input.canonical ? 1 : 0, counts.data()));
+        }
+        lap(2);
 
         recs.assign(n, Record());
         for (size_t i = 0; i < n; i++) { recs[i].name = &names[i]; recs[i].seq = &seqs[i]; }
         const unsigned workers = std::max<unsigned>(1, std::min<unsigned>(threads, (unsigned)n));
-        auto work = [&](unsigned th) { for (size_t i = th; i < n; i += workers) processSeq(recs[i], counts.data() + offs[i]); };   // processInterlaced, :477-483
+        auto work = [&](unsigned th) {                                                          // processInterlaced, :477-483
+            for (size_t i = th; i < n; i += workers) { if (stats_only) processSeqStats(recs[i], stats[i]); else processSeq(recs[i], counts.data() + offs[i]); }
+        };
         if (workers == 1) work(0);
         else {
             vector<std::thread> team;
@@ -351,6 +407,7 @@ void Sect::processSeqFile() {                                                   
             for (auto& t : team) t.join();
         }
 
+        lap(3);
         char line[512];
         for (size_t i = 0; i < n; i++) {
             const Record& r = recs[i];
@@ -364,8 +421,12 @@ void Sect::processSeqFile() {                                                   
             cvg_gc_stream << *r.name << line;
             if (r.mx_x < gcBins && r.mx_y < cvgBins) contamination_mx.data()[(size_t)r.mx_x * cvgBins + r.mx_y] += seqs[i].size();
         }
+        lap(4);
         if (verbose) std::cerr << "done" << endl;
     }
+    if (getenv("KATGPU_TIMING"))
+        fprintf(stderr, "katgpu_timing {\"phase\": \"sect_coverage\", \"read_s\": %.3f, \"join_s\": %.3f, \"device_call_s\": %.3f, \"records_s\": %.3f, \"text_s\": %.3f}\n",
+                t_part[0], t_part[1], t_part[2], t_part[3], t_part[4]);
     cout << " done.";
     cout.flush();
 }
@@ -410,8 +471,8 @@ int Sect::main(int argc, char* argv[]) {                                        
 }
 
 // ================================================================ Cold (src/cold.cc) ==============================
-// Every record of the assembly profiled against the reads hash and against the assembly's own hash: two
-// katgpu_table_profile_host calls per batch, one -stats.tsv row per record.
+// Every record of the assembly against the reads hash and against the assembly's own hash: two
+// katgpu_table_record_stats_host calls per batch, one -stats.tsv row per record.
 
 Cold::Cold(const vector<string>& reads_files, const string& asm_file) {                          // src/cold.cc:67-77
     reads.setMultipleInputs(reads_files);
@@ -438,32 +499,16 @@ void Cold::execute() {                                                          
     }
 }
 
-void Cold::processSeq(Row& r, const string& seq, const uint64_t* readsCounts, const uint64_t* asmCounts) {   // src/cold.cc:303-408
+void Cold::processSeq(Row& r, const string& seq, const katgpu_record_stats& rd, const katgpu_record_stats& as) {   // src/cold.cc:303-408
     const uint16_t k = reads.merLen;
     const uint64_t seqLength = seq.size();
     const int64_t nbCounts = (int64_t)seqLength - k + 1;
-    const size_t nb = nbCounts > 0 ? (size_t)nbCounts : 0;
-    uint64_t nbNonZero = 0, nbInvalid = 0;
+    const uint64_t nbNonZero = rd.non_zero, nbInvalid = rd.invalid;
     r.median = 0; r.mean = 0.0; r.asmCn = 0;
-    if (nb) {
-        uint32_t bad = 0;
-        uint64_t sum = 0;
-        for (size_t i = 0; i < seqLength; i++) {                     // rolling validKmer: invalid windows count for neither sum nor nonZero
-            bad += !isBase(seq[i]);
-            if (i >= k) bad -= !isBase(seq[i - k]);
-            if (i + 1 >= k) {
-                const size_t w = i + 1 - k;
-                if (bad) nbInvalid++;
-                else { sum += readsCounts[w]; if (readsCounts[w]) nbNonZero++; }
-            }
-        }
-        vector<uint64_t> sorted(readsCounts, readsCounts + nb);
-        std::nth_element(sorted.begin(), sorted.begin() + nb / 2, sorted.end());
-        r.median = (uint32_t)(double)sorted[nb / 2];
-        r.mean = (double)sum / (double)nbCounts;
-        sorted.assign(asmCounts, asmCounts + nb);
-        std::nth_element(sorted.begin(), sorted.begin() + nb / 2, sorted.end());
-        r.asmCn = (uint32_t)(double)sorted[nb / 2];
+    if (nbCounts > 0) {
+        r.median = (uint32_t)(double)rd.median;
+        r.mean = (double)rd.sum / (double)nbCounts;
+        r.asmCn = (uint32_t)(double)as.median;
     }
     r.length = (uint32_t)seqLength;
     r.nonZero = (uint32_t)nbNonZero;
@@ -472,13 +517,7 @@ void Cold::processSeq(Row& r, const string& seq, const uint64_t* readsCounts, co
     r.percentInvalid = nbInvalid == 0 || nbCounts <= 0 ? 0.0 : ((double)nbInvalid / (double)nbCounts) * 100.0;
     const uint64_t notInvalid = (uint64_t)nbCounts - nbInvalid;
     r.percentNonZeroCorrected = nbNonZero == 0 || notInvalid <= 0 ? 0.0 : ((double)nbNonZero / (double)notInvalid) * 100.0;
-    uint64_t gs = 0, cs = 0, ns = 0;
-    for (char c : seq) {
-        if (c == 'G' || c == 'g') gs++;
-        else if (c == 'C' || c == 'c') cs++;
-        else if (c == 'N' || c == 'n') ns++;
-    }
-    volatile double num = (double)(gs + cs), den = (double)(seqLength - ns);
+    volatile double num = (double)rd.gc_bases, den = (double)(seqLength - rd.n_bases);
     r.gc = num / den;
 }
 
@@ -495,8 +534,8 @@ void Cold::processSeqFile() {                                                   
     vector<string> names, seqs;
     vector<Row> rows;
     string joined;
-    vector<uint64_t> rcounts, acounts;
-    vector<size_t> offs;
+    vector<katgpu_record_stats> rstats, astats;
+    vector<uint64_t> offs, lens;
     while (!reader.atEnd()) {
         if (verbose) std::cerr << "Loading Batch of sequences... ";
         names.clear(); seqs.clear();
@@ -509,21 +548,15 @@ void Cold::processSeqFile() {                                                   
         const size_t n = names.size();
         if (verbose) std::cerr << "Loaded " << n << " records.  Processing batch... ";
         joined.clear(); joined.reserve(bases);
-        offs.assign(n, 0);
-        for (size_t i = 0; i < n; i++) { offs[i] = joined.size(); joined += seqs[i]; joined += '\n'; }
-        if (rcounts.size() < joined.size()) { rcounts.resize(joined.size()); acounts.resize(joined.size()); }
-        Engine::check(katgpu_table_profile_host(reads.hash, joined.data(), joined.size(), reads.canonical ? 1 : 0, rcounts.data()));
-        Engine::check(katgpu_table_profile_host(assembly.hash, joined.data(), joined.size(), assembly.canonical ? 1 : 0, acounts.data()));
+        offs.assign(n, 0); lens.assign(n, 0);
+        for (size_t i = 0; i < n; i++) { offs[i] = joined.size(); lens[i] = seqs[i].size(); joined += seqs[i]; joined += '\n'; }
+        rstats.resize(n); astats.resize(n);
+        // the device reduces every record's counts: everything from the reads hash, the median (asm_cn) from the assembly's
+        Engine::check(katgpu_table_record_stats_host(reads.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, reads.canonical ? 1 : 0, rstats.data()));
+        Engine::check(katgpu_table_record_stats_host(assembly.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, assembly.canonical ? 1 : 0, astats.data()));
 
         rows.assign(n, Row());
-        const unsigned workers = std::max<unsigned>(1, std::min<unsigned>(threads, (unsigned)n));
-        auto work = [&](unsigned th) { for (size_t i = th; i < n; i += workers) processSeq(rows[i], seqs[i], rcounts.data() + offs[i], acounts.data() + offs[i]); };
-        if (workers == 1) work(0);
-        else {
-            vector<std::thread> team;
-            for (unsigned th = 0; th < workers; th++) team.emplace_back(work, th);
-            for (auto& t : team) t.join();
-        }
+        for (size_t i = 0; i < n; i++) processSeq(rows[i], seqs[i], rstats[i], astats[i]);
         char line[512];
         for (size_t i = 0; i < n; i++) {                                                        // printStatTable, src/cold.cc:254-271
             const Row& r = rows[i];

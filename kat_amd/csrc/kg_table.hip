@@ -1,13 +1,15 @@
 // kg_table.hip -- the HBM-resident count table behind katgpu_table: geometry and layout choice, allocation, regrow
 // (hash_counter::double_size), statistics, batch lookups and per-position profiles, record export / merge, the k-mer filter and the
-// per-record hit counts of `kat filter`.
+// per-record hit counts of `kat filter`, the per-record coverage statistics of `kat sect -n` and `kat cold`.
 #include "kg_host.hpp"
 #include "kg_kernels.hpp"
 #include "kg_wide.hpp"
 #include "kg_filter.hpp"
+#include "kg_record_stats.hpp"
 
 static const uint32_t g_region_slots = (uint32_t)hook_u64("KATGPU_TEST_REGION_SLOTS", REGION_SLOTS);
 static const bool g_no_packed = hook("KATGPU_NO_PACKED") != nullptr;   // tests / A-B: every table in the KV12 layout
+static const bool g_forbid_profile_host = hook_u64("KATGPU_TEST_FORBID_PROFILE_HOST", 0) != 0;   // tests: a driver that should not need per-position counts asks for none
 
 // like_p1/like_p2 != 0: adopt that region grid (so that comp can join region against region) and take up the capacity in the
 // region size, if a region of the resulting size still fits LDS.
@@ -277,6 +279,7 @@ extern "C" int katgpu_table_profile_device(katgpu_table* t, const uint8_t* dev_b
 // k-1 bases it shares with the next one), so any length fits next to the table.
 extern "C" int katgpu_table_profile_host(katgpu_table* t, const char* bases, size_t n, int canonicalise, uint64_t* counts) {
     if (!t || (n && (!bases || !counts))) return KATGPU_ERR_INVALID_ARG;
+    if (g_forbid_profile_host) return fail(t->ctx, KATGPU_ERR_INVALID_ARG, "katgpu_table_profile_host is forbidden (KATGPU_TEST_FORBID_PROFILE_HOST)");
     const uint32_t k = t->dev().k;
     if (n < k) return KATGPU_OK;
     katgpu_ctx* c = t->ctx;
@@ -655,5 +658,159 @@ extern "C" int katgpu_table_seq_hits_host(katgpu_table* t, const char* bases, si
     pool_release(c, db); pool_release(c, dr);
     if (rc) return rc;
     if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "seq hits: %s", hipGetErrorString(e));
+    return KATGPU_OK;
+}
+
+// ------------------------------------------------------------------ per-record coverage statistics (kat sect -n, kat cold) ----
+
+static const uint32_t g_stats_short = (uint32_t)std::min<uint64_t>(hook_u64("KATGPU_TEST_STATS_SHORT", RS_SHORT_WINDOWS), RS_SHORT_WINDOWS);   // tests: the short / long limit, in windows
+static const size_t g_stats_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_STATS_BATCH", (uint64_t)32 << 20), 1);                    // tests: bases per batch of the host form
+static_assert(sizeof(katgpu_record_stats) == RS_FIELDS * sizeof(uint64_t), "the kernels write a record's statistics as six words");
+
+// Everything on the stream: the result cleared, K11 over the tiles, and, when n_long records are long (long_windows windows in all),
+// their slots, K12 and the eight passes of K13 over those windows.  *ws is the workspace of the long records (null: none), to be
+// pool_release'd once the stream has run.  Two timed sections: the second only when there are long records.
+static int launch_record_stats(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec,
+                               int canonicalise, katgpu_record_stats* dev_out, uint64_t n_long, uint64_t long_windows, void** ws) {
+    katgpu_ctx* c = t->ctx;
+    *ws = nullptr;
+    HIPCHK(c, hipMemsetAsync(dev_out, 0, n_rec * sizeof(katgpu_record_stats), c->stream));
+    if (!n || !n_rec) return KATGPU_OK;
+    const DevTable& d = t->dev();
+    const uint32_t k = d.k;
+    const bool wide = d.keys_b != nullptr;
+    const bool aligned = (reinterpret_cast<uintptr_t>(dev_bases) & 15) == 0;
+    const uint64_t n_out = n >= k ? n - k + 1 : 0;
+    unsigned long long* o = (unsigned long long*)dev_out;
+    {
+        ScopedTimer tm(c, KATGPU_K_PROFILE, n_out);
+        const uint64_t n_tiles = (n + RS_TILE_STRIDE - 1) / RS_TILE_STRIDE;
+        const dim3 g((unsigned)std::min<uint64_t>(n_tiles, (uint64_t)c->n_cu * 8)), b(COUNT_BLOCK);
+#define RS_SHORT(A, W) hipLaunchKernelGGL((k_rstats_short<A, W>), g, b, 0, c->stream, d, t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_tiles, dev_start, dev_len, (uint64_t)n_rec, g_stats_short, o)
+        if (wide && aligned) RS_SHORT(true, true); else if (wide) RS_SHORT(false, true); else if (aligned) RS_SHORT(true, false); else RS_SHORT(false, false);
+#undef RS_SHORT
+        HIPCHK(c, hipGetLastError());
+    }
+    if (!n_long || !long_windows) return KATGPU_OK;
+    // the long records' workspace: selection state | digit histograms | slot of every record | a count per window of a long record
+    const size_t hist_off = align_up(n_long * sizeof(RsSel), 16), slot_off = hist_off + n_long * RS_DIGITS * sizeof(uint64_t);
+    const size_t cnt_off = align_up(slot_off + n_rec * sizeof(uint32_t), 16), bytes = cnt_off + long_windows * sizeof(uint64_t);
+    uint8_t* w = nullptr;
+    if (pool_alloc(c, (void**)&w, bytes) != hipSuccess)
+        return fail(c, KATGPU_ERR_NOMEM, "record statistics: no %zu bytes of device memory for the counts of %llu long records (%llu windows)", bytes,
+                    (unsigned long long)n_long, (unsigned long long)long_windows);
+    *ws = w;
+    RsSel* sel = (RsSel*)w;
+    unsigned long long* hist = (unsigned long long*)(w + hist_off);
+    uint32_t* rec_slot = (uint32_t*)(w + slot_off);
+    uint64_t* cnt = (uint64_t*)(w + cnt_off);
+    ScopedTimer tm(c, KATGPU_K_PROFILE, 0);
+    HIPCHK(c, hipMemsetAsync(w, 0, slot_off, c->stream));
+    HIPCHK(c, hipMemsetAsync(rec_slot, 0xFF, n_rec * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_rstats_classify, dim3(1), dim3(RS_CLASSIFY_BLOCK), 0, c->stream, dev_len, (uint64_t)n_rec, k, g_stats_short, n_long, long_windows, rec_slot, sel);
+    {
+        const uint64_t per_chunk = wide ? WIDE_CHUNK_STARTS : CHUNK_STARTS;
+        const uint64_t n_chunks = (n + per_chunk - 1) / per_chunk;
+        const dim3 g((unsigned)std::min<uint64_t>(n_chunks, (uint64_t)c->n_cu * 8)), b(COUNT_BLOCK);
+#define RS_LONG(A, W) hipLaunchKernelGGL((k_rstats_long<A, W>), g, b, 0, c->stream, d, t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, rec_slot, cnt, long_windows, sel, o)
+        if (wide && aligned) RS_LONG(true, true); else if (wide) RS_LONG(false, true); else if (aligned) RS_LONG(true, false); else RS_LONG(false, false);
+#undef RS_LONG
+    }
+    const uint64_t sel_chunks = (long_windows + RS_SEL_CHUNK - 1) / RS_SEL_CHUNK;
+    const dim3 hg((unsigned)std::min<uint64_t>(sel_chunks, (uint64_t)c->n_cu * 8)), pg((unsigned)((n_long + 3) / 4));
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(k_rstats_hist, hg, dim3(256), 0, c->stream, cnt, long_windows, sel_chunks, k, dev_len, sel, n_long, (uint32_t)shift, hist);
+        hipLaunchKernelGGL(k_rstats_pick, pg, dim3(256), 0, c->stream, sel, n_long, (uint32_t)shift, hist, o);
+    }
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+// Device form.  The number of long records and of their windows comes back from the device first (two words; refresh_counters has synchronised already);
+// with none, the rest is asynchronous on the stream, otherwise the call returns when the selection's workspace has been released.
+extern "C" int katgpu_table_record_stats_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                                const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, katgpu_record_stats* dev_out) {
+    if (!t || (n_rec && (!dev_rec_start || !dev_rec_len || !dev_out)) || (n && !dev_bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!n_rec) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    unsigned long long* scratch = (unsigned long long*)&t->dev().ctrs[CTR_SCRATCH];
+    unsigned long long n_long[2] = {0, 0};
+    HIPCHK(c, hipMemsetAsync(scratch, 0, sizeof n_long, c->stream));
+    hipLaunchKernelGGL(k_rstats_count_long, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, c->stream, dev_rec_len, (uint64_t)n_rec, t->dev().k, g_stats_short, scratch);
+    HIPCHK(c, hipMemcpyAsync(n_long, scratch, sizeof n_long, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    void* ws = nullptr;
+    rc = launch_record_stats(t, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, canonicalise, dev_out, n_long[0], n_long[1], &ws);
+    if (ws) {
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        pool_release(c, ws);
+        if (!rc && e != hipSuccess) rc = fail(c, KATGPU_ERR_DEVICE, "record stats: %s", hipGetErrorString(e));
+    }
+    return rc;
+}
+
+// Host form: the records go through the device in batches of at most g_stats_batch bases and STATS_RECS records (a record longer than
+// that is a batch of its own), so any input fits next to the table; a batch also ends where its long records would have more than
+// g_stats_batch / 4 windows between them (a single record may), which bounds their count scratch by the longest record or 8 bytes x that.
+// What comes back is sizeof(katgpu_record_stats) per record.
+extern "C" int katgpu_table_record_stats_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                                              size_t n_rec, int canonicalise, katgpu_record_stats* out) {
+    if (!t || (n_rec && (!rec_start || !rec_len || !out)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!n_rec) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    for (size_t r = 0; r < n_rec; ++r) {
+        if (rec_start[r] > n || rec_len[r] > n - rec_start[r]) return fail(c, KATGPU_ERR_INVALID_ARG, "record %zu lies beyond the %zu bases", r, n);
+        if (r && rec_start[r] < rec_start[r - 1] + rec_len[r - 1]) return fail(c, KATGPU_ERR_INVALID_ARG, "record %zu starts before record %zu ends: records must be in order and disjoint", r, r - 1);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    const uint32_t k = t->dev().k;
+    const size_t STATS_RECS = (size_t)1 << 20;
+    const size_t rec_words = 2 + RS_FIELDS;                        // start, length, the six result words
+    uint8_t* db = nullptr; uint64_t* dr = nullptr;
+    size_t db_bytes = 0;
+    if (pool_alloc(c, (void**)&dr, std::min(n_rec, STATS_RECS) * rec_words * sizeof(uint64_t)) != hipSuccess)
+        return fail(c, KATGPU_ERR_NOMEM, "record statistics: no device memory for the records of a batch");
+    const size_t cap = std::min(n_rec, STATS_RECS);
+    std::vector<uint64_t> st(cap), ln(cap);
+    hipError_t e = hipSuccess;
+    for (size_t r0 = 0; r0 < n_rec && !rc && e == hipSuccess;) {
+        const uint64_t base = rec_start[r0];
+        auto long_windows_of = [&](size_t r) { const uint64_t w = rec_len[r] >= k ? rec_len[r] - k + 1 : 0; return w > g_stats_short ? w : (uint64_t)0; };
+        uint64_t n_long = 0, long_windows = 0;
+        size_t r1 = r0;
+        do {
+            const uint64_t w = long_windows_of(r1);
+            n_long += w != 0; long_windows += w;
+            ++r1;
+        } while (r1 < n_rec && r1 - r0 < STATS_RECS && rec_start[r1] + rec_len[r1] - base <= g_stats_batch &&
+                 long_windows + long_windows_of(r1) <= std::max<uint64_t>(g_stats_batch / 4, 1));
+        const size_t nb = rec_start[r1 - 1] + rec_len[r1 - 1] - base;
+        if (nb + 64 > db_bytes) {
+            pool_release(c, db); db = nullptr;
+            db_bytes = std::max(nb + 64, std::min(g_stats_batch, n) + 64);
+            if (pool_alloc(c, (void**)&db, db_bytes) != hipSuccess) { db_bytes = 0; rc = fail(c, KATGPU_ERR_NOMEM, "record statistics: no %zu bytes of device memory for a batch of bases", nb + 64); break; }
+        }
+        for (size_t r = r0; r < r1; ++r) { st[r - r0] = rec_start[r] - base; ln[r - r0] = rec_len[r]; }
+        const size_t m = r1 - r0;
+        katgpu_record_stats* d_out = (katgpu_record_stats*)(dr + 2 * cap);
+        if (nb) e = hipMemcpyAsync(db, bases + base, nb, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dr, st.data(), m * 8, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dr + cap, ln.data(), m * 8, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) break;
+        void* ws = nullptr;
+        rc = launch_record_stats(t, db, nb, dr, dr + cap, m, canonicalise, d_out, n_long, long_windows, &ws);
+        if (!rc) e = hipMemcpyAsync(out + r0, d_out, m * sizeof(katgpu_record_stats), hipMemcpyDeviceToHost, c->stream);
+        const hipError_t es = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = es;
+        pool_release(c, ws);
+        r0 = r1;
+    }
+    hipStreamSynchronize(c->stream);
+    pool_release(c, db); pool_release(c, dr);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "record stats: %s", hipGetErrorString(e));
     return KATGPU_OK;
 }
