@@ -238,6 +238,15 @@ int katgpu_jf_write_records_wide(const char* path, uint32_t k, int canonical, co
                                  const uint64_t* counts, size_t n);
 int katgpu_jf_read_records_wide(const char* path, uint32_t* k, int* canonical, uint64_t** keys_hi, uint64_t** keys_lo, uint64_t** counts, size_t* n);
 const char* katgpu_jf_last_error(void);
+/* Records of a k <= 32 table whose position (M * kmer) & (2^r - 1) lies in [pos_lo, pos_hi), in .jf file order
+   ((pos, kmer) ascending), packed as binary_writer writes them (ceil(2k/8) key bytes + 4 count bytes, count saturated),
+   into device memory.  cols: the 2k columns of M as katgpu_jf_write_records stores them in "matrix1" (host pointer).
+   dev_out == NULL or cap_records == 0: only *n_out (how many records the range holds) is set.
+   Needs 1 <= r <= min(2k, 63) and pos_lo <= pos_hi <= 2^r, else KATGPU_ERR_INVALID_ARG; k > 32: KATGPU_ERR_K.
+   A buffer too small for the range is KATGPU_ERR_INVALID_ARG, with *n_out set; so is a matrix that sends more than 2^16 records
+   of the range to one stretch of positions (M is expected to spread the table, as a header's matrix does).  katgpu_jf_dump is built on this. */
+int katgpu_table_jf_records_device(katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t pos_lo, uint64_t pos_hi,
+                                   uint8_t* dev_out, size_t cap_records, size_t* n_out);
 
 /* ---- reducers ---------------------------------------------------------------------------------------- */
 

@@ -40,7 +40,7 @@ EXPORTS = (
     "katgpu_comm_transport_note", "katgpu_comm_distinct_devices", "katgpu_comm_barrier", "katgpu_exchange_merge", "katgpu_allreduce_u64", "katgpu_comm_stats",
     "katgpu_table_packed_records", "katgpu_table_extract_packed", "katgpu_table_merge_regions_packed", "katgpu_comm_wire", "katgpu_exchange_begin", "katgpu_exchange_finish",
     "katgpu_table_filter", "katgpu_table_seq_hits_host", "katgpu_table_seq_hits_device",
-    "katgpu_table_record_stats_host", "katgpu_table_record_stats_device",
+    "katgpu_table_record_stats_host", "katgpu_table_record_stats_device", "katgpu_table_jf_records_device",
 )
 
 # katgpu_record_stats: one record of Table.record_stats
@@ -165,6 +165,7 @@ def load_library():
     L.katgpu_jf_write_records_wide.argtypes = [C.c_char_p, u32, C.c_int, vp, vp, vp, sz]
     L.katgpu_jf_read_records_wide.argtypes = [C.c_char_p, C.POINTER(u32), C.POINTER(C.c_int), pp, pp, pp, C.POINTER(sz)]
     L.katgpu_jf_last_error.restype = C.c_char_p
+    L.katgpu_table_jf_records_device.argtypes = [vp, u32, vp, u64, u64, vp, sz, C.POINTER(sz)]
     _lib = L
     return L
 
@@ -637,6 +638,27 @@ class Table:
         rc = self.engine.L.katgpu_jf_dump(self.h, os.fsencode(path))
         if rc:
             raise KatGpuError(rc, self.engine.L.katgpu_jf_last_error().decode(errors="replace") or self.engine.L.katgpu_last_error(self.engine.h).decode(errors="replace"))
+
+    def jf_records(self, r, cols, pos_lo=0, pos_hi=None, count_only=False):
+        """The packed .jf records whose position under the matrix `cols` (2k columns of r bits, a header's "matrix1") lies in
+        [pos_lo, pos_hi), in file order (katgpu_table_jf_records_device): a uint8 array of n * (ceil(2k/8) + 4) bytes, or n alone."""
+        cc = np.ascontiguousarray(cols, np.uint64)
+        assert cc.size == 2 * self.k
+        hi = (1 << r) if pos_hi is None else pos_hi
+        n = C.c_size_t()
+        L = self.engine.L
+        self.engine._chk(L.katgpu_table_jf_records_device(self.h, r, cc.ctypes.data, pos_lo, hi, None, 0, C.byref(n)))
+        if count_only:
+            return n.value
+        rb = (2 * self.k + 7) // 8 + 4
+        if not n.value:
+            return np.zeros(0, np.uint8)
+        buf = self.engine.alloc(n.value * rb)
+        try:
+            self.engine._chk(L.katgpu_table_jf_records_device(self.h, r, cc.ctypes.data, pos_lo, hi, buf.ptr, n.value, C.byref(n)))
+            return buf.download(np.uint8, n.value * rb)
+        finally:
+            buf.free()
 
     # ---- reducers ----
     def hist(self, low=1, high=10000, inc=1):

@@ -1,4 +1,5 @@
-// kg_jf.cpp -- Jellyfish "binary/sorted" hash files (.jf): reader and writer.  Pure host code.
+// kg_jf.cpp -- Jellyfish "binary/sorted" hash files (.jf): reader and writer.  Pure host code; the records of a k <= 32 table's dump
+// are ordered and packed on the device (kg_jf_records.hpp, jf_stream_records in kg_table.hip).
 //
 // Replaces JellyfishHelper::dumpHash / HashLoader::loadHash (lib/src/jellyfish_helper.cc:248-256,97-187) and the parts
 // of Jellyfish they stand on: generic_file_header::write/read (JF/include/jellyfish/generic_file_header.hpp:96-153),
@@ -13,6 +14,7 @@
 // (bit i of the k-mer selects column key_len-1-i: rectangular_binary_matrix.hpp:206-240).  Checked against the
 // reference's own fixture tests/data/ecoli.header.jf27 (tests/test_jf.py).
 #include "../../include/katgpu.h"
+#include "kg_jf.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -128,23 +130,21 @@ struct Rec { uint64_t pos; u128 key; uint64_t count; };
 
 extern "C" const char* katgpu_jf_last_error(void) { return g_jf_err.c_str(); }
 
-// keys_hi == nullptr: one-word k-mers
-static int write_records(const char* path, uint32_t k, int canonical, const uint64_t* keys_hi, const uint64_t* keys, const uint64_t* counts, size_t n) {
-    const unsigned key_len = 2 * k, key_bytes = (key_len + 7) / 8, counter_len = 4;
-    // size: the power of two Jellyfish would have needed for n entries (HashLoader sizes 2n rounded up, jellyfish_helper.cc:144-145)
+// What a file of n records says about itself: size = 2^r, the power of two Jellyfish would have needed for n entries (HashLoader sizes
+// 2n rounded up, jellyfish_helper.cc:144-145), and the matrix seeded from k and n.
+struct JfGeometry { unsigned r; uint64_t size; std::vector<uint64_t> cols; };
+static JfGeometry jf_geometry(uint32_t k, size_t n) {
+    const unsigned key_len = 2 * k;
     unsigned r = 1;
     while (((uint64_t)1 << r) < std::max<uint64_t>(2 * (uint64_t)n, 2)) ++r;
     if (r > key_len) r = key_len;
-    const uint64_t size = (uint64_t)1 << r;
-    const std::vector<uint64_t> cols = random_matrix(r, key_len, 0x6B61746770750000ULL ^ ((uint64_t)k << 8) ^ (uint64_t)n);
-    std::vector<Rec> recs(n);
-    for (size_t i = 0; i < n; ++i) {
-        const u128 key = ((u128)(keys_hi ? keys_hi[i] : 0) << 64) | keys[i];
-        recs[i] = {matrix_times(cols, key) & (size - 1), key, counts[i]};
-    }
-    std::sort(recs.begin(), recs.end(), [](const Rec& a, const Rec& b) { return a.pos != b.pos ? a.pos < b.pos : a.key < b.key; });
+    return {r, (uint64_t)1 << r, random_matrix(r, key_len, 0x6B61746770750000ULL ^ ((uint64_t)k << 8) ^ (uint64_t)n)};
+}
 
-    // ---- header (alphabetical keys, terse, like jsoncpp's FastWriter) ----
+// the 9 digits, the JSON (alphabetical keys, terse, like jsoncpp's FastWriter) and its zero padding
+static bool write_header(FILE* f, uint32_t k, int canonical, const JfGeometry& g) {
+    const unsigned key_len = 2 * k, counter_len = 4;
+    const std::vector<uint64_t>& cols = g.cols;
     char host[256] = "localhost", cwd[4096] = ".", when[64] = "";
     gethostname(host, sizeof host - 1);
     if (!getcwd(cwd, sizeof cwd)) strcpy(cwd, ".");
@@ -156,18 +156,32 @@ static int write_records(const char* path, uint32_t k, int canonical, const uint
     js += ",\"exe_path\":\"katgpu\",\"format\":\"binary/sorted\",\"hostname\":" + json_quote(host);
     js += ",\"key_len\":" + std::to_string(key_len) + ",\"matrix1\":{\"c\":" + std::to_string(key_len) + ",\"columns\":[";
     for (unsigned i = 0; i < key_len; ++i) { if (i) js += ','; js += std::to_string(cols[i]); }
-    js += "],\"r\":" + std::to_string(r) + "},\"max_reprobe\":126,\"pwd\":" + json_quote(cwd) + ",\"reprobes\":[1";
+    js += "],\"r\":" + std::to_string(g.r) + "},\"max_reprobe\":126,\"pwd\":" + json_quote(cwd) + ",\"reprobes\":[1";
     for (unsigned i = 1; i <= 126; ++i) js += "," + std::to_string((uint64_t)i * (i + 1) / 2);      // JF/lib/storage.cc:20-50
-    js += "],\"size\":" + std::to_string(size) + ",\"time\":\"" + when + "\",\"val_len\":7}";
+    js += "],\"size\":" + std::to_string(g.size) + ",\"time\":\"" + when + "\",\"val_len\":7}";
     size_t hlen = js.size();
     const size_t rem = (9 + js.size()) % 8;
     if (rem) hlen += 8 - rem;
+    js.resize(hlen, '\0');
+    return fprintf(f, "%09zu", hlen) == 9 && fwrite(js.data(), 1, js.size(), f) == js.size();
+}
+
+// keys_hi == nullptr: one-word k-mers
+static int write_records(const char* path, uint32_t k, int canonical, const uint64_t* keys_hi, const uint64_t* keys, const uint64_t* counts, size_t n) {
+    const unsigned key_len = 2 * k, key_bytes = (key_len + 7) / 8, counter_len = 4;
+    const JfGeometry g = jf_geometry(k, n);
+    const std::vector<uint64_t>& cols = g.cols;
+    const uint64_t size = g.size;
+    std::vector<Rec> recs(n);
+    for (size_t i = 0; i < n; ++i) {
+        const u128 key = ((u128)(keys_hi ? keys_hi[i] : 0) << 64) | keys[i];
+        recs[i] = {matrix_times(cols, key) & (size - 1), key, counts[i]};
+    }
+    std::sort(recs.begin(), recs.end(), [](const Rec& a, const Rec& b) { return a.pos != b.pos ? a.pos < b.pos : a.key < b.key; });
 
     FILE* f = fopen(path, "wb");
     if (!f) { g_jf_err = std::string("cannot open ") + path + " for writing"; return KATGPU_ERR_IO; }
-    fprintf(f, "%09zu", hlen);
-    fwrite(js.data(), 1, js.size(), f);
-    for (size_t i = js.size(); i < hlen; ++i) fputc('\0', f);
+    write_header(f, k, canonical, g);
     std::vector<uint8_t> buf;
     buf.reserve((size_t)(key_bytes + counter_len) * std::min<size_t>(n, 1 << 20));
     for (size_t i = 0; i < n; ++i) {
@@ -307,6 +321,29 @@ extern "C" int katgpu_jf_dump(katgpu_table* t, const char* path) {
     }
     int rc = katgpu_table_export(t, nullptr, nullptr, 0, &n);
     if (rc) return rc;
+    {   // the records come off the device in file order, range of positions by range; the host holds two pinned buffers of them
+        const uint32_t k = katgpu_table_k(t);
+        const JfGeometry g = jf_geometry(k, n);
+        timespec t0, t1;
+        clock_gettime(CLOCK_MONOTONIC, &t0);
+        FILE* f = fopen(path, "wb");
+        if (!f) { g_jf_err = std::string("cannot open ") + path + " for writing"; return KATGPU_ERR_IO; }
+        JfDumpTiming tm;
+        bool ok = write_header(f, k, katgpu_table_canonical(t), g);
+        rc = ok ? jf_stream_records(t, g.r, g.cols.data(), f, &tm) : KATGPU_ERR_IO;
+        ok = fclose(f) == 0;
+        if (rc == KATGPU_OK && !ok) rc = KATGPU_ERR_IO;
+        if (rc == KATGPU_ERR_IO) g_jf_err = std::string("write error on ") + path;
+        else g_jf_err.clear();
+        clock_gettime(CLOCK_MONOTONIC, &t1);
+        if (rc != KG_JF_NO_SCRATCH) {
+            if (rc == KATGPU_OK && getenv("KATGPU_TIMING"))
+                fprintf(stderr, "katgpu_timing {\"phase\": \"jf_dump\", \"records\": %zu, \"ranges\": %u, \"device_s\": %.3f, \"copy_s\": %.3f, \"write_s\": %.3f, \"total_s\": %.3f}\n",
+                        n, tm.ranges, tm.device_s, tm.copy_s, tm.write_s, (double)(t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) * 1e-9);
+            return rc;
+        }
+    }
+    // no device scratch to be had: the records to the host, ordered and packed there
     std::vector<uint64_t> keys(std::max<size_t>(n, 1)), counts(std::max<size_t>(n, 1));
     if (n) { rc = katgpu_table_export(t, keys.data(), counts.data(), n, &n); if (rc) return rc; }
     return katgpu_jf_write_records(path, katgpu_table_k(t), katgpu_table_canonical(t), keys.data(), counts.data(), n);

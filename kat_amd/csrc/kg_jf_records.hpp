@@ -1,0 +1,184 @@
+// kg_jf_records.hpp -- the records of a Jellyfish "binary/sorted" hash file, ordered and packed on the device (k <= 32).
+//
+// Replaces, for one-word tables, the order sorted_dumper emits (JF/include/jellyfish/sorted_dumper.hpp:80-112) and the bytes
+// binary_writer writes per record (binary_dumper.hpp:47-51): records ascending by ((M * kmer) & (size - 1), kmer), each
+// ceil(2k/8) key bytes + 4 count bytes, little endian, the count saturated.  kg_jf.cpp describes the file around them.
+//
+//  J1 k_jf_select     slot walk: rebuild the key, position = parity(key & row) per matrix row, keep [pos_lo, pos_hi);
+//                     <2> counts the range, <0> histograms it over buckets of 2^shift positions, <1> scatters (pos, key, count)
+//                     records to their bucket's stretch of the scratch segment
+//  J2 k_jf_scan       exclusive scan of the bucket histogram (one workgroup), the total and the largest bucket
+//  J3 k_jf_rank       buckets beyond one LDS tile only: a record's rank among its bucket, by comparison with all of it (global memory)
+//  J4 k_jf_sort_pack  one workgroup per bucket: bitonic sort of the bucket on (pos, key) in LDS (or, for a ranked bucket, a gather
+//                     by rank, tile after tile), then the tile's bytes assembled in LDS and stored as whole dwords
+//
+// Positions of distinct keys under a random matrix are close to uniform, so the host picks `shift` for a mean of at most
+// JF_BUCKET_MEAN records per bucket: a bucket beyond JF_TILE is then some 16 standard deviations out, and only a matrix that
+// maps many keys to few positions sends work through J3.  Integer and byte work bound by the table walk; no MFMA.
+#pragma once
+#include "kg_device.hpp"
+
+namespace kg {
+
+constexpr int JF_BLOCK = 256;
+constexpr uint32_t JF_TILE = 512;            // records sorted and packed per workgroup pass: 10 KB of records + 6 KB of bytes in LDS
+constexpr uint32_t JF_BUCKET_MEAN = 256;     // the host sizes buckets for at most this many expected records
+constexpr uint32_t JF_RANK_MAX = 1u << 16;      // the largest bucket the ranking path takes: 2^32 comparisons, a fraction of a second
+constexpr uint32_t JF_MAX_REC_BYTES = 12;    // k = 32: 8 key bytes + 4 count bytes
+constexpr int JF_SCAN_BLOCK = 1024;
+
+// the r rows of M over the 2k key bits (row j, bit i = column 2k-1-i, bit j).  Passed by value: the rows sit in the kernel
+// argument segment and a wave reads them with scalar loads.
+struct JfRows { uint64_t row[63]; };
+
+__device__ __forceinline__ uint64_t jf_pos(const JfRows& m, uint32_t r, uint64_t key) {
+    uint64_t pos = 0;
+    for (uint32_t j = 0; j < r; ++j) pos |= (uint64_t)(__popcll(key & m.row[j]) & 1) << j;
+    return pos;
+}
+
+__device__ __forceinline__ bool jf_less(uint64_t pa, uint64_t ka, uint64_t pb, uint64_t kb) { return pa != pb ? pa < pb : ka < kb; }
+
+// J1.  MODE 2: *total += records of the range.  MODE 0: ++hist[bucket].  MODE 1: record -> scratch[cursor[bucket]++].
+template <int MODE>
+__global__ void __launch_bounds__(JF_BLOCK)
+k_jf_select(DevTable t, uint32_t n_ovf, JfRows m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift,
+            uint32_t* __restrict__ hist_or_cursor, unsigned long long* __restrict__ total,
+            uint64_t* __restrict__ out_pos, uint64_t* __restrict__ out_key, uint32_t* __restrict__ out_cnt) {
+    uint64_t mine = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= t.cap; i += stride) {
+        uint64_t key = EMPTY, in_slot = 0;
+        if (i < t.cap) { const SlotView v = slot_view(t, i); if (!v.occ) continue; key = v.key; in_slot = v.cnt; }
+        else if (!t.ctrs[CTR_ONES]) continue;                                  // the all-ones k-mer lives beside the slots
+        const uint64_t pos = jf_pos(m, r, key);
+        if (pos < pos_lo || pos >= pos_hi) continue;
+        if (MODE == 2) { ++mine; continue; }
+        const uint64_t b = (pos - pos_lo) >> shift;
+        const uint32_t at = atomicAdd(&hist_or_cursor[b], 1u);
+        if (MODE == 1) {
+            const uint64_t c = i < t.cap ? slot_total(t, i, key, in_slot, n_ovf) : t.ctrs[CTR_ONES];
+            out_pos[at] = pos; out_key[at] = key;
+            out_cnt[at] = c > 0xFFFFFFFFULL ? 0xFFFFFFFFu : (uint32_t)c;       // binary_writer::write saturates
+        }
+    }
+    if (MODE == 2) {
+        for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(total, (unsigned long long)mine);
+    }
+}
+
+// J2.  off[i] = cursor[i] = sum of hist[0..i), off[nb] = the total; res[0] = total (64 bits), res[1] = largest bucket.
+static __global__ void __launch_bounds__(JF_SCAN_BLOCK)
+k_jf_scan(const uint32_t* __restrict__ hist, uint32_t nb, uint32_t* __restrict__ off, uint32_t* __restrict__ cursor, unsigned long long* __restrict__ res) {
+    __shared__ uint32_t s_wave[JF_SCAN_BLOCK / 64];
+    __shared__ uint32_t s_max;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) s_max = 0;
+    uint64_t carry = 0;
+    uint32_t mx = 0;
+    for (uint32_t base = 0; base < nb; base += JF_SCAN_BLOCK) {
+        const uint32_t i = base + tid;
+        const uint32_t v = i < nb ? hist[i] : 0;
+        mx = v > mx ? v : mx;
+        uint32_t x = v;
+        for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x, d, 64); if ((int)lane >= d) x += y; }
+        if (lane == 63) s_wave[wave] = x;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t w = 0; w < JF_SCAN_BLOCK / 64; ++w) { const uint32_t s = s_wave[w]; all += s; if (w < wave) before += s; }
+        if (i < nb) { const uint32_t e = (uint32_t)carry + before + x - v; off[i] = e; cursor[i] = e; }
+        carry += all;
+        __syncthreads();
+    }
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t y = __shfl_down(mx, o, 64); mx = y > mx ? y : mx; }
+    if (lane == 0) atomicMax(&s_max, mx);
+    __syncthreads();
+    if (tid == 0) { off[nb] = (uint32_t)carry; res[0] = carry; res[1] = s_max; }
+}
+
+// J3.  rank[i] = how many records of i's bucket sort before record i, for the buckets one LDS tile cannot hold.  Quadratic in the
+// bucket: the host refuses a range whose largest bucket exceeds JF_RANK_MAX before it launches this.
+static __global__ void __launch_bounds__(JF_BLOCK)
+k_jf_rank(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ key, uint32_t n, uint64_t pos_lo, uint32_t shift,
+          const uint32_t* __restrict__ off, uint32_t* __restrict__ rank) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t p = pos[i], kk = key[i];
+        const uint64_t b = (p - pos_lo) >> shift;
+        const uint32_t lo = off[b], hi = off[b + 1];
+        if (hi - lo <= JF_TILE) continue;
+        uint32_t before = 0;
+        for (uint32_t j = lo; j < hi; ++j) before += jf_less(pos[j], key[j], p, kk) ? 1u : 0u;
+        rank[i] = before;
+    }
+}
+
+// J4.  Bucket b holds the records [off[b], off[b+1]) of the scratch segment and of the output.  The packed bytes of a tile start at
+// any byte address, so the tile is laid out in LDS with the same misalignment as its place in `out`: every dword of the image that
+// lies wholly inside the tile goes out as one dword store (a wave's stores are 256 contiguous bytes), and the at most two dwords a
+// tile shares with its neighbours go out byte by byte.
+static __global__ void __launch_bounds__(JF_BLOCK)
+k_jf_sort_pack(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ key, const uint32_t* __restrict__ cnt,
+               const uint32_t* __restrict__ off, const uint32_t* __restrict__ rank, uint32_t nb, uint32_t key_bytes, uint8_t* __restrict__ out) {
+    __shared__ uint64_t s_pos[JF_TILE];
+    __shared__ uint64_t s_key[JF_TILE];
+    __shared__ uint32_t s_cnt[JF_TILE];
+    __shared__ uint32_t s_img[JF_TILE * JF_MAX_REC_BYTES / 4 + 2];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t rb = key_bytes + 4;
+    for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
+        const uint32_t lo = off[b], m = off[b + 1] - lo;
+        for (uint32_t t0 = 0; t0 < m; t0 += JF_TILE) {
+            const uint32_t n_tile = m - t0 < JF_TILE ? m - t0 : JF_TILE;
+            if (m <= JF_TILE) {
+                uint32_t p2 = 1;
+                while (p2 < m) p2 <<= 1;
+                for (uint32_t i = tid; i < p2; i += JF_BLOCK) {
+                    const bool real = i < m;                                  // padding sorts last: a position is below 2^63
+                    s_pos[i] = real ? pos[lo + i] : ~0ULL; s_key[i] = real ? key[lo + i] : ~0ULL; s_cnt[i] = real ? cnt[lo + i] : 0;
+                }
+                __syncthreads();
+                for (uint32_t k2 = 2; k2 <= p2; k2 <<= 1)
+                    for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
+                        for (uint32_t t = tid; t < p2 / 2; t += JF_BLOCK) {
+                            const uint32_t i = 2 * t - (t & (j - 1)), l = i + j;
+                            const bool up = (i & k2) == 0;
+                            const uint64_t pa = s_pos[i], ka = s_key[i], pb = s_pos[l], kb = s_key[l];
+                            if (jf_less(pb, kb, pa, ka) == up) {
+                                s_pos[i] = pb; s_key[i] = kb; s_pos[l] = pa; s_key[l] = ka;
+                                const uint32_t ca = s_cnt[i]; s_cnt[i] = s_cnt[l]; s_cnt[l] = ca;
+                            }
+                        }
+                        __syncthreads();
+                    }
+            } else {
+                for (uint32_t i = tid; i < m; i += JF_BLOCK) {
+                    const uint32_t at = rank[lo + i] - t0;                   // (wraps below t0: not this tile's)
+                    if (at < n_tile) { s_key[at] = key[lo + i]; s_cnt[at] = cnt[lo + i]; }
+                }
+                __syncthreads();
+            }
+            uint8_t* dst = out + (uint64_t)(lo + t0) * rb;
+            const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3);
+            uint8_t* img = reinterpret_cast<uint8_t*>(s_img);
+            for (uint32_t i = tid; i < n_tile; i += JF_BLOCK) {
+                uint8_t* p = img + mis + i * rb;
+                const uint64_t kk = s_key[i];
+                const uint32_t c = s_cnt[i];
+                for (uint32_t x = 0; x < key_bytes; ++x) p[x] = (uint8_t)(kk >> (8 * x));
+                for (uint32_t x = 0; x < 4; ++x) p[key_bytes + x] = (uint8_t)(c >> (8 * x));
+            }
+            __syncthreads();
+            const uint32_t end = mis + n_tile * rb;                           // the image is bytes [mis, end) of s_img
+            uint32_t* dst32 = reinterpret_cast<uint32_t*>(dst - mis);
+            for (uint32_t d = tid; d < (end + 3) / 4; d += JF_BLOCK) {
+                if (4 * d >= mis && 4 * d + 4 <= end) dst32[d] = s_img[d];
+                else for (uint32_t x = 4 * d; x < 4 * d + 4; ++x) if (x >= mis && x < end) dst[x - mis] = img[x];
+            }
+            __syncthreads();
+        }
+    }
+}
+
+}  // namespace kg
