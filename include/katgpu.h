@@ -247,6 +247,15 @@ const char* katgpu_jf_last_error(void);
    of the range to one stretch of positions (M is expected to spread the table, as a header's matrix does).  katgpu_jf_dump is built on this. */
 int katgpu_table_jf_records_device(katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t pos_lo, uint64_t pos_hi,
                                    uint8_t* dev_out, size_t cap_records, size_t* n_out);
+/* n_records packed .jf records (ceil(key_len/8) key bytes + counter_len count bytes each, little endian) held in DEVICE memory at any
+ * byte alignment are added to t: hash->add(key, val) per record.  Exact 64-bit sums; a zero count adds nothing; key bits above key_len
+ * are ignored.  key_len != 2k of the table: KATGPU_ERR_MISMATCH; counter_len outside 1..8: KATGPU_ERR_INVALID_ARG.  The table grows
+ * as it does under katgpu_table_merge_device.  katgpu_jf_load is built on this. */
+int katgpu_table_add_jf_records_device(katgpu_table* t, const uint8_t* dev_records, size_t n_records,
+                                       uint32_t key_len, uint32_t counter_len);
+/* katgpu_jf_load for records [n*part/n_parts, n*(part+1)/n_parts) of the file only; the table is sized for all n, so that the parts'
+ * tables share one region grid.  part >= n_parts or n_parts == 0: KATGPU_ERR_INVALID_ARG. */
+int katgpu_jf_load_part(katgpu_ctx* ctx, const char* path, uint32_t part, uint32_t n_parts, katgpu_table** out);
 
 /* ---- reducers ---------------------------------------------------------------------------------------- */
 

@@ -41,6 +41,7 @@ EXPORTS = (
     "katgpu_table_packed_records", "katgpu_table_extract_packed", "katgpu_table_merge_regions_packed", "katgpu_comm_wire", "katgpu_exchange_begin", "katgpu_exchange_finish",
     "katgpu_table_filter", "katgpu_table_seq_hits_host", "katgpu_table_seq_hits_device",
     "katgpu_table_record_stats_host", "katgpu_table_record_stats_device", "katgpu_table_jf_records_device",
+    "katgpu_table_add_jf_records_device", "katgpu_jf_load_part",
 )
 
 # katgpu_record_stats: one record of Table.record_stats
@@ -166,6 +167,8 @@ def load_library():
     L.katgpu_jf_read_records_wide.argtypes = [C.c_char_p, C.POINTER(u32), C.POINTER(C.c_int), pp, pp, pp, C.POINTER(sz)]
     L.katgpu_jf_last_error.restype = C.c_char_p
     L.katgpu_table_jf_records_device.argtypes = [vp, u32, vp, u64, u64, vp, sz, C.POINTER(sz)]
+    L.katgpu_table_add_jf_records_device.argtypes = [vp, vp, sz, u32, u32]
+    L.katgpu_jf_load_part.argtypes = [vp, C.c_char_p, u32, u32, pp]
     _lib = L
     return L
 
@@ -420,6 +423,14 @@ class Engine:
             raise KatGpuError(rc, self.L.katgpu_jf_last_error().decode(errors="replace"))
         return Table(self, self.L.katgpu_table_k(h), bool(self.L.katgpu_table_canonical(h)), _handle=h.value)
 
+    def load_jf_part(self, path, part, n_parts):
+        """load_jf for the part-th of n_parts stretches of the file's records; the table is sized for the whole file."""
+        h = C.c_void_p()
+        rc = self.L.katgpu_jf_load_part(self.h, os.fsencode(path), part, n_parts, C.byref(h))
+        if rc:
+            raise KatGpuError(rc, self.L.katgpu_jf_last_error().decode(errors="replace"))
+        return Table(self, self.L.katgpu_table_k(h), bool(self.L.katgpu_table_canonical(h)), _handle=h.value)
+
     # ---- profiling ----
     def profile_reset(self):
         self._chk(self.L.katgpu_profile_reset(self.h))
@@ -657,6 +668,20 @@ class Table:
         try:
             self.engine._chk(L.katgpu_table_jf_records_device(self.h, r, cc.ctypes.data, pos_lo, hi, buf.ptr, n.value, C.byref(n)))
             return buf.download(np.uint8, n.value * rb)
+        finally:
+            buf.free()
+
+    def add_jf_records(self, raw, key_len, counter_len, offset=0):
+        """Packed .jf records (a uint8 array, ceil(key_len/8) + counter_len bytes each) added to the table on the device
+        (katgpu_table_add_jf_records_device).  offset: the records sit that many bytes into their device buffer."""
+        a = np.ascontiguousarray(raw, np.uint8).ravel()
+        rb = (key_len + 7) // 8 + counter_len
+        assert a.size % rb == 0
+        buf = self.engine.alloc(max(offset + a.size, 1))
+        try:
+            if a.size:
+                buf.upload(a, offset)
+            self.engine._chk(self.engine.L.katgpu_table_add_jf_records_device(self.h, buf.ptr + offset, a.size // rb, key_len, counter_len))
         finally:
             buf.free()
 

@@ -208,14 +208,14 @@ void InputHandler::loadHash() {                                             // l
     auto t0 = std::chrono::steady_clock::now();
     std::cout << "Loading hashes into memory...";
     std::cout.flush();
-    int rc = katgpu_jf_load(Engine::ctx(), input[0].c_str(), &hash);
+    // --gpus N: every rank reads its stretch of the file's records into a table sized for the whole file (one region grid for all),
+    // then the tables are made one by owner
+    int rc = Engine::dist() ? katgpu_jf_load_part(Engine::ctx(), input[0].c_str(), (uint32_t)Engine::rank(), (uint32_t)Engine::world(), &hash)
+                            : katgpu_jf_load(Engine::ctx(), input[0].c_str(), &hash);
     if (rc) throw JellyfishException(katgpu_jf_last_error());
     canonical = katgpu_table_canonical(hash) != 0;                          // hashLoader->getCanonical() / getMerLen()
     merLen = (uint16_t)katgpu_table_k(hash);
-    if (Engine::dist()) {                                                   // every rank has read the file: rank 0's copy is the run's, shared out by owner
-        if (!Engine::speaker()) Engine::check(katgpu_table_clear(hash));
-        Engine::exchange(hash);
-    }
+    if (Engine::dist()) Engine::exchange(hash);
     std::cout << " done.";
     double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     char buf[64]; snprintf(buf, sizeof buf, "  Time taken: %.1fs\n\n", s);

@@ -134,7 +134,7 @@ public:
     void validateInput();                        // throws if an input is missing; sets mode
     void count(uint16_t threads, const katgpu_table* like = nullptr, bool more_to_count = false);   // *** the drop-in boundary: katgpu_count ***
     void loadHeader() {}                         // the header travels with katgpu_jf_load (lib/src/input_handler.cc:139-143)
-    void loadHash();                             // lib/src/input_handler.cc:204-219 -> katgpu_jf_load
+    void loadHash();                             // lib/src/input_handler.cc:204-219 -> katgpu_jf_load (--gpus N: katgpu_jf_load_part)
     void validateMerLen(uint16_t merLen);        // lib/src/input_handler.cc:145-158
     void dump(const std::string& outputPath, uint16_t threads);   // lib/src/input_handler.cc:221-243 -> katgpu_jf_dump
     static std::shared_ptr<std::vector<std::string>> globFiles(const std::string& input);

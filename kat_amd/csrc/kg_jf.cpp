@@ -1,5 +1,6 @@
 // kg_jf.cpp -- Jellyfish "binary/sorted" hash files (.jf): reader and writer.  Pure host code; the records of a k <= 32 table's dump
-// are ordered and packed on the device (kg_jf_records.hpp, jf_stream_records in kg_table.hip).
+// are ordered and packed on the device (kg_jf_records.hpp, jf_stream_records in kg_table.hip), and the records of a file being loaded
+// are unpacked and added there (kg_jf_load.hpp, jf_stream_load in kg_table.hip).
 //
 // Replaces JellyfishHelper::dumpHash / HashLoader::loadHash (lib/src/jellyfish_helper.cc:248-256,97-187) and the parts
 // of Jellyfish they stand on: generic_file_header::write/read (JF/include/jellyfish/generic_file_header.hpp:96-153),
@@ -206,10 +207,11 @@ extern "C" int katgpu_jf_write_records_wide(const char* path, uint32_t k, int ca
     return write_records(path, k, canonical, keys_hi, keys_lo, counts, n);
 }
 
-// max_key_len: 64 for the one-word form (keys_hi == nullptr), 2 * KATGPU_MAX_K for the wide one
-static int read_records(const char* path, unsigned max_key_len, uint32_t* k, int* canonical, uint64_t** keys_hi, uint64_t** keys, uint64_t** counts, size_t* n) {
-    *keys = *counts = nullptr; *n = 0;
-    if (keys_hi) *keys_hi = nullptr;
+// What a file's header says, and where its records are.  max_key_len: 64 for the one-word form, 2 * KATGPU_MAX_K for the wide one.
+// KATGPU_OK: *fp is the open file; else it is closed and g_jf_err says why.
+struct JfHeader { uint32_t key_len = 0, counter_len = 0; bool canonical = false; size_t offset = 0, n = 0; };
+static int read_header(const char* path, unsigned max_key_len, FILE** fp, JfHeader* h) {
+    *fp = nullptr;
     FILE* f = fopen(path, "rb");
     if (!f) { g_jf_err = std::string("Could not find input file at: ") + path + "; please check the path and try again."; return KATGPU_ERR_IO; }
     char digits[10] = {0};
@@ -252,7 +254,21 @@ static int read_records(const char* path, unsigned max_key_len, uint32_t* k, int
         g_jf_err = "Size of database (" + std::to_string(data_bytes) + ") must be a multiple of the length of a record (" + std::to_string(rec) + ")";   // :162-167
         return KATGPU_ERR_FORMAT;
     }
-    const size_t nrec = data_bytes / rec;
+    h->key_len = (uint32_t)key_len; h->counter_len = (uint32_t)counter_len; h->canonical = json_bool(js, "canonical", false);
+    h->offset = offset; h->n = data_bytes / rec;
+    *fp = f;
+    return KATGPU_OK;
+}
+
+static int read_records(const char* path, unsigned max_key_len, uint32_t* k, int* canonical, uint64_t** keys_hi, uint64_t** keys, uint64_t** counts, size_t* n) {
+    *keys = *counts = nullptr; *n = 0;
+    if (keys_hi) *keys_hi = nullptr;
+    FILE* f = nullptr;
+    JfHeader h;
+    const int hrc = read_header(path, max_key_len, &f, &h);
+    if (hrc) return hrc;
+    const size_t key_len = h.key_len, counter_len = h.counter_len, key_bytes = (key_len + 7) / 8, rec = key_bytes + counter_len, offset = h.offset;
+    const size_t nrec = h.n;
     uint64_t* kk = (uint64_t*)malloc(std::max<size_t>(nrec, 1) * 8);
     uint64_t* cc = (uint64_t*)malloc(std::max<size_t>(nrec, 1) * 8);
     uint64_t* kh = keys_hi ? (uint64_t*)malloc(std::max<size_t>(nrec, 1) * 8) : nullptr;
@@ -275,7 +291,7 @@ static int read_records(const char* path, unsigned max_key_len, uint32_t* k, int
     }
     fclose(f);
     *k = (uint32_t)(key_len / 2);
-    if (canonical) *canonical = json_bool(js, "canonical", false) ? 1 : 0;
+    if (canonical) *canonical = h.canonical ? 1 : 0;
     *keys = kk; *counts = cc; *n = nrec;
     if (keys_hi) *keys_hi = kh;
     return KATGPU_OK;
@@ -293,21 +309,55 @@ extern "C" int katgpu_jf_read_records_wide(const char* path, uint32_t* k, int* c
 
 // ---- device-level wrappers: InputHandler::loadHash / dump ----
 
-extern "C" int katgpu_jf_load(katgpu_ctx* ctx, const char* path, katgpu_table** out) {
-    if (!ctx || !out) return KATGPU_ERR_INVALID_ARG;
-    *out = nullptr;
+// the load as it was before the records were streamed: the whole file decoded on the host, the part's records merged from there
+static int load_part_on_host(katgpu_ctx* ctx, katgpu_table* t, const char* path, uint32_t part, uint32_t n_parts) {
     uint32_t k = 0; int canonical = 0; uint64_t *keys_hi = nullptr, *keys = nullptr, *counts = nullptr; size_t n = 0;
     int rc = katgpu_jf_read_records_wide(path, &k, &canonical, &keys_hi, &keys, &counts, &n);
     if (rc) return rc;
-    katgpu_table* t = nullptr;
-    rc = katgpu_table_create(ctx, k, canonical, std::max<uint64_t>((uint64_t)(n / 0.6) + 1024, 1 << 16), 0, &t);
-    if (!rc) rc = k > 32 ? katgpu_table_merge_host_wide(t, keys_hi, keys, counts, n)
-                         : katgpu_table_merge_host(t, keys, counts, n);       // hash->add(reader.key(), reader.val()) per record (:172-174)
+    const size_t lo = (size_t)((u128)n * part / n_parts), m = (size_t)((u128)n * (part + 1) / n_parts) - lo;
+    rc = k > 32 ? katgpu_table_merge_host_wide(t, keys_hi + lo, keys + lo, counts + lo, m)
+                : katgpu_table_merge_host(t, keys + lo, counts + lo, m);
     free(keys_hi); free(keys); free(counts);
-    if (rc) { if (t) katgpu_table_free(t); g_jf_err = katgpu_last_error(ctx); return rc; }
+    if (rc) g_jf_err = katgpu_last_error(ctx);
+    return rc;
+}
+
+// Host: the two pinned buffers of jf_stream_load (a chunk of records each, 2^24 by default: 2 x 185 MB at k = 27); device: its two
+// buffers of the same size beside the table.  Neither grows with the file.
+extern "C" int katgpu_jf_load_part(katgpu_ctx* ctx, const char* path, uint32_t part, uint32_t n_parts, katgpu_table** out) {
+    if (!ctx || !out || !path || n_parts == 0 || part >= n_parts) return KATGPU_ERR_INVALID_ARG;
+    *out = nullptr;
+    timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    FILE* f = nullptr;
+    JfHeader h;
+    int rc = read_header(path, 2 * KATGPU_MAX_K, &f, &h);
+    if (rc) return rc;
+    const size_t n = h.n, rec = (h.key_len + 7) / 8 + h.counter_len;
+    const size_t lo = (size_t)((u128)n * part / n_parts), m = (size_t)((u128)n * (part + 1) / n_parts) - lo;
+    katgpu_table* t = nullptr;
+    rc = katgpu_table_create(ctx, h.key_len / 2, h.canonical ? 1 : 0, std::max<uint64_t>((uint64_t)(n / 0.6) + 1024, 1 << 16), 0, &t);
+    JfLoadTiming tm;
+    if (rc) g_jf_err = katgpu_last_error(ctx);
+    else if (fseek(f, (long)(h.offset + lo * rec), SEEK_SET) != 0) rc = KATGPU_ERR_IO;
+    else {
+        rc = jf_stream_load(t, f, m, h.key_len, h.counter_len, &tm);      // hash->add(reader.key(), reader.val()) per record (:172-174)
+        if (rc && rc != KATGPU_ERR_IO) g_jf_err = katgpu_last_error(ctx);
+    }
+    if (rc == KATGPU_ERR_IO) g_jf_err = std::string("read error on ") + path;
+    fclose(f);
+    const bool streamed = rc != KG_JF_NO_SCRATCH;
+    if (!streamed) rc = load_part_on_host(ctx, t, path, part, n_parts);
+    if (rc) { if (t) katgpu_table_free(t); return rc; }
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    if (streamed && getenv("KATGPU_TIMING"))
+        fprintf(stderr, "katgpu_timing {\"phase\": \"jf_load\", \"records\": %zu, \"chunks\": %u, \"read_s\": %.3f, \"copy_s\": %.3f, \"device_s\": %.3f, \"total_s\": %.3f}\n",
+                m, tm.chunks, tm.read_s, tm.copy_s, tm.device_s, (double)(t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) * 1e-9);
     *out = t;
     return KATGPU_OK;
 }
+
+extern "C" int katgpu_jf_load(katgpu_ctx* ctx, const char* path, katgpu_table** out) { return katgpu_jf_load_part(ctx, path, 0, 1, out); }
 
 extern "C" int katgpu_jf_dump(katgpu_table* t, const char* path) {
     if (!t || !path) return KATGPU_ERR_INVALID_ARG;

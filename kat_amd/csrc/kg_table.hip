@@ -1,5 +1,5 @@
 // kg_table.hip -- the HBM-resident count table behind katgpu_table: geometry and layout choice, allocation, regrow
-// (hash_counter::double_size), statistics, batch lookups and per-position profiles, record export / merge, the k-mer filter and the
+// (hash_counter::double_size), statistics, batch lookups and per-position profiles, record export / merge, .jf records out and in, the k-mer filter and the
 // per-record hit counts of `kat filter`, the per-record coverage statistics of `kat sect -n` and `kat cold`.
 #include "kg_host.hpp"
 #include "kg_kernels.hpp"
@@ -7,6 +7,7 @@
 #include "kg_filter.hpp"
 #include "kg_record_stats.hpp"
 #include "kg_jf_records.hpp"
+#include "kg_jf_load.hpp"
 #include "kg_jf.hpp"
 
 static const uint32_t g_region_slots = (uint32_t)hook_u64("KATGPU_TEST_REGION_SLOTS", REGION_SLOTS);
@@ -646,6 +647,121 @@ int jf_stream_records(katgpu_table* t, uint32_t r, const uint64_t* cols, FILE* f
     release();
     if (!rc && written != distinct) rc = fail(c, KATGPU_ERR_DEVICE, "jf dump: wrote %llu of %llu records", (unsigned long long)written, (unsigned long long)distinct);
     return rc;
+}
+
+// ------------------------------------------------------------------ .jf records into a table ----
+
+// n packed records at dev_recs added to t, with room made the way katgpu_table_merge_device makes it.  *unseen: records launched since
+// t->distinct was read -- every one may be a new k-mer; while the table holds that bound below its fill limit nothing is read back, so
+// a caller that feeds chunk after chunk synchronises only where the table may have to grow.
+static int jf_add_records(katgpu_table* t, const uint8_t* dev_recs, size_t n, uint32_t key_len, uint32_t counter_len, uint64_t* unseen) {
+    katgpu_ctx* c = t->ctx;
+    const uint32_t rb = (key_len + 7) / 8 + counter_len;
+    size_t pos = 0;
+    while (pos < n) {
+        const uint64_t limit = (uint64_t)(load_limit(t->dev()) * (double)t->dev().cap);
+        const uint64_t want = n - pos;
+        uint64_t take = want;
+        if (t->distinct + *unseen + want > limit) {
+            int rc = refresh_counters(t); if (rc) return rc;
+            *unseen = 0;
+            const uint64_t room = limit > t->distinct ? limit - t->distinct : 0;
+            if (room < std::min<uint64_t>(want, std::max<uint64_t>(t->dev().cap / 8, 1024))) {
+                rc = ensure_room(t, std::min<uint64_t>(want, std::max<uint64_t>(t->dev().cap / 2, 1024)));
+                if (rc) return rc;
+                continue;
+            }
+            take = std::min(want, room);
+        }
+        t->count_bound = 0xFFFFFFFFULL;          // the amounts are arbitrary: the next k_count launch sweeps first
+        {
+            ScopedTimer tm(c, KATGPU_K_MERGE, take);
+            const dim3 grid((unsigned)std::min<uint64_t>((take + JL_TILE - 1) / JL_TILE, (uint64_t)c->n_cu * 8));
+            if (t->dev().keys_b) hipLaunchKernelGGL(k_jf_add<true>, grid, dim3(JL_BLOCK), 0, c->stream, t->dev(), dev_recs + pos * rb, (uint64_t)take, key_len, counter_len);
+            else hipLaunchKernelGGL(k_jf_add<false>, grid, dim3(JL_BLOCK), 0, c->stream, t->dev(), dev_recs + pos * rb, (uint64_t)take, key_len, counter_len);
+        }
+        HIPCHK(c, hipGetLastError());
+        *unseen += take;
+        pos += take;
+    }
+    return KATGPU_OK;
+}
+
+extern "C" int katgpu_table_add_jf_records_device(katgpu_table* t, const uint8_t* dev_records, size_t n_records, uint32_t key_len, uint32_t counter_len) {
+    if (!t || (n_records && !dev_records)) return KATGPU_ERR_INVALID_ARG;
+    katgpu_ctx* c = t->ctx;
+    if (key_len != 2 * t->dv.k) return fail(c, KATGPU_ERR_MISMATCH, "jf records of %u key bits into a table of k = %u", key_len, t->dv.k);
+    if (counter_len < 1 || counter_len > 8) return fail(c, KATGPU_ERR_INVALID_ARG, "jf records: a count of %u bytes (1 to 8 are possible)", counter_len);
+    if (!n_records) return KATGPU_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    uint64_t unseen = 0;
+    rc = jf_add_records(t, dev_records, n_records, key_len, counter_len, &unseen);
+    if (rc) return rc;
+    return refresh_counters(t);
+}
+
+static const uint64_t g_jf_load_records = hook_u64("KATGPU_JF_LOAD_RECORDS", 0);   // tests: many chunks at tiny sizes
+
+int jf_stream_load(katgpu_table* t, FILE* f, size_t n, uint32_t key_len, uint32_t counter_len, JfLoadTiming* tm) {
+    katgpu_ctx* c = t->ctx;
+    if (!n) return KATGPU_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t rb = (key_len + 7) / 8 + counter_len;
+    const size_t chunk = (size_t)std::min<uint64_t>(g_jf_load_records ? g_jf_load_records : (uint64_t)1 << 24, n);
+    const size_t buf_bytes = chunk * rb;
+    const int nbuf = n > chunk ? 2 : 1;
+    uint8_t *d_buf[2] = {nullptr, nullptr}, *pinned[2] = {nullptr, nullptr};
+    hipEvent_t ev[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};      // copy started, copied, add started, added
+    bool used[2] = {false, false};
+    hipStream_t copy = nullptr;
+    auto release = [&]() {
+        hipStreamSynchronize(c->stream);
+        if (copy) { hipStreamSynchronize(copy); hipStreamDestroy(copy); }
+        for (int i = 0; i < 2; ++i) { pool_release(c, d_buf[i]); if (pinned[i]) hipHostFree(pinned[i]); for (hipEvent_t e : ev[i]) if (e) hipEventDestroy(e); }
+    };
+    bool have = hipStreamCreateWithFlags(&copy, hipStreamNonBlocking) == hipSuccess;
+    for (int i = 0; have && i < nbuf; ++i) {
+        have = pool_alloc(c, (void**)&d_buf[i], buf_bytes) == hipSuccess && hipHostMalloc((void**)&pinned[i], buf_bytes, hipHostMallocDefault) == hipSuccess;
+        for (int j = 0; have && j < 4; ++j) have = hipEventCreate(&ev[i][j]) == hipSuccess;
+    }
+    if (!have) { (void)hipGetLastError(); release(); return KG_JF_NO_SCRATCH; }
+
+    auto collect = [&](int slot) -> int {                         // the chunk that went through this slot has been added: its buffers are free
+        if (!used[slot]) return KATGPU_OK;
+        HIPCHK(c, hipEventSynchronize(ev[slot][3]));
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[slot][0], ev[slot][1]) == hipSuccess) tm->copy_s += ms * 1e-3;
+        if (hipEventElapsedTime(&ms, ev[slot][2], ev[slot][3]) == hipSuccess) tm->device_s += ms * 1e-3;
+        used[slot] = false;
+        return KATGPU_OK;
+    };
+    int rc = refresh_counters(t);
+    uint64_t unseen = 0;
+    int slot = 0;
+    for (size_t pos = 0; !rc && pos < n; slot = (slot + 1) % nbuf) {
+        const size_t take = std::min(chunk, n - pos);
+        rc = collect(slot);                                       // (the chunk before this one is being copied or added meanwhile)
+        if (rc) break;
+        const double t0 = now_ms();
+        const bool ok = fread(pinned[slot], rb, take, f) == take;
+        tm->read_s += (now_ms() - t0) * 1e-3;
+        if (!ok) { rc = KATGPU_ERR_IO; break; }
+        hipEventRecord(ev[slot][0], copy);
+        const hipError_t e = hipMemcpyAsync(d_buf[slot], pinned[slot], take * rb, hipMemcpyHostToDevice, copy);
+        hipEventRecord(ev[slot][1], copy);
+        if (e != hipSuccess) { rc = fail(c, KATGPU_ERR_DEVICE, "jf load: %s", hipGetErrorString(e)); break; }
+        hipStreamWaitEvent(c->stream, ev[slot][1], 0);
+        hipEventRecord(ev[slot][2], c->stream);
+        rc = jf_add_records(t, d_buf[slot], take, key_len, counter_len, &unseen);
+        hipEventRecord(ev[slot][3], c->stream);
+        used[slot] = true;
+        pos += take;
+        ++tm->chunks;
+    }
+    for (int i = 0; i < nbuf; ++i) { const int x = collect((slot + i) % nbuf); if (!rc) rc = x; }
+    release();
+    return rc ? rc : refresh_counters(t);
 }
 
 // ------------------------------------------------------------------ wide tables (33 <= k <= 63): records in and out ----
