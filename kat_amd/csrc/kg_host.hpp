@@ -1,7 +1,10 @@
 // kg_host.hpp -- what the host-side translation units of libkatgpu.so share: the context and table objects behind the opaque
 // handles of include/katgpu.h, error plumbing, the allocation pool, launch timing.  The library is split by concern:
 //   kg_context.hip   context, pool, profile counters, device buffers, the synthetic workload
-//   kg_table.hip     table life cycle (create / regrow / stats), lookups and profiles, record export / merge
+//   kg_table.hip     table life cycle: geometry, create / regrow / free, counters and statistics, room for records to come
+//   kg_query.hip     a sequence or keys against a table: lookups, profiles, per-record hits and coverage statistics
+//   kg_records.hip   records out of a table and into one: partition / export / merge, the k-mer filter
+//   kg_jf_device.hip .jf records in file order out of a table, and streamed from a file into one
 //   kg_count.hip     counting: the direct kernel, the partitioned counter's host loop, the host feeder, katgpu_count*
 //   kg_scan.hip      device-side record scan of raw FASTQ / FASTA bytes (katgpu_count_files' fast path)
 //   kg_exchange.hip  region-ordered extraction / merge for the multi-GPU exchange
@@ -20,10 +23,11 @@
 #include <cstring>
 #include <ctime>
 #include <atomic>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <string>
-#include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
 #include <vector>
@@ -214,6 +218,10 @@ bool table_may_stay_uncleared(const DevTable& d);
 double load_limit(const DevTable& d);
 int ensure_room(katgpu_table* t, uint64_t incoming);
 int table_wait(katgpu_table* t);               // the table's device arrays exist (katgpu_count allocates them asynchronously)
+// n records added to t in steps that fit under its fill limit, growing it between steps: launch(pos, take) adds records [pos, pos + take).
+// unseen == nullptr: the counters are read back before every step.  Otherwise *unseen is the number of records launched since t->distinct
+// was read -- every one may be a new k-mer -- and nothing is read back while the table holds that bound below its limit.
+int add_in_rooms(katgpu_table* t, size_t n, uint64_t* unseen, const std::function<int(size_t pos, uint64_t take)>& launch);
 // counting (kg_count.hip)
 int count_resident(katgpu_table* t, const uint8_t* dev_bases, size_t n);
 // large plain FASTQ / FASTA files: raw bytes to the device, record scan there (kg_scan.hip).  *took = false: not a file for this path
@@ -239,3 +247,108 @@ struct ScopedTimer {
     }
 };
 
+
+// ------------------------------------------------------------------ what the entry points share ----
+
+// A temporary device allocation that frees itself when it leaves scope: plain (hipMalloc; hipFree synchronises by itself) or out of a
+// context's pool (pool_release, once the context's stream has run dry: nothing queued there may still use the block; an idle stream costs nothing).
+struct DevBuf {
+    void* p = nullptr;
+    katgpu_ctx* pool = nullptr;          // non-null: a pool allocation of this context
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), pool(o.pool) { o.p = nullptr; }
+    ~DevBuf() { reset(); }
+    hipError_t plain(size_t bytes) { reset(); pool = nullptr; return hipMalloc(&p, bytes); }                 // (both leave p null when they fail)
+    hipError_t pooled(katgpu_ctx* c, size_t bytes) { reset(); pool = c; return pool_alloc(c, &p, bytes); }
+    void reset() { if (p && pool) { hipStreamSynchronize(pool->stream); pool_release(pool, p); } else if (p) hipFree(p); p = nullptr; }
+    template <typename T> T* as() const { return static_cast<T*>(p); }
+};
+
+// The four (aligned, wide) instantiations of a window kernel behind one call: launch(A, W, grid, n_chunks) with A and W a
+// std::true_type / std::false_type each, n_chunks = the chunks of per_chunk items in n, and a grid of at most eight workgroups per CU.
+template <typename Launch>
+void launch_aligned_wide(katgpu_ctx* c, bool aligned, bool wide, uint64_t n, uint64_t per_chunk, Launch&& launch) {
+    const uint64_t n_chunks = (n + per_chunk - 1) / per_chunk;
+    const dim3 grid((unsigned)std::min<uint64_t>(n_chunks, (uint64_t)c->n_cu * 8));
+    if (wide && aligned) launch(std::true_type{}, std::true_type{}, grid, n_chunks);
+    else if (wide) launch(std::false_type{}, std::true_type{}, grid, n_chunks);
+    else if (aligned) launch(std::true_type{}, std::false_type{}, grid, n_chunks);
+    else launch(std::false_type{}, std::false_type{}, grid, n_chunks);
+}
+
+// records of a host form: inside the n bases, in order and disjoint
+inline int check_records(katgpu_ctx* c, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec, size_t n) {
+    for (size_t r = 0; r < n_rec; ++r) {
+        if (rec_start[r] > n || rec_len[r] > n - rec_start[r]) return fail(c, KATGPU_ERR_INVALID_ARG, "record %zu lies beyond the %zu bases", r, n);
+        if (r && rec_start[r] < rec_start[r - 1] + rec_len[r - 1]) return fail(c, KATGPU_ERR_INVALID_ARG, "record %zu starts before record %zu ends: records must be in order and disjoint", r, r - 1);
+    }
+    return KATGPU_OK;
+}
+
+// The records of a host form through the device in batches [r0, r1) of at most max_bases bases and max_recs records (a record longer than that is a
+// batch of its own); joins(r, first) may end a batch earlier: it is asked once per record, in order, after the two limits (a batch's first record joins
+// whatever it says).  Per batch the bases from its first record's start to its last one's end, the starts (counted from there) and the lengths go up
+// (dev_start, dev_len: max_recs words each), body(dev_bases, nb, dev_start, dev_len, m, r0) queues its work, and the stream is waited for.
+// no_room != null: a batch of bases that finds no device memory ends the loop with KATGPU_ERR_NOMEM and its bytes there, for the caller to word.
+template <typename Joins, typename Body>
+int for_record_batches(katgpu_ctx* c, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec, size_t max_bases,
+                       size_t max_recs, uint64_t* dev_start, uint64_t* dev_len, const char* what, size_t* no_room, Joins&& joins, Body&& body) {
+    DevBuf db;
+    size_t db_bytes = 0;
+    std::vector<uint64_t> st(max_recs), ln(max_recs);
+    int rc = KATGPU_OK; hipError_t e = hipSuccess;
+    for (size_t r0 = 0; r0 < n_rec && !rc && e == hipSuccess;) {
+        const uint64_t base = rec_start[r0];
+        size_t r1 = r0;
+        joins(r1++, true);
+        while (r1 < n_rec && r1 - r0 < max_recs && rec_start[r1] + rec_len[r1] - base <= max_bases && joins(r1, false)) ++r1;
+        const size_t nb = rec_start[r1 - 1] + rec_len[r1 - 1] - base, m = r1 - r0;
+        if (nb + 64 > db_bytes) {
+            db_bytes = std::max(nb + 64, std::min(max_bases, n) + 64);
+            e = db.pooled(c, db_bytes);
+            if (e != hipSuccess) { db_bytes = 0; if (no_room) { *no_room = nb + 64; rc = KATGPU_ERR_NOMEM; } break; }
+        }
+        for (size_t r = r0; r < r1; ++r) { st[r - r0] = rec_start[r] - base; ln[r - r0] = rec_len[r]; }
+        if (nb) e = hipMemcpyAsync(db.p, bases + base, nb, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dev_start, st.data(), m * 8, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(dev_len, ln.data(), m * 8, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) break;
+        rc = body(db.as<uint8_t>(), nb, dev_start, dev_len, m, r0);
+        e = hipStreamSynchronize(c->stream);
+        r0 = r1;
+    }
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+    return KATGPU_OK;
+}
+
+// What a stream of .jf records between a file and the device runs on: a copy stream beside the context's and up to two slots of a device buffer, a
+// pinned buffer of that size and four events.  alloc(void**, bytes) makes a device buffer; pooled: pool_release gives it back, else hipFree.
+// Going out of scope waits for both streams and gives everything back.
+struct JfSlots {
+    katgpu_ctx* c;
+    bool pooled = false;
+    hipStream_t copy = nullptr;
+    struct Slot { uint8_t *dev = nullptr, *pinned = nullptr; hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; } slot[2];
+    explicit JfSlots(katgpu_ctx* c_) : c(c_) {}
+    JfSlots(const JfSlots&) = delete;
+    template <typename Alloc> bool setup(int n_slots, size_t bytes, bool pooled_, Alloc&& alloc) {
+        pooled = pooled_;
+        bool have = hipStreamCreateWithFlags(&copy, hipStreamNonBlocking) == hipSuccess;
+        for (int i = 0; have && i < n_slots; ++i) {
+            have = alloc((void**)&slot[i].dev, bytes) == hipSuccess && hipHostMalloc((void**)&slot[i].pinned, bytes, hipHostMallocDefault) == hipSuccess;
+            for (int j = 0; have && j < 4; ++j) have = hipEventCreate(&slot[i].ev[j]) == hipSuccess;
+        }
+        if (!have) (void)hipGetLastError();
+        return have;
+    }
+    ~JfSlots() {
+        hipStreamSynchronize(c->stream);
+        if (copy) { hipStreamSynchronize(copy); hipStreamDestroy(copy); }
+        for (Slot& s : slot) {
+            if (pooled) pool_release(c, s.dev); else hipFree(s.dev);
+            if (s.pinned) hipHostFree(s.pinned);
+            for (hipEvent_t e : s.ev) if (e) hipEventDestroy(e);
+        }
+    }
+};

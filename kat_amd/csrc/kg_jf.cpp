@@ -1,6 +1,6 @@
 // kg_jf.cpp -- Jellyfish "binary/sorted" hash files (.jf): reader and writer.  Pure host code; the records of a k <= 32 table's dump
-// are ordered and packed on the device (kg_jf_records.hpp, jf_stream_records in kg_table.hip), and the records of a file being loaded
-// are unpacked and added there (kg_jf_load.hpp, jf_stream_load in kg_table.hip).
+// are ordered and packed on the device (kg_jf_records.hpp, jf_stream_records in kg_jf_device.hip), and the records of a file being loaded
+// are unpacked and added there (kg_jf_load.hpp, jf_stream_load in kg_jf_device.hip).
 //
 // Replaces JellyfishHelper::dumpHash / HashLoader::loadHash (lib/src/jellyfish_helper.cc:248-256,97-187) and the parts
 // of Jellyfish they stand on: generic_file_header::write/read (JF/include/jellyfish/generic_file_header.hpp:96-153),

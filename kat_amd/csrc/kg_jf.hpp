@@ -1,4 +1,4 @@
-// kg_jf.hpp -- what the .jf reader and writer (kg_jf.cpp, pure host code) ask of the device side (kg_table.hip).
+// kg_jf.hpp -- what the .jf reader and writer (kg_jf.cpp, pure host code) ask of the device side (kg_jf_device.hip).
 #pragma once
 #include "../../include/katgpu.h"
 #include <cstdio>

@@ -1,0 +1,274 @@
+// kg_query.hip -- a sequence or keys against a table, which is left as it is: batch lookups (katgpu_table_get*), per-position profiles
+// (katgpu_table_profile_*), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*) and the per-record coverage statistics
+// of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*).  The host forms send their input through the device in batches.
+#include "kg_host.hpp"
+#include "kg_kernels.hpp"
+#include "kg_wide.hpp"
+#include "kg_filter.hpp"
+#include "kg_record_stats.hpp"
+
+static const bool g_forbid_profile_host = hook_u64("KATGPU_TEST_FORBID_PROFILE_HOST", 0) != 0;   // tests: a driver that should not need per-position counts asks for none
+static const size_t g_profile_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_PROFILE_BATCH", (uint64_t)32 << 20), 1);   // tests: window starts per batch of profile_host
+static const size_t g_hits_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_HITS_BATCH", (uint64_t)64 << 20), 1);        // tests: bases per batch of seq_hits_host
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static uint64_t chunk_starts(bool wide) { return wide ? WIDE_CHUNK_STARTS : CHUNK_STARTS; }   // window starts per chunk of the window kernels
+
+extern "C" int katgpu_table_get(katgpu_table* t, const uint64_t* keys, size_t n, int canonicalise, uint64_t* counts) {
+    if (!t || (n && (!keys || !counts))) return KATGPU_ERR_INVALID_ARG;
+    NARROW_ONLY(t, "katgpu_table_get: use katgpu_table_get_wide;");
+    if (!n) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    DevBuf dk, dc;
+    HIPCHK(c, dk.plain(n * 8));
+    if (dc.plain(n * 8) != hipSuccess) return fail(c, KATGPU_ERR_NOMEM, "lookup buffers");
+    hipMemcpyAsync(dk.p, keys, n * 8, hipMemcpyHostToDevice, c->stream);
+    hipLaunchKernelGGL(k_get, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, t->dev(), t->n_ovf, dk.as<uint64_t>(), (uint64_t)n, canonicalise, dc.as<uint64_t>());
+    hipMemcpyAsync(counts, dc.p, n * 8, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s", hipGetErrorString(e));
+    return KATGPU_OK;
+}
+
+extern "C" int katgpu_table_get_wide(katgpu_table* t, const uint64_t* keys_hi, const uint64_t* keys_lo, size_t n, int canonicalise, uint64_t* counts) {
+    if (!t || (n && (!keys_hi || !keys_lo || !counts))) return KATGPU_ERR_INVALID_ARG;
+    katgpu_ctx* c = t->ctx;
+    if (!t->dev().keys_b) return fail(c, KATGPU_ERR_K, "katgpu_table_get_wide is for k > 32 tables (k = %u): use katgpu_table_get", t->dev().k);
+    if (!n) return KATGPU_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    DevBuf buf; HIPCHK(c, buf.plain(3 * n * 8));
+    uint64_t* d = buf.as<uint64_t>();
+    hipMemcpyAsync(d, keys_hi, n * 8, hipMemcpyHostToDevice, c->stream);
+    hipMemcpyAsync(d + n, keys_lo, n * 8, hipMemcpyHostToDevice, c->stream);
+    hipLaunchKernelGGL(k_get_w, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, t->dev(), t->n_ovf, d, d + n, (uint64_t)n, canonicalise, d + 2 * n);
+    hipMemcpyAsync(counts, d + 2 * n, n * 8, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s", hipGetErrorString(e));
+    return KATGPU_OK;
+}
+
+static int launch_profile(katgpu_table* t, const uint8_t* dev_bases, size_t n, int canonicalise, uint64_t* dev_counts) {
+    katgpu_ctx* c = t->ctx;
+    const bool wide = t->dev().keys_b != nullptr;
+    const uint64_t n_out = n - t->dev().k + 1;
+    ScopedTimer tm(c, KATGPU_K_PROFILE, n_out);
+    launch_aligned_wide(c, aligned16(dev_bases) && aligned16(dev_counts), wide, n_out, chunk_starts(wide), [&](auto A, auto W, dim3 grid, uint64_t n_chunks) {
+        hipLaunchKernelGGL((k_profile<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, t->dev(), t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_counts);
+    });
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+extern "C" int katgpu_table_profile_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, int canonicalise, uint64_t* dev_counts) {
+    if (!t || (n && (!dev_bases || !dev_counts))) return KATGPU_ERR_INVALID_ARG;
+    if (n < t->dev().k) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    return launch_profile(t, dev_bases, n, canonicalise, dev_counts);
+}
+
+// Host form: the sequence goes through the device in batches of g_profile_batch window starts (each batch re-sends the
+// k-1 bases it shares with the next one), so any length fits next to the table.
+extern "C" int katgpu_table_profile_host(katgpu_table* t, const char* bases, size_t n, int canonicalise, uint64_t* counts) {
+    if (!t || (n && (!bases || !counts))) return KATGPU_ERR_INVALID_ARG;
+    if (g_forbid_profile_host) return fail(t->ctx, KATGPU_ERR_INVALID_ARG, "katgpu_table_profile_host is forbidden (KATGPU_TEST_FORBID_PROFILE_HOST)");
+    const uint32_t k = t->dev().k;
+    if (n < k) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    const size_t n_out = n - k + 1;
+    const size_t batch = std::min(n_out, g_profile_batch);
+    DevBuf db, dc;
+    HIPCHK(c, db.pooled(c, batch + 64));
+    if (dc.pooled(c, batch * 8) != hipSuccess) return fail(c, KATGPU_ERR_NOMEM, "profile buffers");
+    hipError_t e = hipSuccess;
+    for (size_t pos = 0; pos < n_out && rc == KATGPU_OK && e == hipSuccess; pos += batch) {
+        const size_t starts = std::min(batch, n_out - pos);
+        const size_t nb = starts + k - 1;
+        e = hipMemcpyAsync(db.p, bases + pos, nb, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) break;
+        rc = launch_profile(t, db.as<uint8_t>(), nb, canonicalise, dc.as<uint64_t>());
+        if (rc) break;
+        e = hipMemcpyAsync(counts + pos, dc.p, starts * 8, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s", hipGetErrorString(e));
+    return KATGPU_OK;
+}
+
+static int launch_seq_hits(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec,
+                           int canonicalise, uint64_t* dev_hits) {
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipMemsetAsync(dev_hits, 0, n_rec * sizeof(uint64_t), c->stream));
+    const uint32_t k = t->dev().k;
+    if (n < k || !n_rec) return KATGPU_OK;
+    const bool wide = t->dev().keys_b != nullptr;
+    const uint64_t n_out = n - k + 1;
+    unsigned long long* h = (unsigned long long*)dev_hits;
+    ScopedTimer tm(c, KATGPU_K_PROFILE, n_out);
+    launch_aligned_wide(c, aligned16(dev_bases), wide, n_out, chunk_starts(wide), [&](auto A, auto W, dim3 grid, uint64_t n_chunks) {
+        hipLaunchKernelGGL((k_seq_hits<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, t->dev(), t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, h);
+    });
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+extern "C" int katgpu_table_seq_hits_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                            const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, uint64_t* dev_hits) {
+    if (!t || (n_rec && (!dev_rec_start || !dev_rec_len || !dev_hits)) || (n && !dev_bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!n_rec) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    return launch_seq_hits(t, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, canonicalise, dev_hits);
+}
+
+// Host form: the records go through the device in batches of at most g_hits_batch bases and SEQ_HITS_RECS records (for_record_batches),
+// so any input fits next to the table.
+extern "C" int katgpu_table_seq_hits_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                                          size_t n_rec, int canonicalise, uint64_t* hits) {
+    if (!t || (n_rec && (!rec_start || !rec_len || !hits)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!n_rec) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = refresh_counters(t); if (rc) return rc;
+    const size_t SEQ_HITS_RECS = (size_t)1 << 20;
+    DevBuf recs;                                                   // start, length and hits of every record of a batch
+    HIPCHK(c, recs.pooled(c, SEQ_HITS_RECS * 3 * sizeof(uint64_t)));
+    uint64_t* dr = recs.as<uint64_t>();
+    return for_record_batches(c, bases, n, rec_start, rec_len, n_rec, g_hits_batch, SEQ_HITS_RECS, dr, dr + SEQ_HITS_RECS, "seq hits", nullptr,
+                              [](size_t, bool) { return true; },
+                              [&](const uint8_t* db, size_t nb, const uint64_t* ds, const uint64_t* dl, size_t m, size_t r0) {
+        int rc = launch_seq_hits(t, db, nb, ds, dl, m, canonicalise, dr + 2 * SEQ_HITS_RECS);
+        if (rc) return rc;
+        const hipError_t e = hipMemcpyAsync(hits + r0, dr + 2 * SEQ_HITS_RECS, m * 8, hipMemcpyDeviceToHost, c->stream);
+        return e == hipSuccess ? KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "seq hits: %s", hipGetErrorString(e));
+    });
+}
+
+// ------------------------------------------------------------------ per-record coverage statistics (kat sect -n, kat cold) ----
+
+static const uint32_t g_stats_short = (uint32_t)std::min<uint64_t>(hook_u64("KATGPU_TEST_STATS_SHORT", RS_SHORT_WINDOWS), RS_SHORT_WINDOWS);   // tests: the short / long limit, in windows
+static const size_t g_stats_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_STATS_BATCH", (uint64_t)32 << 20), 1);                    // tests: bases per batch of the host form
+static_assert(sizeof(katgpu_record_stats) == RS_FIELDS * sizeof(uint64_t), "the kernels write a record's statistics as six words");
+
+// Everything on the stream: the result cleared, K11 over the tiles, and, when n_long records are long (long_windows windows in all),
+// their slots, K12 and the eight passes of K13 over those windows.  ws takes the workspace of the long records (none: left empty), to be
+// let go once the stream has run.  Two timed sections: the second only when there are long records.
+static int launch_record_stats(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec,
+                               int canonicalise, katgpu_record_stats* dev_out, uint64_t n_long, uint64_t long_windows, DevBuf& ws) {
+    katgpu_ctx* c = t->ctx;
+    ws.reset();
+    HIPCHK(c, hipMemsetAsync(dev_out, 0, n_rec * sizeof(katgpu_record_stats), c->stream));
+    if (!n || !n_rec) return KATGPU_OK;
+    const DevTable& d = t->dev();
+    const uint32_t k = d.k;
+    const bool wide = d.keys_b != nullptr;
+    const bool aligned = aligned16(dev_bases);
+    const uint64_t n_out = n >= k ? n - k + 1 : 0;
+    unsigned long long* o = (unsigned long long*)dev_out;
+    {
+        ScopedTimer tm(c, KATGPU_K_PROFILE, n_out);
+        launch_aligned_wide(c, aligned, wide, n, RS_TILE_STRIDE, [&](auto A, auto W, dim3 grid, uint64_t n_tiles) {
+            hipLaunchKernelGGL((k_rstats_short<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, d, t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_tiles, dev_start, dev_len, (uint64_t)n_rec, g_stats_short, o);
+        });
+        HIPCHK(c, hipGetLastError());
+    }
+    if (!n_long || !long_windows) return KATGPU_OK;
+    // the long records' workspace: selection state | digit histograms | slot of every record | a count per window of a long record
+    const size_t hist_off = align_up(n_long * sizeof(RsSel), 16), slot_off = hist_off + n_long * RS_DIGITS * sizeof(uint64_t);
+    const size_t cnt_off = align_up(slot_off + n_rec * sizeof(uint32_t), 16), bytes = cnt_off + long_windows * sizeof(uint64_t);
+    if (ws.pooled(c, bytes) != hipSuccess)
+        return fail(c, KATGPU_ERR_NOMEM, "record statistics: no %zu bytes of device memory for the counts of %llu long records (%llu windows)", bytes,
+                    (unsigned long long)n_long, (unsigned long long)long_windows);
+    uint8_t* w = ws.as<uint8_t>();
+    RsSel* sel = (RsSel*)w;
+    unsigned long long* hist = (unsigned long long*)(w + hist_off);
+    uint32_t* rec_slot = (uint32_t*)(w + slot_off);
+    uint64_t* cnt = (uint64_t*)(w + cnt_off);
+    ScopedTimer tm(c, KATGPU_K_PROFILE, 0);
+    HIPCHK(c, hipMemsetAsync(w, 0, slot_off, c->stream));
+    HIPCHK(c, hipMemsetAsync(rec_slot, 0xFF, n_rec * sizeof(uint32_t), c->stream));
+    hipLaunchKernelGGL(k_rstats_classify, dim3(1), dim3(RS_CLASSIFY_BLOCK), 0, c->stream, dev_len, (uint64_t)n_rec, k, g_stats_short, n_long, long_windows, rec_slot, sel);
+    launch_aligned_wide(c, aligned, wide, n, chunk_starts(wide), [&](auto A, auto W, dim3 grid, uint64_t n_chunks) {
+        hipLaunchKernelGGL((k_rstats_long<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, d, t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, rec_slot, cnt, long_windows, sel, o);
+    });
+    const uint64_t sel_chunks = (long_windows + RS_SEL_CHUNK - 1) / RS_SEL_CHUNK;
+    const dim3 hg((unsigned)std::min<uint64_t>(sel_chunks, (uint64_t)c->n_cu * 8)), pg((unsigned)((n_long + 3) / 4));
+    for (int shift = 56; shift >= 0; shift -= 8) {
+        hipLaunchKernelGGL(k_rstats_hist, hg, dim3(256), 0, c->stream, cnt, long_windows, sel_chunks, k, dev_len, sel, n_long, (uint32_t)shift, hist);
+        hipLaunchKernelGGL(k_rstats_pick, pg, dim3(256), 0, c->stream, sel, n_long, (uint32_t)shift, hist, o);
+    }
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+// Device form.  The number of long records and of their windows comes back from the device first (two words; refresh_counters has synchronised already);
+// with none, the rest is asynchronous on the stream, otherwise the call returns when the selection's workspace has been released.
+extern "C" int katgpu_table_record_stats_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                                const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, katgpu_record_stats* dev_out) {
+    if (!t || (n_rec && (!dev_rec_start || !dev_rec_len || !dev_out)) || (n && !dev_bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!n_rec) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    unsigned long long* scratch = (unsigned long long*)&t->dev().ctrs[CTR_SCRATCH];
+    unsigned long long n_long[2] = {0, 0};
+    HIPCHK(c, hipMemsetAsync(scratch, 0, sizeof n_long, c->stream));
+    hipLaunchKernelGGL(k_rstats_count_long, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, c->stream, dev_rec_len, (uint64_t)n_rec, t->dev().k, g_stats_short, scratch);
+    HIPCHK(c, hipMemcpyAsync(n_long, scratch, sizeof n_long, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    DevBuf ws;
+    rc = launch_record_stats(t, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, canonicalise, dev_out, n_long[0], n_long[1], ws);
+    if (ws.p) {
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (!rc && e != hipSuccess) rc = fail(c, KATGPU_ERR_DEVICE, "record stats: %s", hipGetErrorString(e));
+    }
+    return rc;
+}
+
+// Host form: the records go through the device in batches of at most g_stats_batch bases and STATS_RECS records (for_record_batches),
+// so any input fits next to the table; a batch also ends where its long records would have more than
+// g_stats_batch / 4 windows between them (a single record may), which bounds their count scratch by the longest record or 8 bytes x that.
+// What comes back is sizeof(katgpu_record_stats) per record.
+extern "C" int katgpu_table_record_stats_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                                              size_t n_rec, int canonicalise, katgpu_record_stats* out) {
+    if (!t || (n_rec && (!rec_start || !rec_len || !out)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!n_rec) return KATGPU_OK;
+    katgpu_ctx* c = t->ctx;
+    int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = refresh_counters(t); if (rc) return rc;
+    const uint32_t k = t->dev().k;
+    const size_t cap = std::min(n_rec, (size_t)1 << 20);           // records per batch
+    DevBuf recs, ws;                                               // start, length and the six result words of every record of a batch; the long records' workspace
+    if (recs.pooled(c, cap * (2 + RS_FIELDS) * sizeof(uint64_t)) != hipSuccess)
+        return fail(c, KATGPU_ERR_NOMEM, "record statistics: no device memory for the records of a batch");
+    uint64_t* dr = recs.as<uint64_t>();
+    katgpu_record_stats* d_out = (katgpu_record_stats*)(dr + 2 * cap);
+    uint64_t n_long = 0, long_windows = 0;                         // of the batch being cut
+    auto joins = [&](size_t r, bool first) {
+        if (first) n_long = long_windows = 0;
+        uint64_t w = rec_len[r] >= k ? rec_len[r] - k + 1 : 0;
+        if (w <= g_stats_short) w = 0;
+        if (!first && long_windows + w > std::max<uint64_t>(g_stats_batch / 4, 1)) return false;
+        n_long += w != 0; long_windows += w;
+        return true;
+    };
+    size_t no_room = 0;
+    rc = for_record_batches(c, bases, n, rec_start, rec_len, n_rec, g_stats_batch, cap, dr, dr + cap, "record stats", &no_room, joins,
+                            [&](const uint8_t* db, size_t nb, const uint64_t* ds, const uint64_t* dl, size_t m, size_t r0) {
+        int rc = launch_record_stats(t, db, nb, ds, dl, m, canonicalise, d_out, n_long, long_windows, ws);
+        if (rc) return rc;
+        const hipError_t e = hipMemcpyAsync(out + r0, d_out, m * sizeof(katgpu_record_stats), hipMemcpyDeviceToHost, c->stream);
+        return e == hipSuccess ? KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "record stats: %s", hipGetErrorString(e));
+    });
+    return no_room ? fail(c, KATGPU_ERR_NOMEM, "record statistics: no %zu bytes of device memory for a batch of bases", no_room) : rc;
+}

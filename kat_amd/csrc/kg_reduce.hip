@@ -23,8 +23,8 @@ extern "C" int katgpu_hist(katgpu_table* t, uint64_t base, uint64_t ceil_, uint6
     katgpu_ctx* c = t->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = refresh_counters(t); if (rc) return rc;
-    unsigned long long* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, nb * 8));
+    DevBuf buf; HIPCHK(c, buf.plain(nb * 8));
+    unsigned long long* d = buf.as<unsigned long long>();
     hipMemsetAsync(d, 0, nb * 8, c->stream);
     const uint32_t lds_bins = (uint32_t)std::min<uint64_t>(nb, 16384);          // 64 KB of u32 -> two blocks per CU
     {
@@ -38,7 +38,6 @@ extern "C" int katgpu_hist(katgpu_table* t, uint64_t base, uint64_t ceil_, uint6
     }
     hipMemcpyAsync(out, d, nb * 8, hipMemcpyDeviceToHost, c->stream);
     hipError_t e = hipStreamSynchronize(c->stream);
-    hipFree(d);
     if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s", hipGetErrorString(e));
     return KATGPU_OK;
 }
@@ -49,8 +48,8 @@ extern "C" int katgpu_gcp(katgpu_table* t, double cvg_scale, uint32_t cvg_bins, 
     HIPCHK(c, hipSetDevice(c->device));
     int rc = refresh_counters(t); if (rc) return rc;
     const size_t cells = (size_t)t->dev().k * ((size_t)cvg_bins + 1);
-    unsigned long long* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, cells * 8));
+    DevBuf buf; HIPCHK(c, buf.plain(cells * 8));
+    unsigned long long* d = buf.as<unsigned long long>();
     hipMemsetAsync(d, 0, cells * 8, c->stream);
     const size_t lds = cells * sizeof(uint32_t);
     const uint32_t use_lds = lds <= 150 * 1024 ? (g_comp_plain_inc ? 2 : 1) : 0;   // 160 KB LDS per CU
@@ -71,7 +70,6 @@ extern "C" int katgpu_gcp(katgpu_table* t, double cvg_scale, uint32_t cvg_bins, 
     HIPCHK(c, hipGetLastError());
     hipMemcpyAsync(out, d, cells * 8, hipMemcpyDeviceToHost, c->stream);
     hipError_t e = hipStreamSynchronize(c->stream);
-    hipFree(d);
     if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s", hipGetErrorString(e));
     return KATGPU_OK;
 }
@@ -90,15 +88,15 @@ extern "C" int katgpu_comp(katgpu_table* t1, katgpu_table* t2, int canon1, int c
     const bool wide = t1->dev().keys_b != nullptr;               // same k => same key width in both tables
     const uint32_t ss = std::min(d1_bins, d2_bins);
     const size_t mx_cells = (size_t)d1_bins * d2_bins, total = mx_cells + 13 + 4 * (size_t)ss;
-    unsigned long long* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, total * 8));
+    DevBuf buf, seen; HIPCHK(c, buf.plain(total * 8));         // the results; a bit per slot of hash 2 (below)
+    unsigned long long* d = buf.as<unsigned long long>();
     hipMemsetAsync(d, 0, total * 8, c->stream);
     CompArgs a{};
     a.d1_scale = d1_scale; a.d2_scale = d2_scale; a.d1_bins = d1_bins; a.d2_bins = d2_bins; a.spec_size = ss;
     a.canon_probe = canon2 ? 1 : 0;
     a.main_mx = d; a.counters = d + mx_cells; a.spectra = d + mx_cells + 13;
     const size_t lds1 = 16 * 8 + COMP_TILE * COMP_TILE * 4 + 3 * (size_t)ss * 4, lds2 = 16 * 8 + COMP_TILE * COMP_TILE * 4 + (size_t)ss * 4;
-    if (lds1 > 150 * 1024) { hipFree(d); return fail(c, KATGPU_ERR_INVALID_ARG, "min(d1_bins,d2_bins) = %u too large for the LDS-privatised spectra", ss); }
+    if (lds1 > 150 * 1024) return fail(c, KATGPU_ERR_INVALID_ARG, "min(d1_bins,d2_bins) = %u too large for the LDS-privatised spectra", ss);
     if (lds1 > 64 * 1024) {
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(wide ? k_comp<1, true> : k_comp<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(wide ? k_comp<2, true> : k_comp<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
@@ -130,10 +128,9 @@ extern "C" int katgpu_comp(katgpu_table* t1, katgpu_table* t2, int canon1, int c
     const bool join_1 = same_grid && ident1 && (g_force_join || join_pays(t1, t2));
     const uint32_t wpr = (t2->dev().region_slots + 31) / 32;
     const bool marked = !fused && join_1 && !g_no_seen && t1->dev().canonical && t2->dev().canonical && t2->ones == 0 && join1 + (size_t)wpr * 4 <= 150 * 1024;
-    uint32_t* seen_bits = nullptr;
     if (marked) {
-        if (pool_alloc(c, (void**)&seen_bits, (size_t)t2->dev().n_regions * wpr * 4) != hipSuccess) { (void)hipGetLastError(); seen_bits = nullptr; }
-        a.seen = seen_bits; a.seen_wpr = wpr;
+        if (seen.pooled(c, (size_t)t2->dev().n_regions * wpr * 4) != hipSuccess) (void)hipGetLastError();
+        a.seen = seen.as<uint32_t>(); a.seen_wpr = wpr;
     }
     // unscaled matrices of more than COMP_TILE bins (KAT's defaults): the spectra of the k-mers that land in the LDS tile are its marginals
     a.plain_inc = g_comp_plain_inc ? 1 : 0;
@@ -191,8 +188,6 @@ extern "C" int katgpu_comp(katgpu_table* t1, katgpu_table* t2, int canon1, int c
     hipMemcpyAsync(counters, d + mx_cells, 13 * 8, hipMemcpyDeviceToHost, c->stream);
     hipMemcpyAsync(spectra, d + mx_cells + 13, 4 * (size_t)ss * 8, hipMemcpyDeviceToHost, c->stream);
     hipError_t e = hipStreamSynchronize(c->stream);
-    hipFree(d);
-    if (seen_bits) pool_release(c, seen_bits);
     if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s", hipGetErrorString(e));
     return KATGPU_OK;
 }
@@ -209,8 +204,8 @@ extern "C" int katgpu_comp3(katgpu_table* t1, katgpu_table* t2, katgpu_table* t3
         return fail(c, KATGPU_ERR_MISMATCH, "Cannot process hashes that were created with different K-mer lengths.  Expected: %u.  Key length was %u", t1->dev().k, t3->dev().k);
     rc = refresh_counters(t3); if (rc) return rc;
     const size_t cells = (size_t)d1_bins * d2_bins;
-    unsigned long long* d = nullptr;
-    HIPCHK(c, hipMalloc(&d, (3 * cells + 13) * 8));
+    DevBuf buf; HIPCHK(c, buf.plain((3 * cells + 13) * 8));
+    unsigned long long* d = buf.as<unsigned long long>();
     hipMemsetAsync(d, 0, (3 * cells + 13) * 8, c->stream);
     Comp3Args a{};
     a.d1_scale = d1_scale; a.d2_scale = d2_scale; a.d1_bins = d1_bins; a.d2_bins = d2_bins;
@@ -233,7 +228,6 @@ extern "C" int katgpu_comp3(katgpu_table* t1, katgpu_table* t2, katgpu_table* t3
     hipMemcpyAsync(mixed_mx, d + 2 * cells, cells * 8, hipMemcpyDeviceToHost, c->stream);
     hipMemcpyAsync(c3, d + 3 * cells, sizeof c3, hipMemcpyDeviceToHost, c->stream);
     hipError_t e = hipStreamSynchronize(c->stream);
-    hipFree(d);
     if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s", hipGetErrorString(e));
     counters[CC_H3_TOTAL] = c3[CC_H3_TOTAL];
     counters[CC_H3_DISTINCT] = c3[CC_H3_DISTINCT];

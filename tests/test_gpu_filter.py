@@ -3,6 +3,7 @@ end to end (files byte for byte, stdout lines, errors)."""
 import gzip
 import os
 import subprocess
+import sys
 import time
 
 import numpy as np
@@ -10,6 +11,7 @@ import pytest
 
 from kat_amd import synth
 from tests import filter_model as fm
+from tests import host_batch_case as hb
 
 pytestmark = pytest.mark.gpu
 
@@ -155,6 +157,25 @@ def test_seq_hits_against_profile(engine, ko, k, canon):
         engine.sync()
         assert np.array_equal(dr.download(np.uint64, len(recs), offset=16 * len(recs)), want)
         db.free(); dr.free()
+
+
+@pytest.mark.parametrize("k,canon", [(27, False), (51, True)])
+def test_seq_hits_host_in_many_batches(ko, tmp_path, k, canon):
+    """katgpu_table_seq_hits_host with batches of 4000 bases: the records of 5000 and 9000 bases are batches of their own, the run of 3000
+    empty records spans cuts, and every record's hits equal what one batch gives (the model's count over the oracle's profile)."""
+    o = (ko.WideTable(k, canon) if k > 32 else ko.Table(k, canon)).count_bases(hb.counted())
+    b, st, ln, recs = hb.hits_records(k)
+    assert int(ln.max()) == 9000 and int((ln == 0).sum()) >= 3000 and b"".join(s.encode() for s in recs) == b
+    for canonicalise in (False, True):
+        want = np.array([fm.record_hits(*ko.profile(o, s, canonicalise)) if s else 0 for s in recs], np.uint64)
+        assert want.sum() > 0
+        out = str(tmp_path / ("hits%d.npy" % canonicalise))
+        r = subprocess.run([sys.executable, "-m", "tests.host_batch_case", "hits", str(k), str(int(canon)), str(int(canonicalise)), "0", out], cwd=ROOT,
+                           env={**os.environ, "KATGPU_TEST_HITS_BATCH": "4000"}, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(b) > 60000 and int(open(out + ".sections").read()) > 10              # the hook bites: but for the two long records', no batch holds more than 4000 bases
+        got = np.load(out)
+        assert got.dtype == np.uint64 and np.array_equal(got, want), (k, canonicalise, np.nonzero(got != want)[0][:10])
 
 
 # ---- the command line ----

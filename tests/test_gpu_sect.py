@@ -3,10 +3,12 @@ the C++ host mirror's `katgpu sect` files byte for byte against oracle/koracle_s
 option sweeps)."""
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
 
+from tests import host_batch_case as hb
 from tests.test_oracle_sect import make_cases
 
 pytestmark = pytest.mark.gpu
@@ -76,6 +78,31 @@ def test_profile_device_unaligned_and_batches(ko, engine):
     idx = np.arange(got.size) % genome.size
     assert np.array_equal(got, period[idx])
     t.free()
+
+
+@pytest.mark.parametrize("k,batch,n_bases", [(27, 5000, 0), (51, 5000, 0), (27, 1, 300)], ids=["k27", "k51", "k27-one-start"])
+def test_profile_host_in_many_batches(ko, tmp_path, k, batch, n_bases):
+    """katgpu_table_profile_host in batches of 5000 window starts (six of them, cut off the kernel's 4064-start chunks), and of a single
+    start (the smallest seam there is): every position as in one profile of the whole sequence."""
+    o = (ko.WideTable(k, True) if k > 32 else ko.Table(k, True)).count_bases(hb.counted())
+    s = hb.profile_sequence()
+    assert s.size == 30000 and 150 < np.isin(s, np.frombuffer(b"ACGT", np.uint8), invert=True).sum() < 450
+    s = s[:n_bases] if n_bases else s
+    for canonicalise in (False, True):
+        want, _ = ko.profile(o, s.tobytes(), canonicalise)
+        assert want.size == s.size - k + 1 and (want > 0).any() and (want == 0).any()
+        out = str(tmp_path / ("profile%d.npy" % canonicalise))
+        r = subprocess.run([sys.executable, "-m", "tests.host_batch_case", "profile", str(k), "1", str(int(canonicalise)), str(n_bases), out], cwd=ROOT,
+                           env={**os.environ, "KATGPU_TEST_PROFILE_BATCH": str(batch)}, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        cuts = list(range(batch, want.size, batch))
+        assert int(open(out + ".sections").read()) == len(cuts) + 1 == (6 if batch == 5000 else 274)      # the hook bites
+        got = np.load(out)
+        assert got.dtype == np.uint64 and got.shape == want.shape
+        bad = np.nonzero(got != want)[0]
+        near = [int(p) for p in bad if min(abs(int(p) - c) for c in cuts) < k]            # within k - 1 window starts of a cut: windows that share bases with the other batch
+        assert bad.size == 0, "k = %d, canonicalise = %s: %d positions differ; within k - 1 = %d starts of a cut (cuts at %s): %s; elsewhere: %s" % (
+            k, canonicalise, bad.size, k - 1, cuts[:8], near[:20], [int(p) for p in bad if int(p) not in near][:20])
 
 
 def test_counts_above_32_bits(ko, engine):
