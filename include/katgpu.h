@@ -209,6 +209,34 @@ int katgpu_table_record_stats_host(katgpu_table* t, const char* bases, size_t n,
                                    size_t n_rec, int canonicalise, katgpu_record_stats* out);
 int katgpu_table_record_stats_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
                                      const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, katgpu_record_stats* dev_out);
+/* `kat sect -n -E / -F`: the intervals Sect::printRegions (src/sect.cc:373-424) finds in a record's per-position counts, found on
+ * the device.  Records are given as for katgpu_table_seq_hits_*; nb = rec_len - k + 1 when rec_len >= k, else 0.  With c[j], j in
+ * [0, nb), the table's full count of window j of a record (side table included, 64 bits; 0 when the window holds a byte outside
+ * ACGTacgt: what katgpu_table_profile_* writes), window j is in a range when c[j] >= min && (max == 0 || c[j] <= max), and a region
+ * is a maximal run [start, stop) of such j inside one record: a run never continues into the next record, not even where two records
+ * touch and k = 1 puts their windows side by side; a run that reaches the record's last window has stop == nb.  One call takes
+ * n_ranges = 1 or 2 ranges, which share the lookups (`-E` is (1, min_repeat), `-F` is (min_repeat, max_repeat)).  For each range the
+ * regions come sorted by (record, start), range 1's after range 0's, n_out[q] of them for range q; `record` counts from the call's
+ * first record, start and stop from the record's first window.  No per-position array crosses the bus in either form.
+ * Host form: validates the records (KATGPU_ERR_INVALID_ARG, the messages of katgpu_table_seq_hits_host) and returns one malloc'ed
+ * array of n_out[0] + n_out[1] regions in *regions (katgpu_free_host; never NULL on success).  Device memory, beyond the table and
+ * from the context's pool: the records go through in batches of at most B = 2^25 bases and 2^20 records, a record longer than B
+ * being a batch of its own: max(B, L) + 64 bytes of bases, with L the longest record, and 16 bytes per record of a batch; (1 +
+ * n_ranges) / 8 bytes per base of a batch for the bit masks (one bit per base and range, one more for the records' first windows),
+ * 16 bytes per range and 16384 bases for the counters, and 24 bytes per region of a batch.  KATGPU_ERR_NOMEM, with a message, when
+ * that cannot be had.
+ * Device form: takes device pointers, does not validate the records, and takes the masks and counters above, for all n bases, from
+ * the pool.  It writes the first min(n_out[0] + n_out[1], cap) regions of the concatenated order to dev_regions and always reports
+ * the true totals: a caller that sees n_out[0] + n_out[1] > cap calls again with more room.  cap == 0 with dev_regions == NULL only
+ * counts.  It returns when the work is done. */
+typedef struct katgpu_count_range { uint64_t min, max; } katgpu_count_range;   /* max == 0: no upper bound */
+typedef struct katgpu_region { uint64_t record, start, stop; } katgpu_region;
+int katgpu_table_record_regions_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                                     size_t n_rec, int canonicalise, const katgpu_count_range* ranges, uint32_t n_ranges /* 1 or 2 */,
+                                     katgpu_region** regions, size_t n_out[/* n_ranges */]);
+int katgpu_table_record_regions_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                       const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, const katgpu_count_range* ranges,
+                                       uint32_t n_ranges, katgpu_region* dev_regions, size_t cap, size_t n_out[/* n_ranges */]);
 /* All (key,count) pairs in unspecified order (the eager_iterator walk, JF/.../large_hash_iterator.hpp:28-65).
  * Pass cap = 0 to query *n_out only. */
 int katgpu_table_export(katgpu_table* t, uint64_t* keys, uint64_t* counts, size_t cap, size_t* n_out);

@@ -42,6 +42,7 @@ EXPORTS = (
     "katgpu_table_filter", "katgpu_table_seq_hits_host", "katgpu_table_seq_hits_device",
     "katgpu_table_record_stats_host", "katgpu_table_record_stats_device", "katgpu_table_jf_records_device",
     "katgpu_table_add_jf_records_device", "katgpu_jf_load_part",
+    "katgpu_table_record_regions_host", "katgpu_table_record_regions_device",
 )
 
 # katgpu_record_stats: one record of Table.record_stats
@@ -120,6 +121,8 @@ def load_library():
     L.katgpu_table_seq_hits_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp]
     L.katgpu_table_record_stats_host.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp]
     L.katgpu_table_record_stats_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp]
+    L.katgpu_table_record_regions_host.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp, C.c_uint32, vp, vp]
+    L.katgpu_table_record_regions_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp, C.c_uint32, vp, sz, vp]
     L.katgpu_hist.argtypes = [vp, u64, u64, u64, vp, sz]
     L.katgpu_gcp.argtypes = [vp, C.c_double, u32, vp]
     L.katgpu_comp.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, u32, u32, vp, vp, vp]
@@ -595,6 +598,40 @@ class Table:
         canon = self.canonical if canonicalise is None else canonicalise
         p = [getattr(x, "ptr", x) for x in (dev_bases, dev_rec_start, dev_rec_len, dev_out)]
         self.engine._chk(self.engine.L.katgpu_table_record_stats_device(self.h, p[0], n, p[1], p[2], n_rec, int(bool(canon)), p[3]))
+
+    def record_regions(self, bases, rec_start, rec_len, ranges, canonicalise=None):
+        """Count-range regions of records (katgpu_table_record_regions_host).  `ranges`: one or two (min, max) pairs, max == 0 for no
+        upper bound.  One (m, 3) u64 array per range: (record, start, stop) of every maximal run of windows whose count lies in the
+        range, start and stop counted from the record's first window, sorted by (record, start)."""
+        if isinstance(bases, str):
+            bases = bases.encode()
+        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
+        st, ln = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_len, np.uint64)
+        assert st.size == ln.size
+        rg = np.ascontiguousarray(ranges, np.uint64).reshape(-1, 2)
+        canon = self.canonical if canonicalise is None else canonicalise
+        p = C.c_void_p()
+        n_out = (C.c_size_t * max(rg.shape[0], 2))()
+        self.engine._chk(self.engine.L.katgpu_table_record_regions_host(self.h, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size,
+                                                                        int(bool(canon)), rg.ctypes.data, rg.shape[0], C.byref(p), n_out))
+        try:
+            total = sum(n_out[q] for q in range(rg.shape[0]))
+            flat = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), shape=(total * 3,)).copy() if total else np.zeros(0, np.uint64)
+        finally:
+            self.engine.L.katgpu_free_host(p)
+        cuts = np.cumsum([0] + [n_out[q] for q in range(rg.shape[0])])
+        return [flat[3 * cuts[q]:3 * cuts[q + 1]].reshape(-1, 3) for q in range(rg.shape[0])]
+
+    def record_regions_device(self, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, ranges, dev_regions, cap, canonicalise=None):
+        """Device-resident form: DeviceBuffers or raw device addresses; `dev_regions` takes `cap` regions of 24 bytes (None with cap 0:
+        count only).  Returns the true number of regions per range, whatever `cap`."""
+        canon = self.canonical if canonicalise is None else canonicalise
+        p = [getattr(x, "ptr", x) for x in (dev_bases, dev_rec_start, dev_rec_len, dev_regions)]
+        rg = np.ascontiguousarray(ranges, np.uint64).reshape(-1, 2)
+        n_out = (C.c_size_t * max(rg.shape[0], 2))()
+        self.engine._chk(self.engine.L.katgpu_table_record_regions_device(self.h, p[0], n, p[1], p[2], n_rec, int(bool(canon)), rg.ctypes.data,
+                                                                          rg.shape[0], p[3], cap, n_out))
+        return [int(n_out[q]) for q in range(rg.shape[0])]
 
     def export(self):
         n = C.c_size_t()

@@ -332,6 +332,7 @@ private:
     void recordScalars(Record& r, uint64_t nbNonZero, uint64_t nbInvalid, uint64_t gcBases, uint64_t nBases);
     void gcText(Record& r, const std::vector<int16_t>& gc);
     void regions(std::string& out, const Record& r, const uint64_t* counts, size_t nb, uint32_t min_count, uint32_t max_count);
+    void regionsText(std::string& out, const Record& r, const katgpu_region* rg, size_t n_rg, uint32_t min_count, uint32_t max_count);
     void merge();
     InputHandler input;
     std::string seqFile, outputPrefix;

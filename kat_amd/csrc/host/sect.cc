@@ -335,6 +335,27 @@ void Sect::regions(string& out, const Record& r, const uint64_t* cnt, size_t nb,
     }
 }
 
+// The bytes of regions() from the record's intervals as the device found them (katgpu_table_record_regions_host): rg[i] is the run
+// [start, stop) of window starts, in order.  A run that ends inside the record prints seq[start, stop) and then seq[stop + 1, stop + k - 1)
+// -- the base at `stop` is skipped, as in the reference -- and one that reaches the last window prints seq[start, nb + k - 1).
+void Sect::regionsText(string& out, const Record& r, const katgpu_region* rg, size_t n_rg, uint32_t min_count, uint32_t max_count) {
+    const string& seq = *r.seq;
+    const uint16_t k = input.merLen;
+    const size_t nb = seq.size() >= k ? seq.size() - k + 1 : 0;
+    const string maxcntstr = max_count > 0 ? string("-") + std::to_string(max_count) : "+";
+    for (size_t i = 0; i < n_rg; i++) {
+        const uint32_t start = (uint32_t)rg[i].start;
+        const size_t stop = (size_t)rg[i].stop;
+        const uint32_t end = (uint32_t)(stop + k - 1);
+        out += '>'; out += *r.name;
+        out += "___region:" + std::to_string((uint32_t)(i + 1)) + "_length:" + std::to_string((uint32_t)(end - start - 1)) + "_pos:" + std::to_string(start + 1) + ":" +
+               std::to_string(end) + "_cov:" + std::to_string(min_count) + maxcntstr + "\n";
+        out.append(seq, rg[i].start, stop - rg[i].start);
+        for (size_t q = stop == nb ? nb : stop + 1; q < end; q++) out += seq[q];
+        out += '\n';
+    }
+}
+
 void Sect::processSeqFile() {                                                                   // src/sect.cc:143-244
     PhaseTimer timer;
     cout << "Calculating kmer coverage across sequences ...";
@@ -358,7 +379,14 @@ void Sect::processSeqFile() {                                                   
     string joined;
     vector<uint64_t> counts, offs, lens;
     vector<katgpu_record_stats> stats;
-    const bool stats_only = noCountStats && !extractNR && !extractR;
+    // -n: nothing per position is written.  The device reduces the counts per record, and with -E / -F it finds the regions as well
+    const bool stats_only = noCountStats;
+    vector<katgpu_count_range> ranges;
+    if (stats_only && extractNR) ranges.push_back({1, minRepeat});
+    if (stats_only && extractR) ranges.push_back({minRepeat, maxRepeat});
+    katgpu_region* found = nullptr;
+    size_t n_found[2] = {0, 0};
+    vector<size_t> first_nr, first_r;                         // a record's regions: [first[i], first[i + 1]) of its range's
     // KATGPU_TIMING: where the phase's wall time goes (reader | joined buffer | device call | per-record host work | text), one line on stderr
     double t_part[5] = {0, 0, 0, 0, 0};
     auto lap = [&, t = std::chrono::steady_clock::now()](int part) mutable {
@@ -384,10 +412,21 @@ void Sect::processSeqFile() {                                                   
         offs.assign(n, 0);
         for (size_t i = 0; i < n; i++) { offs[i] = joined.size(); joined += seqs[i]; joined += '\n'; }   // a newline can never be in a record
         lap(1);
-        if (stats_only) {                                     // nothing per position is written: the device reduces the counts per record
+        if (stats_only) {
             lens.resize(n); stats.resize(n);
             for (size_t i = 0; i < n; i++) lens[i] = seqs[i].size();
             Engine::check(katgpu_table_record_stats_host(input.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, input.canonical ? 1 : 0, stats.data()));
+            if (!ranges.empty()) {
+                Engine::check(katgpu_table_record_regions_host(input.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, input.canonical ? 1 : 0,
+                                                               ranges.data(), (uint32_t)ranges.size(), &found, n_found));
+                auto index = [&](vector<size_t>& first, const katgpu_region* rg, size_t m) {      // the regions come sorted by record
+                    first.assign(n + 1, 0);
+                    for (size_t i = 0; i < m; i++) first[rg[i].record + 1]++;
+                    for (size_t i = 0; i < n; i++) first[i + 1] += first[i];
+                };
+                if (extractNR) index(first_nr, found, n_found[0]);
+                if (extractR) index(first_r, found + (extractNR ? n_found[0] : 0), n_found[extractNR ? 1 : 0]);
+            }
         } else {
             if (counts.size() < joined.size()) counts.resize(joined.size());
             Engine::check(katgpu_table_profile_host(input.hash, joined.data(), joined.size(), input.canonical ? 1 : 0, counts.data()));
@@ -398,7 +437,13 @@ void Sect::processSeqFile() {                                                   
         for (size_t i = 0; i < n; i++) { recs[i].name = &names[i]; recs[i].seq = &seqs[i]; }
         const unsigned workers = std::max<unsigned>(1, std::min<unsigned>(threads, (unsigned)n));
         auto work = [&](unsigned th) {                                                          // processInterlaced, :477-483
-            for (size_t i = th; i < n; i += workers) { if (stats_only) processSeqStats(recs[i], stats[i]); else processSeq(recs[i], counts.data() + offs[i]); }
+            for (size_t i = th; i < n; i += workers) {
+                if (!stats_only) { processSeq(recs[i], counts.data() + offs[i]); continue; }
+                processSeqStats(recs[i], stats[i]);
+                const katgpu_region* r_found = found + (extractNR ? n_found[0] : 0);
+                if (extractNR) regionsText(recs[i].nr_txt, recs[i], found + first_nr[i], first_nr[i + 1] - first_nr[i], 1, minRepeat);
+                if (extractR) regionsText(recs[i].r_txt, recs[i], r_found + first_r[i], first_r[i + 1] - first_r[i], minRepeat, maxRepeat);
+            }
         };
         if (workers == 1) work(0);
         else {
@@ -406,6 +451,8 @@ void Sect::processSeqFile() {                                                   
             for (unsigned th = 0; th < workers; th++) team.emplace_back(work, th);
             for (auto& t : team) t.join();
         }
+        katgpu_free_host(found);
+        found = nullptr;
 
         lap(3);
         char line[512];

@@ -1,11 +1,12 @@
 // kg_query.hip -- a sequence or keys against a table, which is left as it is: batch lookups (katgpu_table_get*), per-position profiles
-// (katgpu_table_profile_*), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*) and the per-record coverage statistics
-// of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*).  The host forms send their input through the device in batches.
+// (katgpu_table_profile_*), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*), the per-record coverage statistics
+// of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*) and the count-range regions of `kat sect -n -E / -F` (katgpu_table_record_regions_*).  The host forms send their input through the device in batches.
 #include "kg_host.hpp"
 #include "kg_kernels.hpp"
 #include "kg_wide.hpp"
 #include "kg_filter.hpp"
 #include "kg_record_stats.hpp"
+#include "kg_record_regions.hpp"
 
 static const bool g_forbid_profile_host = hook_u64("KATGPU_TEST_FORBID_PROFILE_HOST", 0) != 0;   // tests: a driver that should not need per-position counts asks for none
 static const size_t g_profile_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_PROFILE_BATCH", (uint64_t)32 << 20), 1);   // tests: window starts per batch of profile_host
@@ -271,4 +272,158 @@ extern "C" int katgpu_table_record_stats_host(katgpu_table* t, const char* bases
         return e == hipSuccess ? KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "record stats: %s", hipGetErrorString(e));
     });
     return no_room ? fail(c, KATGPU_ERR_NOMEM, "record statistics: no %zu bytes of device memory for a batch of bases", no_room) : rc;
+}
+
+// ------------------------------------------------------------------ count-range regions of records (kat sect -n -E / -F) ----
+
+static const size_t g_regions_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_REGIONS_BATCH", (uint64_t)32 << 20), 1);   // tests: bases per batch of the host form
+static_assert(sizeof(katgpu_region) == RG_FIELDS * sizeof(uint64_t), "the kernels write a region as three words");
+
+// the workspace of one call or batch of n bases: first-window mask | a mask per range | two counters per range and mask block | a total per range
+struct RegionsWork {
+    DevBuf buf;
+    size_t bytes = 0;
+    uint64_t n_words = 0, n_blk = 0;
+    uint64_t* masks = nullptr;
+    unsigned long long *cnt = nullptr, *totals = nullptr;
+    int fit(katgpu_ctx* c, size_t n, uint32_t n_ranges) {
+        n_words = (n + 63) / 64; n_blk = (n_words + RG_BLOCK - 1) / RG_BLOCK;
+        const size_t cnt_off = (1 + n_ranges) * n_words * 8, tot_off = cnt_off + n_ranges * n_blk * 16, need = tot_off + RG_MAX_RANGES * 8;
+        if (need > bytes) {
+            bytes = 0;
+            if (buf.pooled(c, need) != hipSuccess)
+                return fail(c, KATGPU_ERR_NOMEM, "record regions: no %zu bytes of device memory for the masks of %zu bases", need, n);
+            bytes = need;
+        }
+        uint8_t* w = buf.as<uint8_t>();
+        masks = (uint64_t*)w; cnt = (unsigned long long*)(w + cnt_off); totals = (unsigned long long*)(w + tot_off);
+        return KATGPU_OK;
+    }
+};
+
+static bool regions_args(const katgpu_count_range* ranges, uint32_t n_ranges, RgRanges& rg) {
+    if (!ranges || n_ranges < 1 || n_ranges > RG_MAX_RANGES) return false;
+    rg = RgRanges{{0, 0}, {0, 0}, n_ranges};
+    for (uint32_t q = 0; q < n_ranges; ++q) { rg.min[q] = ranges[q].min; rg.max[q] = ranges[q].max; }
+    return true;
+}
+
+// On the stream: K14 over the chunks of the n bases (n != 0), K15 and K16 over the masks; w.totals then holds the regions of every range.
+static int launch_regions_find(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec,
+                               int canonicalise, const RgRanges& rg, RegionsWork& w) {
+    katgpu_ctx* c = t->ctx;
+    const DevTable& d = t->dev();
+    const bool wide = d.keys_b != nullptr;
+    ScopedTimer tm(c, KATGPU_K_PROFILE, n >= d.k ? n - d.k + 1 : 0);
+    launch_aligned_wide(c, aligned16(dev_bases), wide, w.n_words * 64, chunk_starts(wide), [&](auto A, auto W, dim3 grid, uint64_t n_chunks) {
+        hipLaunchKernelGGL((k_regions_mask<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, d, t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, rg, w.n_words, (uint16_t*)w.masks);
+    });
+    const dim3 grid((unsigned)std::min<uint64_t>(w.n_blk, (uint64_t)c->n_cu * 8));
+    hipLaunchKernelGGL(k_regions_count, grid, dim3(RG_BLOCK), 0, c->stream, w.masks, w.n_words, w.n_blk, rg.n, w.cnt);
+    hipLaunchKernelGGL(k_regions_scan, dim3(1), dim3(RG_SCAN_BLOCK), 0, c->stream, w.cnt, w.n_blk, rg.n, w.totals);
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+// K17 behind it: the first `cap` regions to dev_regions, their records numbered from rec_base
+static int launch_regions_emit(katgpu_table* t, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec, uint64_t rec_base, const RgRanges& rg,
+                               const RegionsWork& w, katgpu_region* dev_regions, size_t cap) {
+    katgpu_ctx* c = t->ctx;
+    if (!cap) return KATGPU_OK;
+    ScopedTimer tm(c, KATGPU_K_PROFILE, 0);
+    const dim3 grid((unsigned)std::min<uint64_t>(w.n_blk, (uint64_t)c->n_cu * 8));
+    hipLaunchKernelGGL(k_regions_emit, grid, dim3(RG_BLOCK), 0, c->stream, w.masks, w.n_words, w.n_blk, rg.n, w.cnt, dev_start, dev_len, (uint64_t)n_rec, rec_base, (unsigned long long*)dev_regions, (uint64_t)cap);
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+extern "C" int katgpu_table_record_regions_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                                  const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, const katgpu_count_range* ranges,
+                                                  uint32_t n_ranges, katgpu_region* dev_regions, size_t cap, size_t n_out[]) {
+    RgRanges rg;
+    if (!t || !n_out || (n_rec && (!dev_rec_start || !dev_rec_len)) || (n && !dev_bases) || (cap && !dev_regions)) return KATGPU_ERR_INVALID_ARG;
+    katgpu_ctx* c = t->ctx;
+    if (!regions_args(ranges, n_ranges, rg)) return fail(c, KATGPU_ERR_INVALID_ARG, "record regions: one or two count ranges, not %u", ranges ? n_ranges : 0);
+    for (uint32_t q = 0; q < n_ranges; ++q) n_out[q] = 0;
+    if (!n_rec || !n) return KATGPU_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    RegionsWork w;
+    rc = w.fit(c, n, n_ranges); if (rc) return rc;
+    rc = launch_regions_find(t, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, canonicalise, rg, w);
+    if (!rc) rc = launch_regions_emit(t, dev_rec_start, dev_rec_len, n_rec, 0, rg, w, dev_regions, cap);
+    unsigned long long totals[RG_MAX_RANGES] = {0, 0};
+    hipError_t e = hipMemcpyAsync(totals, w.totals, n_ranges * 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "record regions: %s", hipGetErrorString(e));
+    for (uint32_t q = 0; q < n_ranges; ++q) n_out[q] = (size_t)totals[q];
+    return KATGPU_OK;
+}
+
+// Host form: the records go through the device in batches of at most g_regions_batch bases and 2^20 records (for_record_batches), so any
+// input fits next to the table.  Per batch the totals come back first, then room for that many regions is found and K17 fills it; the
+// regions of a batch carry the records' indices in the whole call.
+extern "C" int katgpu_table_record_regions_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                                                size_t n_rec, int canonicalise, const katgpu_count_range* ranges, uint32_t n_ranges,
+                                                katgpu_region** regions, size_t n_out[]) {
+    RgRanges rg;
+    if (!t || !regions || !n_out || (n_rec && (!rec_start || !rec_len)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    katgpu_ctx* c = t->ctx;
+    if (!regions_args(ranges, n_ranges, rg)) return fail(c, KATGPU_ERR_INVALID_ARG, "record regions: one or two count ranges, not %u", ranges ? n_ranges : 0);
+    *regions = nullptr;
+    for (uint32_t q = 0; q < n_ranges; ++q) n_out[q] = 0;
+    std::vector<katgpu_region> found[RG_MAX_RANGES];
+    if (n_rec) {
+        int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;
+        HIPCHK(c, hipSetDevice(c->device));
+        rc = refresh_counters(t); if (rc) return rc;
+        const size_t max_recs = std::min(n_rec, (size_t)1 << 20);
+        DevBuf recs, out;                                          // start and length of every record of a batch; the regions of a batch
+        size_t out_cap = 0;
+        if (recs.pooled(c, max_recs * 2 * sizeof(uint64_t)) != hipSuccess)
+            return fail(c, KATGPU_ERR_NOMEM, "record regions: no device memory for the records of a batch");
+        uint64_t* dr = recs.as<uint64_t>();
+        RegionsWork w;
+        size_t no_room = 0;
+        rc = for_record_batches(c, bases, n, rec_start, rec_len, n_rec, g_regions_batch, max_recs, dr, dr + max_recs, "record regions", &no_room,
+                                [](size_t, bool) { return true; },
+                                [&](const uint8_t* db, size_t nb, const uint64_t* ds, const uint64_t* dl, size_t m, size_t r0) {
+            if (!nb) return (int)KATGPU_OK;
+            int rc = w.fit(c, nb, n_ranges); if (rc) return rc;
+            rc = launch_regions_find(t, db, nb, ds, dl, m, canonicalise, rg, w); if (rc) return rc;
+            unsigned long long totals[RG_MAX_RANGES] = {0, 0};
+            hipError_t e = hipMemcpyAsync(totals, w.totals, n_ranges * 8, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "record regions: %s", hipGetErrorString(e));
+            const size_t total = (size_t)(totals[0] + totals[1]);
+            if (!total) return (int)KATGPU_OK;
+            if (total > out_cap) {
+                out_cap = 0;
+                if (out.pooled(c, total * sizeof(katgpu_region)) != hipSuccess)
+                    return fail(c, KATGPU_ERR_NOMEM, "record regions: no %zu bytes of device memory for the %zu regions of a batch", total * sizeof(katgpu_region), total);
+                out_cap = total;
+            }
+            katgpu_region* d_out = out.as<katgpu_region>();
+            rc = launch_regions_emit(t, ds, dl, m, r0, rg, w, d_out, total); if (rc) return rc;
+            for (uint32_t q = 0; q < n_ranges && e == hipSuccess; ++q) {    // (the vectors grow before the copies are queued and rest until the batch's synchronize)
+                const size_t have = found[q].size();
+                found[q].resize(have + (size_t)totals[q]);
+                if (totals[q]) e = hipMemcpyAsync(found[q].data() + have, d_out + (q ? totals[0] : 0), (size_t)totals[q] * sizeof(katgpu_region), hipMemcpyDeviceToHost, c->stream);
+            }
+            return e == hipSuccess ? (int)KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "record regions: %s", hipGetErrorString(e));
+        });
+        if (no_room) return fail(c, KATGPU_ERR_NOMEM, "record regions: no %zu bytes of device memory for a batch of bases", no_room);
+        if (rc) return rc;
+    }
+    const size_t total = found[0].size() + found[1].size();
+    katgpu_region* res = (katgpu_region*)malloc(std::max<size_t>(total, 1) * sizeof(katgpu_region));
+    if (!res) return fail(c, KATGPU_ERR_NOMEM, "record regions: no host memory for %zu regions", total);
+    size_t at = 0;
+    for (uint32_t q = 0; q < n_ranges; ++q) {
+        if (!found[q].empty()) memcpy(res + at, found[q].data(), found[q].size() * sizeof(katgpu_region));
+        at += found[q].size(); n_out[q] = found[q].size();
+    }
+    *regions = res;
+    return KATGPU_OK;
 }
