@@ -270,11 +270,20 @@ const char* katgpu_jf_last_error(void);
    ((pos, kmer) ascending), packed as binary_writer writes them (ceil(2k/8) key bytes + 4 count bytes, count saturated),
    into device memory.  cols: the 2k columns of M as katgpu_jf_write_records stores them in "matrix1" (host pointer).
    dev_out == NULL or cap_records == 0: only *n_out (how many records the range holds) is set.
-   Needs 1 <= r <= min(2k, 63) and pos_lo <= pos_hi <= 2^r, else KATGPU_ERR_INVALID_ARG; k > 32: KATGPU_ERR_K.
+   Needs 1 <= r <= min(2k, 63) and pos_lo <= pos_hi <= 2^r, else KATGPU_ERR_INVALID_ARG; k > 32: KATGPU_ERR_K (use the _wide entry below).
    A buffer too small for the range is KATGPU_ERR_INVALID_ARG, with *n_out set; so is a matrix that sends more than 2^16 records
    of the range to one stretch of positions (M is expected to spread the table, as a header's matrix does).  katgpu_jf_dump is built on this. */
 int katgpu_table_jf_records_device(katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t pos_lo, uint64_t pos_hi,
                                    uint8_t* dev_out, size_t cap_records, size_t* n_out);
+/* The same for a wide table (33 <= k <= KATGPU_MAX_K): the order sorted_dumper::_dump emits
+   (JF/include/jellyfish/sorted_dumper.hpp:80-112) with k-mers compared as multi-word mer_dna::operator< compares them (the 2k-bit word,
+   i.e. (hi, lo), ascending and unsigned), and the bytes binary_writer::write writes (binary_dumper.hpp:47-51): ceil(2k/8) = 9 .. 16
+   key bytes -- the 8 of lo, then the low ones of hi -- + 4 count bytes, count saturated.  cols: the 2k columns of "matrix1"; bit i
+   of the 2k-bit k-mer selects column 2k-1-i.  Needs 1 <= r <= 63 and pos_lo <= pos_hi <= 2^r, else KATGPU_ERR_INVALID_ARG; counting
+   only, a buffer too small and a matrix that does not spread the table are as above.  k <= 32: KATGPU_ERR_K.  katgpu_jf_dump of a
+   wide table is built on this. */
+int katgpu_table_jf_records_device_wide(katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t pos_lo, uint64_t pos_hi,
+                                        uint8_t* dev_out, size_t cap_records, size_t* n_out);
 /* n_records packed .jf records (ceil(key_len/8) key bytes + counter_len count bytes each, little endian) held in DEVICE memory at any
  * byte alignment are added to t: hash->add(key, val) per record.  Exact 64-bit sums; a zero count adds nothing; key bits above key_len
  * are ignored.  key_len != 2k of the table: KATGPU_ERR_MISMATCH; counter_len outside 1..8: KATGPU_ERR_INVALID_ARG.  The table grows

@@ -40,7 +40,7 @@ EXPORTS = (
     "katgpu_comm_transport_note", "katgpu_comm_distinct_devices", "katgpu_comm_barrier", "katgpu_exchange_merge", "katgpu_allreduce_u64", "katgpu_comm_stats",
     "katgpu_table_packed_records", "katgpu_table_extract_packed", "katgpu_table_merge_regions_packed", "katgpu_comm_wire", "katgpu_exchange_begin", "katgpu_exchange_finish",
     "katgpu_table_filter", "katgpu_table_seq_hits_host", "katgpu_table_seq_hits_device",
-    "katgpu_table_record_stats_host", "katgpu_table_record_stats_device", "katgpu_table_jf_records_device",
+    "katgpu_table_record_stats_host", "katgpu_table_record_stats_device", "katgpu_table_jf_records_device", "katgpu_table_jf_records_device_wide",
     "katgpu_table_add_jf_records_device", "katgpu_jf_load_part",
     "katgpu_table_record_regions_host", "katgpu_table_record_regions_device",
 )
@@ -170,6 +170,7 @@ def load_library():
     L.katgpu_jf_read_records_wide.argtypes = [C.c_char_p, C.POINTER(u32), C.POINTER(C.c_int), pp, pp, pp, C.POINTER(sz)]
     L.katgpu_jf_last_error.restype = C.c_char_p
     L.katgpu_table_jf_records_device.argtypes = [vp, u32, vp, u64, u64, vp, sz, C.POINTER(sz)]
+    L.katgpu_table_jf_records_device_wide.argtypes = [vp, u32, vp, u64, u64, vp, sz, C.POINTER(sz)]
     L.katgpu_table_add_jf_records_device.argtypes = [vp, vp, sz, u32, u32]
     L.katgpu_jf_load_part.argtypes = [vp, C.c_char_p, u32, u32, pp]
     _lib = L
@@ -687,15 +688,15 @@ class Table:
         if rc:
             raise KatGpuError(rc, self.engine.L.katgpu_jf_last_error().decode(errors="replace") or self.engine.L.katgpu_last_error(self.engine.h).decode(errors="replace"))
 
-    def jf_records(self, r, cols, pos_lo=0, pos_hi=None, count_only=False):
+    def jf_records(self, r, cols, pos_lo=0, pos_hi=None, count_only=False, _entry="katgpu_table_jf_records_device"):
         """The packed .jf records whose position under the matrix `cols` (2k columns of r bits, a header's "matrix1") lies in
         [pos_lo, pos_hi), in file order (katgpu_table_jf_records_device): a uint8 array of n * (ceil(2k/8) + 4) bytes, or n alone."""
         cc = np.ascontiguousarray(cols, np.uint64)
         assert cc.size == 2 * self.k
         hi = (1 << r) if pos_hi is None else pos_hi
         n = C.c_size_t()
-        L = self.engine.L
-        self.engine._chk(L.katgpu_table_jf_records_device(self.h, r, cc.ctypes.data, pos_lo, hi, None, 0, C.byref(n)))
+        entry = getattr(self.engine.L, _entry)
+        self.engine._chk(entry(self.h, r, cc.ctypes.data, pos_lo, hi, None, 0, C.byref(n)))
         if count_only:
             return n.value
         rb = (2 * self.k + 7) // 8 + 4
@@ -703,10 +704,14 @@ class Table:
             return np.zeros(0, np.uint8)
         buf = self.engine.alloc(n.value * rb)
         try:
-            self.engine._chk(L.katgpu_table_jf_records_device(self.h, r, cc.ctypes.data, pos_lo, hi, buf.ptr, n.value, C.byref(n)))
+            self.engine._chk(entry(self.h, r, cc.ctypes.data, pos_lo, hi, buf.ptr, n.value, C.byref(n)))
             return buf.download(np.uint8, n.value * rb)
         finally:
             buf.free()
+
+    def jf_records_wide(self, r, cols, pos_lo=0, pos_hi=None, count_only=False):
+        """jf_records for a wide table (katgpu_table_jf_records_device_wide): a record's 9 to 16 key bytes are those of lo, then of hi."""
+        return self.jf_records(r, cols, pos_lo, pos_hi, count_only, _entry="katgpu_table_jf_records_device_wide")
 
     def add_jf_records(self, raw, key_len, counter_len, offset=0):
         """Packed .jf records (a uint8 array, ceil(key_len/8) + counter_len bytes each) added to the table on the device

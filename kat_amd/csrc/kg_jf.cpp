@@ -1,5 +1,5 @@
-// kg_jf.cpp -- Jellyfish "binary/sorted" hash files (.jf): reader and writer.  Pure host code; the records of a k <= 32 table's dump
-// are ordered and packed on the device (kg_jf_records.hpp, jf_stream_records in kg_jf_device.hip), and the records of a file being loaded
+// kg_jf.cpp -- Jellyfish "binary/sorted" hash files (.jf): reader and writer.  Pure host code; the records of a table's dump, at either
+// key width, are ordered and packed on the device (kg_jf_records.hpp, jf_stream_records in kg_jf_device.hip), and the records of a file being loaded
 // are unpacked and added there (kg_jf_load.hpp, jf_stream_load in kg_jf_device.hip).
 //
 // Replaces JellyfishHelper::dumpHash / HashLoader::loadHash (lib/src/jellyfish_helper.cc:248-256,97-187) and the parts
@@ -362,14 +362,8 @@ extern "C" int katgpu_jf_load(katgpu_ctx* ctx, const char* path, katgpu_table** 
 extern "C" int katgpu_jf_dump(katgpu_table* t, const char* path) {
     if (!t || !path) return KATGPU_ERR_INVALID_ARG;
     size_t n = 0;
-    if (katgpu_table_k(t) > 32) {
-        int rc = katgpu_table_export_wide(t, nullptr, nullptr, nullptr, 0, &n);
-        if (rc) return rc;
-        std::vector<uint64_t> hi(std::max<size_t>(n, 1)), lo(std::max<size_t>(n, 1)), counts(std::max<size_t>(n, 1));
-        if (n) { rc = katgpu_table_export_wide(t, hi.data(), lo.data(), counts.data(), n, &n); if (rc) return rc; }
-        return katgpu_jf_write_records_wide(path, katgpu_table_k(t), katgpu_table_canonical(t), hi.data(), lo.data(), counts.data(), n);
-    }
-    int rc = katgpu_table_export(t, nullptr, nullptr, 0, &n);
+    const bool wide = katgpu_table_k(t) > 32;
+    int rc = wide ? katgpu_table_export_wide(t, nullptr, nullptr, nullptr, 0, &n) : katgpu_table_export(t, nullptr, nullptr, 0, &n);
     if (rc) return rc;
     {   // the records come off the device in file order, range of positions by range; the host holds two pinned buffers of them
         const uint32_t k = katgpu_table_k(t);
@@ -394,6 +388,11 @@ extern "C" int katgpu_jf_dump(katgpu_table* t, const char* path) {
         }
     }
     // no device scratch to be had: the records to the host, ordered and packed there
+    if (wide) {
+        std::vector<uint64_t> hi(std::max<size_t>(n, 1)), lo(std::max<size_t>(n, 1)), counts(std::max<size_t>(n, 1));
+        if (n) { rc = katgpu_table_export_wide(t, hi.data(), lo.data(), counts.data(), n, &n); if (rc) return rc; }
+        return katgpu_jf_write_records_wide(path, katgpu_table_k(t), katgpu_table_canonical(t), hi.data(), lo.data(), counts.data(), n);
+    }
     std::vector<uint64_t> keys(std::max<size_t>(n, 1)), counts(std::max<size_t>(n, 1));
     if (n) { rc = katgpu_table_export(t, keys.data(), counts.data(), n, &n); if (rc) return rc; }
     return katgpu_jf_write_records(path, katgpu_table_k(t), katgpu_table_canonical(t), keys.data(), counts.data(), n);

@@ -1,5 +1,5 @@
 // kg_jf_device.hip -- the device side of the .jf writer and reader (kg_jf.cpp): a table's records selected, ordered by their position in
-// the file and packed (katgpu_table_jf_records_device; jf_stream_records, range by range into a file), and packed records unpacked and
+// the file and packed (katgpu_table_jf_records_device[_wide]; jf_stream_records, range by range into a file), and packed records unpacked and
 // added to a table (katgpu_table_add_jf_records_device; jf_stream_load, chunk by chunk out of a file).
 #include "kg_host.hpp"
 #include "kg_jf_records.hpp"
@@ -19,7 +19,7 @@ namespace {
 // device scratch of the record producer, kept across the ranges of one dump
 struct JfScratch {
     uint32_t* hist = nullptr; size_t nb_cap = 0;         // hist[nb_cap], cursor[nb_cap], off[nb_cap + 1]
-    uint64_t* recs = nullptr; size_t rec_cap = 0;        // pos[rec_cap], key[rec_cap], then 32-bit counts: 20 bytes per record
+    uint64_t* recs = nullptr; size_t rec_cap = 0;        // pos[rec_cap], (wide: hi[rec_cap],) key[rec_cap], then 32-bit counts: jf_scratch_bytes per record
     uint32_t* rank = nullptr; size_t rank_cap = 0;       // buckets beyond one LDS tile only
     ~JfScratch() { hipFree(hist); hipFree(recs); hipFree(rank); }
     template <typename T>
@@ -32,14 +32,20 @@ struct JfScratch {
     }
 };
 struct JfRange { uint64_t lo, hi, n; };
+template <bool W> constexpr size_t jf_scratch_bytes = W ? 28 : 20;
 }
 
 // the columns of M ("matrix1": bit i of the k-mer selects column 2k-1-i) as rows over the key bits
-static JfRows jf_rows(uint32_t k, uint32_t r, const uint64_t* cols) {
-    JfRows m{};
+template <bool W>
+static JfRows<W> jf_rows(uint32_t k, uint32_t r, const uint64_t* cols) {
+    JfRows<W> m{};
     const uint32_t c = 2 * k;
     for (uint32_t j = 0; j < r; ++j)
-        for (uint32_t i = 0; i < c; ++i) m.row[j] |= ((cols[c - 1 - i] >> j) & 1ULL) << i;
+        for (uint32_t i = 0; i < c; ++i) {
+            const uint64_t bit = (cols[c - 1 - i] >> j) & 1ULL;
+            if (i < 64) m.row[j] |= bit << i;
+            else if constexpr (W) m.row_hi[j] |= bit << (i - 64);
+        }
     return m;
 }
 
@@ -50,15 +56,17 @@ static uint32_t jf_bucket_shift(uint64_t distinct, uint32_t r) {
     return s;
 }
 
-static void jf_launch_select_hist(katgpu_table* t, const JfRows& m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift, uint32_t* hist) {
+template <bool W>
+static void jf_launch_select_hist(katgpu_table* t, const JfRows<W>& m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift, uint32_t* hist) {
     katgpu_ctx* c = t->ctx;
-    hipLaunchKernelGGL(k_jf_select<0>, dim3(grid_for(c, t->dev().cap + 1, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, t->dev(), t->n_ovf, m, r, pos_lo, pos_hi, shift,
-                       hist, (unsigned long long*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
+    hipLaunchKernelGGL((k_jf_select<0, W>), dim3(grid_for(c, t->dev().cap + 1, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, t->dev(), t->n_ovf, m, r, pos_lo, pos_hi, shift,
+                       hist, (unsigned long long*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
 }
 
 // Select, order and pack the records of [pos_lo, pos_hi) into dev_out (room for `cap` records).  Synchronises once, to learn how many
 // the range holds (*n_out); the scatter, the sort and the pack are left running on the compute stream.
-static int jf_range(katgpu_table* t, const JfRows& m, uint32_t r, uint32_t shift, uint64_t pos_lo, uint64_t pos_hi, uint8_t* dev_out, size_t cap,
+template <bool W>
+static int jf_range(katgpu_table* t, const JfRows<W>& m, uint32_t r, uint32_t shift, uint64_t pos_lo, uint64_t pos_hi, uint8_t* dev_out, size_t cap,
                     size_t* n_out, JfScratch& s) {
     katgpu_ctx* c = t->ctx;
     *n_out = 0;
@@ -81,13 +89,13 @@ static int jf_range(katgpu_table* t, const JfRows& m, uint32_t r, uint32_t shift
     if (h[0] > cap) return fail(c, KATGPU_ERR_INVALID_ARG, "jf records: the range holds %llu records, the buffer %zu", h[0], cap);
     if (h[0] >= (1ULL << 31)) return fail(c, KATGPU_ERR_INVALID_ARG, "jf records: %llu records in one range: ask for a narrower one", h[0]);
     const size_t n = (size_t)h[0];
-    if (!s.ensure(c, s.recs, s.rec_cap, n, n * 20)) return fail(c, KATGPU_ERR_NOMEM, "jf records: no device memory to order %zu records", n);
-    uint64_t *d_pos = s.recs, *d_key = s.recs + s.rec_cap;
-    uint32_t* d_cnt = (uint32_t*)(s.recs + 2 * s.rec_cap);
+    if (!s.ensure(c, s.recs, s.rec_cap, n, n * jf_scratch_bytes<W>)) return fail(c, KATGPU_ERR_NOMEM, "jf records: no device memory to order %zu records", n);
+    uint64_t *d_pos = s.recs, *d_hi = W ? s.recs + s.rec_cap : nullptr, *d_key = s.recs + (W ? 2 : 1) * s.rec_cap;
+    uint32_t* d_cnt = (uint32_t*)(d_key + s.rec_cap);
     const uint32_t key_bytes = (2 * dv.k + 7) / 8;
     // (none of these launches is booked under a kernel class of katgpu_profile_get: the dump reports its own phases, katgpu_timing "jf_dump")
-    hipLaunchKernelGGL(k_jf_select<1>, dim3(grid_for(c, dv.cap + 1, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, dv, t->n_ovf, m, r, pos_lo, pos_hi, shift,
-                       cursor, (unsigned long long*)nullptr, d_pos, d_key, d_cnt);
+    hipLaunchKernelGGL((k_jf_select<1, W>), dim3(grid_for(c, dv.cap + 1, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, dv, t->n_ovf, m, r, pos_lo, pos_hi, shift,
+                       cursor, (unsigned long long*)nullptr, d_pos, d_hi, d_key, d_cnt);
     // The ranking path compares every record of an oversized bucket with the whole bucket.  That is for the odd run of equal positions,
     // not for a matrix that piles a table onto a few of them: beyond JF_RANK_MAX records in one bucket the range is refused.
     if (h[1] > JF_RANK_MAX)
@@ -95,17 +103,16 @@ static int jf_range(katgpu_table* t, const JfRows& m, uint32_t r, uint32_t shift
                     h[1], shift, JF_RANK_MAX);
     if (h[1] > JF_TILE) {
         if (!s.ensure(c, s.rank, s.rank_cap, n, n * sizeof(uint32_t))) return fail(c, KATGPU_ERR_NOMEM, "jf records: no device memory to rank %zu records", n);
-        hipLaunchKernelGGL(k_jf_rank, dim3(grid_for(c, n, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, d_pos, d_key, (uint32_t)n, pos_lo, shift, off, s.rank);
+        hipLaunchKernelGGL(k_jf_rank<W>, dim3(grid_for(c, n, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, d_pos, d_hi, d_key, (uint32_t)n, pos_lo, shift, off, s.rank);
     }
-    hipLaunchKernelGGL(k_jf_sort_pack, dim3(std::min<uint32_t>(nb, (uint32_t)c->n_cu * 5)), dim3(JF_BLOCK), 0, c->stream, d_pos, d_key, d_cnt, off, s.rank, nb, key_bytes, dev_out);
+    hipLaunchKernelGGL(k_jf_sort_pack<W>, dim3(std::min<uint32_t>(nb, (uint32_t)c->n_cu * 5)), dim3(JF_BLOCK), 0, c->stream, d_pos, d_hi, d_key, d_cnt, off, s.rank, nb, key_bytes, dev_out);
     HIPCHK(c, hipGetLastError());
     return KATGPU_OK;
 }
 
-extern "C" int katgpu_table_jf_records_device(katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t pos_lo, uint64_t pos_hi,
-                                              uint8_t* dev_out, size_t cap_records, size_t* n_out) {
-    if (!t || !cols || !n_out) return KATGPU_ERR_INVALID_ARG;
-    NARROW_ONLY(t, "katgpu_table_jf_records_device");
+// the entry point of either key width, once the table is known to be of that width
+template <bool W>
+static int jf_records_device(katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t pos_lo, uint64_t pos_hi, uint8_t* dev_out, size_t cap_records, size_t* n_out) {
     katgpu_ctx* c = t->ctx;
     const uint32_t k = t->dv.k;
     if (r < 1 || r > std::min<uint32_t>(2 * k, 63) || pos_lo > pos_hi || pos_hi > (1ULL << r))
@@ -113,12 +120,12 @@ extern "C" int katgpu_table_jf_records_device(katgpu_table* t, uint32_t r, const
     HIPCHK(c, hipSetDevice(c->device));
     int rc = refresh_counters(t); if (rc) return rc;
     *n_out = 0;
-    const JfRows m = jf_rows(k, r, cols);
+    const JfRows<W> m = jf_rows<W>(k, r, cols);
     if (!dev_out || !cap_records) {
         unsigned long long* total = (unsigned long long*)&t->dev().ctrs[CTR_SCRATCH];
         HIPCHK(c, hipMemsetAsync(total, 0, sizeof(uint64_t), c->stream));
-        hipLaunchKernelGGL(k_jf_select<2>, dim3(grid_for(c, t->dev().cap + 1, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, t->dev(), t->n_ovf, m, r, pos_lo, pos_hi, 0u,
-                           (uint32_t*)nullptr, total, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
+        hipLaunchKernelGGL((k_jf_select<2, W>), dim3(grid_for(c, t->dev().cap + 1, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, t->dev(), t->n_ovf, m, r, pos_lo, pos_hi, 0u,
+                           (uint32_t*)nullptr, total, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
         unsigned long long h = 0;
         HIPCHK(c, hipMemcpyAsync(&h, total, sizeof h, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -132,16 +139,31 @@ extern "C" int katgpu_table_jf_records_device(katgpu_table* t, uint32_t r, const
     return rc;
 }
 
+extern "C" int katgpu_table_jf_records_device(katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t pos_lo, uint64_t pos_hi,
+                                              uint8_t* dev_out, size_t cap_records, size_t* n_out) {
+    if (!t || !cols || !n_out) return KATGPU_ERR_INVALID_ARG;
+    NARROW_ONLY(t, "katgpu_table_jf_records_device: use katgpu_table_jf_records_device_wide;");
+    return jf_records_device<false>(t, r, cols, pos_lo, pos_hi, dev_out, cap_records, n_out);
+}
+
+extern "C" int katgpu_table_jf_records_device_wide(katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t pos_lo, uint64_t pos_hi,
+                                                   uint8_t* dev_out, size_t cap_records, size_t* n_out) {
+    if (!t || !cols || !n_out) return KATGPU_ERR_INVALID_ARG;
+    if (!t->dv.keys_b) return fail(t->ctx, KATGPU_ERR_K, "katgpu_table_jf_records_device_wide is for k > 32 tables (k = %u): use katgpu_table_jf_records_device", t->dv.k);
+    return jf_records_device<true>(t, r, cols, pos_lo, pos_hi, dev_out, cap_records, n_out);
+}
+
 static const uint64_t g_jf_range_records = hook_u64("KATGPU_JF_RANGE_RECORDS", 0);   // tests: many ranges at tiny sizes
 
-int jf_stream_records(katgpu_table* t, uint32_t r, const uint64_t* cols, FILE* f, JfDumpTiming* tm) {
+template <bool W>
+static int jf_stream(katgpu_table* t, uint32_t r, const uint64_t* cols, FILE* f, JfDumpTiming* tm) {
     katgpu_ctx* c = t->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = refresh_counters(t); if (rc) return rc;
     const uint64_t distinct = t->distinct;
     if (!distinct) return KATGPU_OK;
     const uint32_t k = t->dev().k, rb = (2 * k + 7) / 8 + 4;
-    const JfRows m = jf_rows(k, r, cols);
+    const JfRows<W> m = jf_rows<W>(k, r, cols);
     const uint32_t shift = jf_bucket_shift(distinct, r);
     JfScratch s;
 
@@ -155,11 +177,11 @@ int jf_stream_records(katgpu_table* t, uint32_t r, const uint64_t* cols, FILE* f
     HIPCHK(c, hipMemcpyAsync(bins.data(), s.hist, nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
 
-    // a range's records: 20 bytes to order them, 4 should they need ranking, its bytes in each of the two output buffers.  Half of what
+    // a range's records: 20 bytes (wide: 28) to order them, 4 should they need ranking, its bytes in each of the two output buffers.  Half of what
     // is free, and at most 2^25 records: the pinned buffers are what the host pays (and pinning is not free: kg_host.hpp, ScanCache).
     size_t free_b = 0, total_b = 0;
     HIPCHK(c, hipMemGetInfo(&free_b, &total_b));
-    uint64_t want = std::min<uint64_t>(std::max<uint64_t>(free_b / 2 / (24 + 2 * rb), 1 << 16), 1 << 25);
+    uint64_t want = std::min<uint64_t>(std::max<uint64_t>(free_b / 2 / (jf_scratch_bytes<W> + 4 + 2 * rb), 1 << 16), 1 << 25);
     if (g_jf_range_records) want = g_jf_range_records;
     std::vector<JfRange> ranges;
     uint64_t acc = 0, start = 0, max_n = 0, sum = 0;
@@ -179,7 +201,7 @@ int jf_stream_records(katgpu_table* t, uint32_t r, const uint64_t* cols, FILE* f
     if (max_nb >= (1ULL << 31) || !s.ensure(c, s.hist, s.nb_cap, (size_t)max_nb, ((size_t)max_nb * 3 + 1) * sizeof(uint32_t))) return KG_JF_NO_SCRATCH;
     const int nbuf = ranges.size() > 1 ? 2 : 1;
     JfSlots io(c);                                                // events of a slot: range started, produced, copied
-    if (!s.ensure(c, s.recs, s.rec_cap, (size_t)max_n, (size_t)max_n * 20) ||
+    if (!s.ensure(c, s.recs, s.rec_cap, (size_t)max_n, (size_t)max_n * jf_scratch_bytes<W>) ||
         !io.setup(nbuf, (size_t)max_n * rb, false, [&](void** p, size_t bytes) { return jf_malloc(c, p, bytes); })) return KG_JF_NO_SCRATCH;
 
     int pend = -1, slot = 0;
@@ -221,6 +243,10 @@ int jf_stream_records(katgpu_table* t, uint32_t r, const uint64_t* cols, FILE* f
     if (!rc) rc = drain();
     if (!rc && written != distinct) rc = fail(c, KATGPU_ERR_DEVICE, "jf dump: wrote %llu of %llu records", (unsigned long long)written, (unsigned long long)distinct);
     return rc;
+}
+
+int jf_stream_records(katgpu_table* t, uint32_t r, const uint64_t* cols, FILE* f, JfDumpTiming* tm) {
+    return t->dv.keys_b ? jf_stream<true>(t, r, cols, f, tm) : jf_stream<false>(t, r, cols, f, tm);
 }
 
 // ------------------------------------------------------------------ .jf records into a table ----

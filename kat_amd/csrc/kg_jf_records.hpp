@@ -1,15 +1,17 @@
-// kg_jf_records.hpp -- the records of a Jellyfish "binary/sorted" hash file, ordered and packed on the device (k <= 32).
+// kg_jf_records.hpp -- the records of a Jellyfish "binary/sorted" hash file, ordered and packed on the device.
+// One body per kernel for both key widths: <W> is a two-word ("wide", 33 <= k <= 63) table, whose key is (hi, lo).
 //
-// Replaces, for one-word tables, the order sorted_dumper emits (JF/include/jellyfish/sorted_dumper.hpp:80-112) and the bytes
-// binary_writer writes per record (binary_dumper.hpp:47-51): records ascending by ((M * kmer) & (size - 1), kmer), each
-// ceil(2k/8) key bytes + 4 count bytes, little endian, the count saturated.  kg_jf.cpp describes the file around them.
+// Replaces the order sorted_dumper emits (JF/include/jellyfish/sorted_dumper.hpp:80-112) and the bytes
+// binary_writer writes per record (binary_dumper.hpp:47-51): records ascending by ((M * kmer) & (size - 1), kmer) -- a two-word k-mer
+// compares as multi-word mer_dna::operator< does, hi first, unsigned -- each ceil(2k/8) key bytes + 4 count bytes, little endian, the
+// count saturated.  kg_jf.cpp describes the file around them.
 //
 //  J1 k_jf_select     slot walk: rebuild the key, position = parity(key & row) per matrix row, keep [pos_lo, pos_hi);
-//                     <2> counts the range, <0> histograms it over buckets of 2^shift positions, <1> scatters (pos, key, count)
+//                     <2> counts the range, <0> histograms it over buckets of 2^shift positions, <1> scatters (pos, [hi,] key, count)
 //                     records to their bucket's stretch of the scratch segment
 //  J2 k_jf_scan       exclusive scan of the bucket histogram (one workgroup), the total and the largest bucket
 //  J3 k_jf_rank       buckets beyond one LDS tile only: a record's rank among its bucket, by comparison with all of it (global memory)
-//  J4 k_jf_sort_pack  one workgroup per bucket: bitonic sort of the bucket on (pos, key) in LDS (or, for a ranked bucket, a gather
+//  J4 k_jf_sort_pack  one workgroup per bucket: bitonic sort of the bucket on (pos, [hi,] key) in LDS (or, for a ranked bucket, a gather
 //                     by rank, tile after tile), then the tile's bytes assembled in LDS and stored as whole dwords
 //
 // Positions of distinct keys under a random matrix are close to uniform, so the host picks `shift` for a mean of at most
@@ -21,43 +23,62 @@
 namespace kg {
 
 constexpr int JF_BLOCK = 256;
-constexpr uint32_t JF_TILE = 512;            // records sorted and packed per workgroup pass: 10 KB of records + 6 KB of bytes in LDS
+constexpr uint32_t JF_TILE = 512;            // records sorted and packed per workgroup pass: 10 KB of records + 6 KB of bytes in LDS (wide: 14 + 10)
 constexpr uint32_t JF_BUCKET_MEAN = 256;     // the host sizes buckets for at most this many expected records
 constexpr uint32_t JF_RANK_MAX = 1u << 16;      // the largest bucket the ranking path takes: 2^32 comparisons, a fraction of a second
-constexpr uint32_t JF_MAX_REC_BYTES = 12;    // k = 32: 8 key bytes + 4 count bytes
+template <bool W> constexpr uint32_t JF_MAX_REC_BYTES = W ? 20 : 12;    // k = 32: 8 key bytes + 4 count bytes; k = 63: 16 + 4
 constexpr int JF_SCAN_BLOCK = 1024;
 
 // the r rows of M over the 2k key bits (row j, bit i = column 2k-1-i, bit j).  Passed by value: the rows sit in the kernel
-// argument segment and a wave reads them with scalar loads.
-struct JfRows { uint64_t row[63]; };
+// argument segment and a wave reads them with scalar loads.  A wide key's bits 64..125 meet row_hi.
+template <bool W> struct JfRows { uint64_t row[63]; };
+template <> struct JfRows<true> { uint64_t row[63], row_hi[63]; };
 
-__device__ __forceinline__ uint64_t jf_pos(const JfRows& m, uint32_t r, uint64_t key) {
+template <bool W>
+__device__ __forceinline__ uint64_t jf_pos(const JfRows<W>& m, uint32_t r, uint64_t hi, uint64_t key) {
     uint64_t pos = 0;
-    for (uint32_t j = 0; j < r; ++j) pos |= (uint64_t)(__popcll(key & m.row[j]) & 1) << j;
+    for (uint32_t j = 0; j < r; ++j) {
+        uint32_t ones = __popcll(key & m.row[j]);
+        if constexpr (W) ones += __popcll(hi & m.row_hi[j]);
+        pos |= (uint64_t)(ones & 1) << j;
+    }
     return pos;
 }
 
-__device__ __forceinline__ bool jf_less(uint64_t pa, uint64_t ka, uint64_t pb, uint64_t kb) { return pa != pb ? pa < pb : ka < kb; }
+// (one-word keys come with hi = 0 on both sides)
+__device__ __forceinline__ bool jf_less(uint64_t pa, uint64_t ha, uint64_t ka, uint64_t pb, uint64_t hb, uint64_t kb) {
+    return pa != pb ? pa < pb : ha != hb ? ha < hb : ka < kb;
+}
 
 // J1.  MODE 2: *total += records of the range.  MODE 0: ++hist[bucket].  MODE 1: record -> scratch[cursor[bucket]++].
-template <int MODE>
+// A wide table is walked as k_export_w walks it, and every k-mer of it is in a slot (the all-T 63-mer's first word is 2^63 - 1, not EMPTY).
+template <int MODE, bool W>
 __global__ void __launch_bounds__(JF_BLOCK)
-k_jf_select(DevTable t, uint32_t n_ovf, JfRows m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift,
+k_jf_select(DevTable t, uint32_t n_ovf, JfRows<W> m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift,
             uint32_t* __restrict__ hist_or_cursor, unsigned long long* __restrict__ total,
-            uint64_t* __restrict__ out_pos, uint64_t* __restrict__ out_key, uint32_t* __restrict__ out_cnt) {
+            uint64_t* __restrict__ out_pos, uint64_t* __restrict__ out_hi, uint64_t* __restrict__ out_key, uint32_t* __restrict__ out_cnt) {
     uint64_t mine = 0;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= t.cap; i += stride) {
-        uint64_t key = EMPTY, in_slot = 0;
-        if (i < t.cap) { const SlotView v = slot_view(t, i); if (!v.occ) continue; key = v.key; in_slot = v.cnt; }
+    const uint64_t end = W ? t.cap : t.cap + 1;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += stride) {
+        uint64_t key = EMPTY, hi = 0, in_slot = 0;
+        if constexpr (W) {
+            const uint64_t a = t.keys[i];
+            if (a == EMPTY) continue;
+            const KeyW kw{a, t.keys_b[i]};
+            hi = keyw_hi(kw); key = keyw_lo(kw);
+        }
+        else if (i < t.cap) { const SlotView v = slot_view(t, i); if (!v.occ) continue; key = v.key; in_slot = v.cnt; }
         else if (!t.ctrs[CTR_ONES]) continue;                                  // the all-ones k-mer lives beside the slots
-        const uint64_t pos = jf_pos(m, r, key);
+        const uint64_t pos = jf_pos<W>(m, r, hi, key);
         if (pos < pos_lo || pos >= pos_hi) continue;
         if (MODE == 2) { ++mine; continue; }
         const uint64_t b = (pos - pos_lo) >> shift;
         const uint32_t at = atomicAdd(&hist_or_cursor[b], 1u);
         if (MODE == 1) {
-            const uint64_t c = i < t.cap ? slot_total(t, i, key, in_slot, n_ovf) : t.ctrs[CTR_ONES];
+            uint64_t c;
+            if constexpr (W) { c = slot_count(t, i, i, n_ovf); out_hi[at] = hi; }
+            else c = i < t.cap ? slot_total(t, i, key, in_slot, n_ovf) : t.ctrs[CTR_ONES];
             out_pos[at] = pos; out_key[at] = key;
             out_cnt[at] = c > 0xFFFFFFFFULL ? 0xFFFFFFFFu : (uint32_t)c;       // binary_writer::write saturates
         }
@@ -99,17 +120,18 @@ k_jf_scan(const uint32_t* __restrict__ hist, uint32_t nb, uint32_t* __restrict__
 
 // J3.  rank[i] = how many records of i's bucket sort before record i, for the buckets one LDS tile cannot hold.  Quadratic in the
 // bucket: the host refuses a range whose largest bucket exceeds JF_RANK_MAX before it launches this.
-static __global__ void __launch_bounds__(JF_BLOCK)
-k_jf_rank(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ key, uint32_t n, uint64_t pos_lo, uint32_t shift,
+template <bool W>
+__global__ void __launch_bounds__(JF_BLOCK)
+k_jf_rank(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ khi, const uint64_t* __restrict__ key, uint32_t n, uint64_t pos_lo, uint32_t shift,
           const uint32_t* __restrict__ off, uint32_t* __restrict__ rank) {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t p = pos[i], kk = key[i];
+        const uint64_t p = pos[i], kk = key[i], hh = W ? khi[i] : 0;
         const uint64_t b = (p - pos_lo) >> shift;
         const uint32_t lo = off[b], hi = off[b + 1];
         if (hi - lo <= JF_TILE) continue;
         uint32_t before = 0;
-        for (uint32_t j = lo; j < hi; ++j) before += jf_less(pos[j], key[j], p, kk) ? 1u : 0u;
+        for (uint32_t j = lo; j < hi; ++j) before += jf_less(pos[j], W ? khi[j] : 0, key[j], p, hh, kk) ? 1u : 0u;
         rank[i] = before;
     }
 }
@@ -118,13 +140,16 @@ k_jf_rank(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ key, ui
 // any byte address, so the tile is laid out in LDS with the same misalignment as its place in `out`: every dword of the image that
 // lies wholly inside the tile goes out as one dword store (a wave's stores are 256 contiguous bytes), and the at most two dwords a
 // tile shares with its neighbours go out byte by byte.
-static __global__ void __launch_bounds__(JF_BLOCK)
-k_jf_sort_pack(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ key, const uint32_t* __restrict__ cnt,
+// A wide record's key bytes are the 8 of lo, then the low key_bytes - 8 of hi.
+template <bool W>
+__global__ void __launch_bounds__(JF_BLOCK)
+k_jf_sort_pack(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ khi, const uint64_t* __restrict__ key, const uint32_t* __restrict__ cnt,
                const uint32_t* __restrict__ off, const uint32_t* __restrict__ rank, uint32_t nb, uint32_t key_bytes, uint8_t* __restrict__ out) {
     __shared__ uint64_t s_pos[JF_TILE];
+    __shared__ uint64_t s_hi[W ? JF_TILE : 1];
     __shared__ uint64_t s_key[JF_TILE];
     __shared__ uint32_t s_cnt[JF_TILE];
-    __shared__ uint32_t s_img[JF_TILE * JF_MAX_REC_BYTES / 4 + 2];
+    __shared__ uint32_t s_img[JF_TILE * JF_MAX_REC_BYTES<W> / 4 + 2];
     const uint32_t tid = threadIdx.x;
     const uint32_t rb = key_bytes + 4;
     for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
@@ -137,6 +162,7 @@ k_jf_sort_pack(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ ke
                 for (uint32_t i = tid; i < p2; i += JF_BLOCK) {
                     const bool real = i < m;                                  // padding sorts last: a position is below 2^63
                     s_pos[i] = real ? pos[lo + i] : ~0ULL; s_key[i] = real ? key[lo + i] : ~0ULL; s_cnt[i] = real ? cnt[lo + i] : 0;
+                    if constexpr (W) s_hi[i] = real ? khi[lo + i] : ~0ULL;
                 }
                 __syncthreads();
                 for (uint32_t k2 = 2; k2 <= p2; k2 <<= 1)
@@ -145,8 +171,10 @@ k_jf_sort_pack(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ ke
                             const uint32_t i = 2 * t - (t & (j - 1)), l = i + j;
                             const bool up = (i & k2) == 0;
                             const uint64_t pa = s_pos[i], ka = s_key[i], pb = s_pos[l], kb = s_key[l];
-                            if (jf_less(pb, kb, pa, ka) == up) {
+                            const uint64_t ha = W ? s_hi[i] : 0, hb = W ? s_hi[l] : 0;
+                            if (jf_less(pb, hb, kb, pa, ha, ka) == up) {
                                 s_pos[i] = pb; s_key[i] = kb; s_pos[l] = pa; s_key[l] = ka;
+                                if constexpr (W) { s_hi[i] = hb; s_hi[l] = ha; }
                                 const uint32_t ca = s_cnt[i]; s_cnt[i] = s_cnt[l]; s_cnt[l] = ca;
                             }
                         }
@@ -155,7 +183,7 @@ k_jf_sort_pack(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ ke
             } else {
                 for (uint32_t i = tid; i < m; i += JF_BLOCK) {
                     const uint32_t at = rank[lo + i] - t0;                   // (wraps below t0: not this tile's)
-                    if (at < n_tile) { s_key[at] = key[lo + i]; s_cnt[at] = cnt[lo + i]; }
+                    if (at < n_tile) { s_key[at] = key[lo + i]; s_cnt[at] = cnt[lo + i]; if constexpr (W) s_hi[at] = khi[lo + i]; }
                 }
                 __syncthreads();
             }
@@ -166,7 +194,9 @@ k_jf_sort_pack(const uint64_t* __restrict__ pos, const uint64_t* __restrict__ ke
                 uint8_t* p = img + mis + i * rb;
                 const uint64_t kk = s_key[i];
                 const uint32_t c = s_cnt[i];
-                for (uint32_t x = 0; x < key_bytes; ++x) p[x] = (uint8_t)(kk >> (8 * x));
+                const uint32_t lo_bytes = W ? 8 : key_bytes;
+                for (uint32_t x = 0; x < lo_bytes; ++x) p[x] = (uint8_t)(kk >> (8 * x));
+                if constexpr (W) { const uint64_t hh = s_hi[i]; for (uint32_t x = 8; x < key_bytes; ++x) p[x] = (uint8_t)(hh >> (8 * (x - 8))); }
                 for (uint32_t x = 0; x < 4; ++x) p[key_bytes + x] = (uint8_t)(c >> (8 * x));
             }
             __syncthreads();
