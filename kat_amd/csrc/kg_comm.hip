@@ -596,7 +596,7 @@ static const bool g_wire_packed = !getenv("KATGPU_COMM_PACKED_RECORDS") || atoi(
 
 // Wide tables (k > 32): the simple exchange -- records (hi, lo, count) grouped by owner, all to all, the table emptied and refilled
 // with what arrived.  Not region-ordered: the wide table's hash is not one to one and its slots are 20 bytes in three arrays, which the
-// LDS merge is not built for; wide tables count through the direct kernel and merge through it too (k_merge_w).  The table keeps its
+// LDS merge is not built for; wide tables count through the direct kernel and merge through it too (k_merge<true>).  The table keeps its
 // handle; it grows if its owner share is larger than what it held.
 static int exchange_merge_wide(katgpu_comm* m, katgpu_table* t) {
     katgpu_ctx* c = m->ctx;

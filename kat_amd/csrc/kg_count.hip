@@ -6,7 +6,6 @@
 #include "kg_kernels.hpp"
 #include "kg_partition.hpp"
 #include "kg_partition_wide.hpp"
-#include "kg_wide.hpp"
 
 #include <condition_variable>
 #include <deque>

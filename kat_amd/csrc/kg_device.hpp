@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace kg {
 
@@ -280,7 +281,8 @@ __device__ __forceinline__ uint64_t pk_key(const DevTable& t, uint64_t pos, uint
 // amount = q * half + r (r < half): the slot takes r (and, should that carry it past its field, gives `half` back), the side table q * half
 __device__ __forceinline__ void pk_split(uint64_t amount, uint32_t cbits, uint64_t& q, uint64_t& r) { q = amount >> (cbits - 1); r = amount & (pk_half(cbits) - 1); }
 
-// One slot of a one-word table, whatever its layout: occupied?, the k-mer, the in-slot count (the side table's part is slot_count's)
+// One slot of a one-word table, whatever its layout: occupied?, the k-mer, the in-slot count (the side table's part is slot_total's;
+// slot_rec below reads a slot whole, at either key width)
 struct SlotView { bool occ; uint64_t key; uint64_t cnt; };
 __device__ __forceinline__ SlotView slot_view(const DevTable& t, uint64_t pos) {
     SlotView v;
@@ -304,8 +306,13 @@ __device__ __forceinline__ uint64_t slot_total(const DevTable& t, uint64_t pos, 
     if (n_ovf) c += ovf_get(t, ovf_by_slot(t) ? pos : key);
     return c;
 }
-__device__ __forceinline__ uint64_t slot_count(const DevTable& t, uint64_t pos, uint64_t key, uint32_t n_ovf) {      // KV12 and wide tables
+__device__ __forceinline__ uint64_t slot_count(const DevTable& t, uint64_t pos, uint64_t key, uint32_t n_ovf) {      // KV12 tables
     return slot_total(t, pos, key, t.counts[pos], n_ovf);
+}
+__device__ __forceinline__ uint64_t slot_count(const DevTable& t, uint64_t pos, uint32_t n_ovf) {                    // wide tables: the side table goes by the slot
+    uint64_t c = t.counts[pos];
+    if (n_ovf) c += ovf_get(t, pos);
+    return c;
 }
 
 // An insert that walked its whole region without finding room: the host keeps every table under its fill limit and the hash
@@ -461,18 +468,18 @@ __device__ __forceinline__ void revcomp_words(uint64_t hi, uint64_t lo, uint32_t
     rlo = (L >> s) | (H << (64 - s));
     rhi = H >> s;
 }
-__device__ __forceinline__ KeyW keyw_canonical(KeyW x, uint32_t k) {
+__device__ __forceinline__ KeyW kmer_canonical(KeyW x, uint32_t k) {
     const uint64_t hi = keyw_hi(x), lo = keyw_lo(x);
     uint64_t rhi, rlo;
     revcomp_words(hi, lo, k, rhi, rlo);
     const bool rc_less = rhi < hi || (rhi == hi && rlo < lo);
     return rc_less ? keyw_from_words(rhi, rlo) : x;
 }
-__device__ __forceinline__ uint32_t keyw_gc(KeyW x, uint32_t k) { return kmer_gc(keyw_lo(x), 32) + kmer_gc(keyw_hi(x), k - 32); }
+__device__ __forceinline__ uint32_t kmer_gc(KeyW x, uint32_t k) { return kmer_gc(keyw_lo(x), 32) + kmer_gc(keyw_hi(x), k - 32); }
 __device__ __forceinline__ uint64_t keyw_hash(KeyW x) { return mix64(x.b ^ (x.a * 0x9E3779B97F4A7C15ULL)); }
-// owner part of a wide k-mer for the multi-GPU merge: a second mix of the CANONICAL form, as owner_of does for one-word k-mers
-__device__ __forceinline__ uint32_t owner_of_w(KeyW key, uint32_t k, uint32_t n_parts) {
-    const KeyW c = keyw_canonical(key, k);
+// owner part of a wide k-mer for the multi-GPU merge: a second mix of the CANONICAL form, as for one-word k-mers
+__device__ __forceinline__ uint32_t owner_of(KeyW key, uint32_t k, uint32_t n_parts) {
+    const KeyW c = kmer_canonical(key, k);
     return (uint32_t)__umul64hi(mix64(keyw_hash(c) ^ 0x9E3779B97F4A7C15ULL), (uint64_t)n_parts);
 }
 __device__ __forceinline__ Probe probe_start_w(KeyW key, const DevTable& t) {
@@ -484,7 +491,7 @@ __device__ __forceinline__ Probe probe_start_w(KeyW key, const DevTable& t) {
     return p;
 }
 
-__device__ __forceinline__ bool table_add_w(const DevTable& t, KeyW key, uint64_t amount, uint32_t& new_distinct) {
+__device__ __forceinline__ bool table_add(const DevTable& t, KeyW key, uint64_t amount, uint32_t& new_distinct) {
     Probe pr = probe_start_w(key, t);
     for (uint32_t probe = 0; probe < t.region_slots; ++probe, pr.next()) {
         const uint64_t pos = pr.pos();
@@ -511,21 +518,85 @@ __device__ __forceinline__ bool table_add_w(const DevTable& t, KeyW key, uint64_
     return false;
 }
 
-__device__ __forceinline__ uint64_t table_get_w(const DevTable& t, KeyW key, uint32_t n_ovf) {
+__device__ __forceinline__ uint64_t table_get(const DevTable& t, KeyW key, uint32_t n_ovf) {
     Probe pr = probe_start_w(key, t);
     for (uint32_t probe = 0; probe < t.region_slots; ++probe, pr.next()) {
         const uint64_t pos = pr.pos();
         const uint64_t a = t.keys[pos];
         if (a == EMPTY) return 0;
-        if (a == key.a && t.keys_b[pos] == key.b) return slot_count(t, pos, pos, n_ovf);
+        if (a == key.a && t.keys_b[pos] == key.b) return slot_count(t, pos, n_ovf);
     }
     return 0;
 }
 
-// the same operations under the one-word names, for a kernel body written once over the key type
-__device__ __forceinline__ KeyW kmer_canonical(KeyW x, uint32_t k) { return keyw_canonical(x, k); }
-__device__ __forceinline__ bool table_inc(const DevTable& t, KeyW key, uint32_t& new_distinct) { return table_add_w(t, key, 1, new_distinct); }   // (wide tables have no unit path: the returning add, amount 1)
-__device__ __forceinline__ uint64_t table_get(const DevTable& t, KeyW key, uint32_t n_ovf) { return table_get_w(t, key, n_ovf); }
+__device__ __forceinline__ bool table_inc(const DevTable& t, KeyW key, uint32_t& new_distinct) { return table_add(t, key, 1, new_distinct); }   // (wide tables have no unit path: the returning add, amount 1)
+
+// ---- one body for both key widths ----
+// kmer_canonical, kmer_gc, owner_of, table_add, table_inc and table_get are overloaded on the key type; a kernel templated on W
+// (wide table) names its key Key<W>, reads a slot with slot_rec<W> and its record columns through RecCols<W>.
+template <bool W> using Key = std::conditional_t<W, KeyW, uint64_t>;
+
+// An occupied slot whole: the k-mer and its full 64-bit count.  Nothing beyond the first key word is read of an empty slot (no
+// keys_b, counts or side table, no packed decode); key and total mean nothing there.
+template <bool W> struct SlotRec { bool occ; Key<W> key; uint64_t total; };
+template <bool W>
+__device__ __forceinline__ SlotRec<W> slot_rec(const DevTable& t, uint64_t pos, uint32_t n_ovf) {
+    SlotRec<W> r{};
+    if constexpr (W) {
+        const uint64_t a = t.keys[pos];
+        r.occ = a != EMPTY;
+        if (r.occ) { r.key = KeyW{a, t.keys_b[pos]}; r.total = slot_count(t, pos, n_ovf); }
+    } else {
+        const SlotView v = slot_view(t, pos);
+        r.occ = v.occ; r.key = v.key;
+        if (v.occ) r.total = slot_total(t, pos, v.key, v.cnt, n_ovf);
+    }
+    return r;
+}
+// ... of a walk over cap + 1 slots: the virtual slot `cap` of a one-word table is the all-ones k-mer, counted in ctrs[CTR_ONES]
+// (a wide table has every k-mer in a slot)
+template <bool W>
+__device__ __forceinline__ SlotRec<W> slot_rec_or_ones(const DevTable& t, uint64_t pos, uint32_t n_ovf) {
+    if (pos < t.cap) return slot_rec<W>(t, pos, n_ovf);
+    SlotRec<W> r{};
+    if constexpr (!W) if (pos == t.cap) { r.key = EMPTY; r.total = t.ctrs[CTR_ONES]; r.occ = r.total != 0; }
+    return r;
+}
+
+// Records as parallel columns of n words each: the key (one-word: the k-mer; wide: the 2k-bit word's high and low 64 bits) and the
+// count.  T = const uint64_t: columns that are only read.
+template <bool W, typename T = uint64_t>
+struct RecCols {
+    static constexpr int KEYS = W ? 2 : 1;
+    T* key[KEYS];
+    T* count;
+    static __host__ __device__ RecCols of(T* d, size_t n) {            // the columns back to back in one buffer of (KEYS + 1) * n words
+        RecCols r;
+        for (int j = 0; j < KEYS; ++j) r.key[j] = d + (size_t)j * n;
+        r.count = d + (size_t)KEYS * n;
+        return r;
+    }
+    __host__ __device__ RecCols from(size_t pos) const {                // the records from pos on
+        RecCols r = *this;
+        for (int j = 0; j < KEYS; ++j) r.key[j] += pos;
+        r.count += pos;
+        return r;
+    }
+    __host__ __device__ bool any_null() const {
+        bool null = !count;
+        for (int j = 0; j < KEYS; ++j) null = null || !key[j];
+        return null;
+    }
+    __device__ __forceinline__ Key<W> load(uint64_t i) const {
+        if constexpr (W) return keyw_from_words(key[0][i], key[1][i]);
+        else return key[0][i];
+    }
+    __device__ __forceinline__ void store(uint64_t at, Key<W> k, uint64_t c) const {
+        if constexpr (W) { key[0][at] = keyw_hi(k); key[1][at] = keyw_lo(k); }
+        else key[0][at] = k;
+        count[at] = c;
+    }
+};
 
 // A lane's value for the whole wave, the lane wave-uniform (a ballot's first set bit, lane 0 ...): v_readlane_b32, a few cycles --
 // __shfl of a uniform lane is a ds_bpermute through the LDS crossbar, ~200 cycles of latency on gfx950 (tools/ubench_valu.hip).

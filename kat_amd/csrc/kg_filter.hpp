@@ -1,6 +1,6 @@
 // kg_filter.hpp -- the two hot loops of `kat filter`, written for gfx950 (CDNA4, wave64).
 //
-//  K9  k_filter / k_filter_w   one pass over every slot of a table: count x GC box -> keep / drop tables  (replaces FilterKmer::filterSlice)
+//  K9  k_filter<SEP, W>        one pass over every slot of a table: count x GC box -> keep / drop tables  (replaces FilterKmer::filterSlice)
 //  K10 k_seq_hits              per-record number of windows found in a table                              (replaces FilterSeq::getProfile + the
 //                                                                                                          nbFound loop of processSeq)
 // K9 rebuilds rather than clears: probing is linear inside a region (kg_device.hpp: Probe), so clearing a slot in place would cut the
@@ -46,54 +46,33 @@ struct FilterTally {
 template <bool SEP>
 __device__ __forceinline__ bool filter_keeps(bool in_b, bool invert) { return SEP ? in_b : in_b != invert; }
 
-// K9, one-word tables (P8 and KV12).  The full count of a slot is the in-slot count plus its side-table entry (keyed by the slot in
-// P8, by the k-mer in KV12); table_add splits it again for the destination slot, so side-table entries follow their k-mer.  The
-// all-ones k-mer kept in the counter block (k = 32, non-canonical) is routed by lane 0 of block 0.
-template <bool SEP>
+// K9, one body for one-word tables (P8 and KV12) and wide ones (W: k = 33 .. 63).  slot_rec gives the full count of a slot -- the
+// in-slot count plus its side-table entry -- and table_add splits it again for the destination slot, so side-table entries follow
+// their k-mer.  The all-ones k-mer a one-word table keeps in its counter block (k = 32, non-canonical) is routed by lane 0 of block 0.
+template <bool SEP, bool W>
 __global__ void __launch_bounds__(256)
 k_filter(DevTable keep, DevTable drop, DevTable src, uint32_t src_n_ovf, FilterBox box, int invert, unsigned long long* __restrict__ counters) {
     uint32_t nd_keep = 0, nd_drop = 0;
     FilterTally v{{0, 0, 0, 0, 0, 0}};
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < src.cap; i += stride) {
-        const SlotView s = slot_view(src, i);
+        const SlotRec<W> s = slot_rec<W>(src, i, src_n_ovf);
         if (!s.occ) continue;
-        const uint64_t cnt = slot_total(src, i, s.key, s.cnt, src_n_ovf);
-        const bool to_keep = filter_keeps<SEP>(filter_in_bounds(box, cnt, kmer_gc(s.key, src.k)), invert != 0);
-        if (to_keep) table_add(keep, s.key, cnt, nd_keep);
-        else if (SEP) table_add(drop, s.key, cnt, nd_drop);
-        v.add(to_keep, SEP && !to_keep, cnt);
+        const bool to_keep = filter_keeps<SEP>(filter_in_bounds(box, s.total, kmer_gc(s.key, src.k)), invert != 0);
+        if (to_keep) table_add(keep, s.key, s.total, nd_keep);
+        else if (SEP) table_add(drop, s.key, s.total, nd_drop);
+        v.add(to_keep, SEP && !to_keep, s.total);
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const uint64_t ones = src.ctrs[CTR_ONES];
-        if (ones) {
-            const bool to_keep = filter_keeps<SEP>(filter_in_bounds(box, ones, kmer_gc(EMPTY, src.k)), invert != 0);
-            if (to_keep) atomicAdd((unsigned long long*)&keep.ctrs[CTR_ONES], (unsigned long long)ones);
-            else if (SEP) atomicAdd((unsigned long long*)&drop.ctrs[CTR_ONES], (unsigned long long)ones);
-            v.add(to_keep, SEP && !to_keep, ones);
+    if constexpr (!W) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            const uint64_t ones = src.ctrs[CTR_ONES];
+            if (ones) {
+                const bool to_keep = filter_keeps<SEP>(filter_in_bounds(box, ones, kmer_gc(EMPTY, src.k)), invert != 0);
+                if (to_keep) atomicAdd((unsigned long long*)&keep.ctrs[CTR_ONES], (unsigned long long)ones);
+                else if (SEP) atomicAdd((unsigned long long*)&drop.ctrs[CTR_ONES], (unsigned long long)ones);
+                v.add(to_keep, SEP && !to_keep, ones);
+            }
         }
-    }
-    flush_distinct(keep, nd_keep);
-    if (SEP) flush_distinct(drop, nd_drop);
-    v.flush(counters);
-}
-
-// K9, wide tables (k = 33 .. 63): the same pass over two key words per slot; the side table is keyed by the slot (k_regrow_w)
-template <bool SEP>
-__global__ void __launch_bounds__(256)
-k_filter_w(DevTable keep, DevTable drop, DevTable src, uint32_t src_n_ovf, FilterBox box, int invert, unsigned long long* __restrict__ counters) {
-    uint32_t nd_keep = 0, nd_drop = 0;
-    FilterTally v{{0, 0, 0, 0, 0, 0}};
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < src.cap; i += stride) {
-        const uint64_t a = src.keys[i];
-        if (a == EMPTY) continue;
-        const KeyW key{a, src.keys_b[i]};
-        const uint64_t cnt = slot_count(src, i, i, src_n_ovf);
-        const bool to_keep = filter_keeps<SEP>(filter_in_bounds(box, cnt, keyw_gc(key, src.k)), invert != 0);
-        if (to_keep) table_add_w(keep, key, cnt, nd_keep);
-        else if (SEP) table_add_w(drop, key, cnt, nd_drop);
-        v.add(to_keep, SEP && !to_keep, cnt);
     }
     flush_distinct(keep, nd_keep);
     if (SEP) flush_distinct(drop, nd_drop);

@@ -150,6 +150,12 @@ inline int fail(katgpu_ctx* c, int code, const char* fmt, ...) {
         if ((t)->dv.keys_b) return fail((t)->ctx, KATGPU_ERR_K, "%s is not available for k > 32 (k = %u)", what, (t)->dv.k);      /* (dv: metadata only -- a table left uncleared stays that way) */ \
     } while (0)
 
+// the `_wide` twin of an entry point that exists once per key width, called on a one-word table
+#define WIDE_ONLY(t, name, narrow_name)                                                                  \
+    do {                                                                                                 \
+        if (!(t)->dv.keys_b) return fail((t)->ctx, KATGPU_ERR_K, "%s is for k > 32 tables (k = %u): use %s", name, (t)->dv.k, narrow_name); \
+    } while (0)
+
 #define HIPCHK(c, expr)                                                                                  \
     do {                                                                                                 \
         hipError_t _e = (expr);                                                                          \
@@ -274,6 +280,13 @@ void launch_aligned_wide(katgpu_ctx* c, bool aligned, bool wide, uint64_t n, uin
     else if (wide) launch(std::false_type{}, std::true_type{}, grid, n_chunks);
     else if (aligned) launch(std::true_type{}, std::false_type{}, grid, n_chunks);
     else launch(std::false_type{}, std::false_type{}, grid, n_chunks);
+}
+
+// The two key widths of a kernel templated on W (wide table) behind one call: f(W) with W a std::true_type / std::false_type.
+template <typename F>
+void launch_wide(bool wide, F&& f) {
+    if (wide) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 // records of a host form: inside the n bases, in order and disjoint

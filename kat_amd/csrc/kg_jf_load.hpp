@@ -6,9 +6,9 @@
 //
 //  L1 k_jf_add<W>  a workgroup takes JL_TILE consecutive records: the aligned 16-byte words that cover the tile's bytes go to LDS
 //                  with one 16-byte load per lane (a wave reads 1 KB in a row), each lane then puts its records' key and count
-//                  together from LDS dwords with shifts and adds them with table_add (W = false: k <= 32, both slot layouts) or
-//                  table_add_w (W = true).  The semantics are k_merge's / k_merge_w's: exact 64-bit sums, a zero count skipped,
-//                  equal keys summed, amounts beyond the slot's field to the side table.
+//                  together from LDS dwords with shifts and adds them with table_add (W = false: k <= 32, both slot layouts;
+//                  W = true: two key words).  The semantics are k_merge's: exact 64-bit sums, a zero count skipped, equal keys
+//                  summed, amounts beyond the slot's field to the side table.
 //
 // A record is R = ceil(key_len / 8) + counter_len bytes (2 .. 24, 11 at k = 27), both fields little endian, back to back; the
 // records start at any byte address.  Bits of the key above key_len are masked off: Jellyfish writes zeros there, and a key
@@ -73,8 +73,10 @@ k_jf_add(DevTable dst, const uint8_t* __restrict__ recs, uint64_t n, uint32_t ke
             const uint64_t cnt = lds_u64(img, at + key_bytes) & cnt_mask;
             if (!cnt) continue;
             const uint64_t lo = lds_u64(img, at) & lo_mask;
-            if (W) table_add_w(dst, keyw_from_words(lds_u64(img, at + 8) & hi_mask, lo), cnt, new_distinct);
-            else table_add(dst, lo, cnt, new_distinct);
+            Key<W> key;
+            if constexpr (W) key = keyw_from_words(lds_u64(img, at + 8) & hi_mask, lo);     // (bits above 2k masked off, as lo's are)
+            else key = lo;
+            table_add(dst, key, cnt, new_distinct);
         }
         __syncthreads();
     }

@@ -51,7 +51,7 @@ __device__ __forceinline__ bool jf_less(uint64_t pa, uint64_t ha, uint64_t ka, u
 }
 
 // J1.  MODE 2: *total += records of the range.  MODE 0: ++hist[bucket].  MODE 1: record -> scratch[cursor[bucket]++].
-// A wide table is walked as k_export_w walks it, and every k-mer of it is in a slot (the all-T 63-mer's first word is 2^63 - 1, not EMPTY).
+// A wide table is walked as k_export walks it, and every k-mer of it is in a slot (the all-T 63-mer's first word is 2^63 - 1, not EMPTY).
 template <int MODE, bool W>
 __global__ void __launch_bounds__(JF_BLOCK)
 k_jf_select(DevTable t, uint32_t n_ovf, JfRows<W> m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift,
@@ -77,7 +77,7 @@ k_jf_select(DevTable t, uint32_t n_ovf, JfRows<W> m, uint32_t r, uint64_t pos_lo
         const uint32_t at = atomicAdd(&hist_or_cursor[b], 1u);
         if (MODE == 1) {
             uint64_t c;
-            if constexpr (W) { c = slot_count(t, i, i, n_ovf); out_hi[at] = hi; }
+            if constexpr (W) { c = slot_count(t, i, n_ovf); out_hi[at] = hi; }
             else c = i < t.cap ? slot_total(t, i, key, in_slot, n_ovf) : t.ctrs[CTR_ONES];
             out_pos[at] = pos; out_key[at] = key;
             out_cnt[at] = c > 0xFFFFFFFFULL ? 0xFFFFFFFFu : (uint32_t)c;       // binary_writer::write saturates

@@ -9,7 +9,8 @@
 //  K6 k_partition, k_extract_count, k_extract_write                              owner-partitioned export for the multi-GPU merge
 //  K7 k_merge, k_merge32, k_merge_apply, k_merge_deferred                        add (key,count) records into a table
 //  K8 k_profile        per-position lookup of a sequence's windows               (replaces the lookups of Sect::processSeq)
-// K1 and K8 are one body for one-word and wide k-mers (k <= 32, 33 <= k <= 63); what else wide tables need is in kg_wide.hpp.
+// K1, K2, K6 (k_partition), K7 (k_merge), K8, k_get and the probe forms of K5 are one body each for one-word and wide k-mers (k <= 32,
+// 33 <= k <= 63: the template parameter W; kg_device.hpp "one body for both key widths"); k_export is the wide tables' own export.
 //
 // All of this is integer / byte work bound by HBM (random 8-16 B slot accesses for K1/K5, streaming for K3/K4);
 // none of it is a contraction, so no MFMA anywhere.
@@ -73,24 +74,29 @@ k_count(DevTable t, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_ch
     flush_distinct(t, new_distinct);
 }
 
-// K2 / K7: add (key,count) records into a table.  src == another table's slots (regrow) or a record list (merge).
-static __global__ void __launch_bounds__(256)
+// K2 / K7: add (key,count) records into a table.  src == another table's slots (regrow: hash_counter::double_size,
+// hash_counter.hpp:204-244) or a record list (merge).
+template <bool W>
+__global__ void __launch_bounds__(256)
 k_regrow(DevTable dst, DevTable src, uint32_t src_n_ovf) {
     uint32_t new_distinct = 0;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < src.cap; i += stride) {
-        const SlotView v = slot_view(src, i);
-        if (v.occ) table_add(dst, v.key, slot_total(src, i, v.key, v.cnt, src_n_ovf), new_distinct);
+        const SlotRec<W> s = slot_rec<W>(src, i, src_n_ovf);
+        if (s.occ) table_add(dst, s.key, s.total, new_distinct);
     }
     flush_distinct(dst, new_distinct);
 }
 
-static __global__ void __launch_bounds__(256)
-k_merge(DevTable dst, const uint64_t* __restrict__ keys, const uint64_t* __restrict__ counts, uint64_t n) {
+template <bool W>
+__global__ void __launch_bounds__(256)
+k_merge(DevTable dst, RecCols<W, const uint64_t> rec, uint64_t n) {
     uint32_t new_distinct = 0;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        if (counts[i]) table_add(dst, keys[i], counts[i], new_distinct);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint64_t c = rec.count[i];
+        if (c) table_add(dst, rec.load(i), c, new_distinct);
+    }
     flush_distinct(dst, new_distinct);
 }
 
@@ -281,7 +287,7 @@ k_gcp(DevTable t, uint32_t n_ovf, double scale, uint32_t bins, unsigned long lon
             uint32_t cell = 0;
             if (occ) {
                 uint32_t g;
-                if constexpr (W) g = keyw_gc(KeyW{s4.w[j], kb[j]}, k);
+                if constexpr (W) g = kmer_gc(KeyW{s4.w[j], kb[j]}, k);
                 else if constexpr (PK) g = kmer_gc(key_in(pk_rem(s4.w[j], t.cbits), rp), k);
                 else g = kmer_gc(s4.w[j], k);
                 uint64_t pos = scale_count(slot_total(t, q * 4 + j, s4.w[j], s4.cnt[j], n_ovf), scale);
@@ -541,29 +547,12 @@ k_comp(DevTable ta, uint32_t na_ovf, DevTable tb, uint32_t nb_ovf, CompArgs a) {
     const uint64_t n_slots = ta.cap + 1;                   // virtual slot cap == the all-ones key
     const uint64_t rounds = (n_slots + stride - 1) / stride;
     for (uint64_t r = 0; r < rounds; ++r) {
-        uint64_t i = first + r * stride;
-        uint64_t key = EMPTY, ca = 0, cb = 0;
-        bool occ = false;
-        if (i < ta.cap) {
-            if constexpr (W) { key = ta.keys[i]; occ = key != EMPTY; if (occ) ca = slot_count(ta, i, key, na_ovf); }
-            else { const SlotView v = slot_view(ta, i); key = v.key; occ = v.occ; if (occ) ca = slot_total(ta, i, key, v.cnt, na_ovf); }
-        } else if (i == ta.cap) {
-            ca = ta.ctrs[CTR_ONES];
-            occ = ca != 0;
-        }
-        if (occ) {
-            // pass 1: hash-1 key probed in hash 2, canonicalised iff input 2 is canonical (src/comp.cc:401)
-            // pass 2: hash-2 key probed in hash 1, ALWAYS canonicalised (src/comp.cc:447 passes a pointer as the bool)
-            if constexpr (W) {
-                KeyW kw{key, ta.keys_b[i]};
-                if (PASS == 2 || a.canon_probe) kw = keyw_canonical(kw, k);
-                cb = table_get_w(tb, kw, nb_ovf);
-            } else {
-                uint64_t probe = (PASS == 2 || a.canon_probe) ? kmer_canonical(key, k) : key;
-                cb = table_get(tb, probe, nb_ovf);
-            }
-        }
-        comp_account<PASS>(occ, ca, cb, a, s_tile, s_spec, acc);
+        const SlotRec<W> s = slot_rec_or_ones<W>(ta, first + r * stride, na_ovf);
+        uint64_t cb = 0;
+        // pass 1: hash-1 key probed in hash 2, canonicalised iff input 2 is canonical (src/comp.cc:401)
+        // pass 2: hash-2 key probed in hash 1, ALWAYS canonicalised (src/comp.cc:447 passes a pointer as the bool)
+        if (s.occ) cb = table_get(tb, (PASS == 2 || a.canon_probe) ? kmer_canonical(s.key, k) : s.key, nb_ovf);
+        comp_account<PASS>(s.occ, s.total, cb, a, s_tile, s_spec, acc);
     }
     comp_flush<PASS>(a, s_acc, s_tile, s_spec, acc);
 }
@@ -918,27 +907,15 @@ k_comp3_pass1(DevTable t1, uint32_t n1_ovf, DevTable t2, uint32_t n2_ovf, DevTab
     const uint64_t first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t rounds = (t1.cap + 1 + stride - 1) / stride;
     for (uint64_t r = 0; r < rounds; ++r) {
-        const uint64_t i = first + r * stride;
-        uint64_t key = EMPTY, c1 = 0;
-        bool occ = false;
-        if (i < t1.cap) {
-            if constexpr (W) { key = t1.keys[i]; occ = key != EMPTY; if (occ) c1 = slot_count(t1, i, key, n1_ovf); }
-            else { const SlotView v = slot_view(t1, i); key = v.key; occ = v.occ; if (occ) c1 = slot_total(t1, i, key, v.cnt, n1_ovf); }
-        } else if (i == t1.cap) { c1 = t1.ctrs[CTR_ONES]; occ = c1 != 0; }
+        const SlotRec<W> s = slot_rec_or_ones<W>(t1, first + r * stride, n1_ovf);
+        const bool occ = s.occ;
         uint32_t which = 0, cell = 0;
         bool in_tile = false;
         if (occ) {
-            uint64_t c2, c3;
-            if constexpr (W) {
-                const KeyW kw{key, t1.keys_b[i]}, can = keyw_canonical(kw, k);
-                c2 = table_get_w(t2, a.canon2 ? can : kw, n2_ovf);
-                c3 = table_get_w(t3, a.canon3 ? can : kw, n3_ovf);
-            } else {
-                const uint64_t can = kmer_canonical(key, k);
-                c2 = table_get(t2, a.canon2 ? can : key, n2_ovf);
-                c3 = table_get(t3, a.canon3 ? can : key, n3_ovf);
-            }
-            uint64_t s1 = scale_count(c1, a.d1_scale), s2 = scale_count(c2, a.d2_scale), s3 = scale_count(c3, a.d2_scale);
+            const Key<W> can = kmer_canonical(s.key, k);
+            const uint64_t c2 = table_get(t2, a.canon2 ? can : s.key, n2_ovf);
+            const uint64_t c3 = table_get(t3, a.canon3 ? can : s.key, n3_ovf);
+            uint64_t s1 = scale_count(s.total, a.d1_scale), s2 = scale_count(c2, a.d2_scale), s3 = scale_count(c3, a.d2_scale);
             if (s1 >= a.d1_bins) s1 = a.d1_bins - 1;
             if (s2 >= a.d2_bins) s2 = a.d2_bins - 1;
             if (s3 >= a.d2_bins) s3 = a.d2_bins - 1;
@@ -974,11 +951,14 @@ k_comp3_pass3(DevTable t3, uint32_t n3_ovf, unsigned long long* counters) {
     if ((threadIdx.x & 63) == 0 && dis) { atomicAdd(&counters[CC_H3_TOTAL], (unsigned long long)tot); atomicAdd(&counters[CC_H3_DISTINCT], (unsigned long long)dis); }
 }
 
-// ---- batch lookup (JellyfishHelper::getCount, lib/src/jellyfish_helper.cc:189-194) ----
-static __global__ void __launch_bounds__(256)
-k_get(DevTable t, uint32_t n_ovf, const uint64_t* __restrict__ keys, uint64_t n, int canonicalise, uint64_t* __restrict__ out) {
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = table_get(t, canonicalise ? kmer_canonical(keys[i], t.k) : keys[i], n_ovf);
+// ---- batch lookup (JellyfishHelper::getCount, lib/src/jellyfish_helper.cc:189-194): rec.count[i] = the table's count of key i ----
+template <bool W>
+__global__ void __launch_bounds__(256)
+k_get(DevTable t, uint32_t n_ovf, RecCols<W> rec, uint64_t n, int canonicalise) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Key<W> key = rec.load(i);
+    rec.count[i] = table_get(t, canonicalise ? kmer_canonical(key, t.k) : key, n_ovf);
 }
 
 // K8.  Per-position coverage of a sequence (kat sect / kat cold; src/sect.cc:516-535): out[i] = count of the k-window
@@ -1032,19 +1012,39 @@ k_profile(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restric
 }
 
 // ---- export / owner partition ----
-// mode 0: count records per part into sizes[]; mode 1: scatter records to cursors[part]++.
-template <int MODE>
+// mode 0: count records per part into sizes[]; mode 1: scatter records to cursors[part]++.  A one-word table is walked over cap + 1
+// slots (slot_rec_or_ones).
+template <int MODE, bool W>
 __global__ void __launch_bounds__(256)
-k_partition(DevTable t, uint32_t n_ovf, uint32_t n_parts, unsigned long long* __restrict__ sizes_or_cursors,
-            uint64_t* __restrict__ out_keys, uint64_t* __restrict__ out_counts) {
+k_partition(DevTable t, uint32_t n_ovf, uint32_t n_parts, unsigned long long* __restrict__ sizes_or_cursors, RecCols<W> out) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= t.cap; i += stride) {
-        uint64_t key = EMPTY, c = 0;
-        if (i < t.cap) { const SlotView v = slot_view(t, i); if (!v.occ) continue; key = v.key; c = slot_total(t, i, key, v.cnt, n_ovf); }
-        else { c = t.ctrs[CTR_ONES]; if (!c) continue; }
-        uint32_t part = n_parts > 1 ? owner_of(key, t.k, n_parts) : 0;
-        unsigned long long at = atomicAdd(&sizes_or_cursors[part], 1ULL);
-        if (MODE == 1) { out_keys[at] = key; out_counts[at] = c; }
+    const uint64_t end = W ? t.cap : t.cap + 1;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += stride) {
+        const SlotRec<W> s = slot_rec_or_ones<W>(t, i, n_ovf);
+        if (!s.occ) continue;
+        const uint32_t part = n_parts > 1 ? owner_of(s.key, t.k, n_parts) : 0;
+        const unsigned long long at = atomicAdd(&sizes_or_cursors[part], 1ULL);
+        if (MODE == 1) out.store(at, s.key, s.total);
+    }
+}
+
+// every (k-mer, count) of a wide table, in slot order: a wave compacts its occupied lanes with one ballot and one cursor add
+static __global__ void __launch_bounds__(256)
+k_export(DevTable t, uint32_t n_ovf, RecCols<true> out, unsigned long long* cursor) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t rounds = (t.cap + stride - 1) / stride;
+    const uint32_t lane = threadIdx.x & 63;
+    for (uint64_t r = 0; r < rounds; ++r) {
+        const uint64_t i = first + r * stride;
+        SlotRec<true> s{};
+        if (i < t.cap) s = slot_rec<true>(t, i, n_ovf);
+        const unsigned long long live = __ballot(s.occ);
+        if (!live) continue;
+        unsigned long long base = 0;
+        if (lane == (uint32_t)(__ffsll((long long)live) - 1)) base = atomicAdd(cursor, (unsigned long long)__popcll(live));
+        base = __shfl(base, __ffsll((long long)live) - 1, 64);
+        if (s.occ) out.store(base + __popcll(live & ((1ULL << lane) - 1)), s.key, s.total);
     }
 }
 

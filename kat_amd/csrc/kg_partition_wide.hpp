@@ -9,7 +9,7 @@
 //     owns its share of every bucket (level 1: offs[w][b] from k_p1_scan; level 2: a bucket is one workgroup's), so an item's place
 //     is one returning LDS add on the share's cursor -- no ranking pass, no staging; neighbours of a run are written by the lanes of
 //     one tile within microseconds of each other and meet in L2.
-// The apply walks a region's run with table_add_w's protocol (claim the first half with a CAS, then the second) on the LDS copy;
+// The apply walks a region's run with the wide table_add's protocol (claim the first half with a CAS, then the second) on the LDS copy;
 // a region without a free slot spills the k-mer to a list the host inserts through the direct kernel after a regrow.
 // Replaces the same reference code as the direct kernel: mer_iterator + multi-word mer_dna (mer_iterator.hpp:59-89, mer_dna.hpp:235-258)
 // and hash_counter::add (hash_counter.hpp:90-113).
@@ -112,7 +112,7 @@ k_w2(uint32_t P1, uint32_t P2, const uint64_t* __restrict__ l1_off, const u64x2*
 }
 
 // ---- level 3: a region's run applied to the region in LDS ----
-// LDS: a[S] | b[S] | counts[S].  The walk is table_add_w on the LDS copy: the first half claims a free slot with a CAS, whoever finds
+// LDS: a[S] | b[S] | counts[S].  The walk is the wide table_add on the LDS copy: the first half claims a free slot with a CAS, whoever finds
 // its first half in a slot installs (or meets) the second half the same way, a match adds one.  A 32-bit wrap of the slot counter
 // is seen by the lane whose add returned 2^32 - 1 and goes to the side table (keyed by the slot, as for every wide table).
 // A k-mer that finds no slot in its region -- the region is full -- goes to the spill list.
@@ -175,7 +175,7 @@ k_insert_keys_w(DevTable t, const u64x2* __restrict__ items, uint64_t n) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const u64x2 it = items[i];
-        table_add_w(t, KeyW{it.x, it.y}, 1, new_distinct);
+        table_add(t, KeyW{it.x, it.y}, 1, new_distinct);
     }
     flush_distinct(t, new_distinct);
 }

@@ -3,7 +3,6 @@
 // of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*) and the count-range regions of `kat sect -n -E / -F` (katgpu_table_record_regions_*).  The host forms send their input through the device in batches.
 #include "kg_host.hpp"
 #include "kg_kernels.hpp"
-#include "kg_wide.hpp"
 #include "kg_filter.hpp"
 #include "kg_record_stats.hpp"
 #include "kg_record_regions.hpp"
@@ -15,40 +14,33 @@ static const size_t g_hits_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_T
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static uint64_t chunk_starts(bool wide) { return wide ? WIDE_CHUNK_STARTS : CHUNK_STARTS; }   // window starts per chunk of the window kernels
 
-extern "C" int katgpu_table_get(katgpu_table* t, const uint64_t* keys, size_t n, int canonicalise, uint64_t* counts) {
-    if (!t || (n && (!keys || !counts))) return KATGPU_ERR_INVALID_ARG;
-    NARROW_ONLY(t, "katgpu_table_get: use katgpu_table_get_wide;");
+// keys: the caller's columns, .count == counts (where the answers go).  One staging buffer: the key column(s), then the counts
+template <bool W>
+static int get_records(katgpu_table* t, RecCols<W, const uint64_t> keys, size_t n, int canonicalise, uint64_t* counts) {
+    if (!t || (n && keys.any_null())) return KATGPU_ERR_INVALID_ARG;
+    if constexpr (W) WIDE_ONLY(t, "katgpu_table_get_wide", "katgpu_table_get");
+    else NARROW_ONLY(t, "katgpu_table_get: use katgpu_table_get_wide;");
     if (!n) return KATGPU_OK;
     katgpu_ctx* c = t->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = refresh_counters(t); if (rc) return rc;
-    DevBuf dk, dc;
-    HIPCHK(c, dk.plain(n * 8));
-    if (dc.plain(n * 8) != hipSuccess) return fail(c, KATGPU_ERR_NOMEM, "lookup buffers");
-    hipMemcpyAsync(dk.p, keys, n * 8, hipMemcpyHostToDevice, c->stream);
-    hipLaunchKernelGGL(k_get, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, t->dev(), t->n_ovf, dk.as<uint64_t>(), (uint64_t)n, canonicalise, dc.as<uint64_t>());
-    hipMemcpyAsync(counts, dc.p, n * 8, hipMemcpyDeviceToHost, c->stream);
+    DevBuf buf;
+    if (buf.plain((keys.KEYS + 1) * n * 8) != hipSuccess) return fail(c, KATGPU_ERR_NOMEM, "lookup buffers");
+    const RecCols<W> d = RecCols<W>::of(buf.as<uint64_t>(), n);
+    for (int j = 0; j < keys.KEYS; ++j) hipMemcpyAsync(d.key[j], keys.key[j], n * 8, hipMemcpyHostToDevice, c->stream);
+    hipLaunchKernelGGL(k_get<W>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, t->dev(), t->n_ovf, d, (uint64_t)n, canonicalise);
+    hipMemcpyAsync(counts, d.count, n * 8, hipMemcpyDeviceToHost, c->stream);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s", hipGetErrorString(e));
     return KATGPU_OK;
 }
 
+extern "C" int katgpu_table_get(katgpu_table* t, const uint64_t* keys, size_t n, int canonicalise, uint64_t* counts) {
+    return get_records<false>(t, {{keys}, counts}, n, canonicalise, counts);
+}
+
 extern "C" int katgpu_table_get_wide(katgpu_table* t, const uint64_t* keys_hi, const uint64_t* keys_lo, size_t n, int canonicalise, uint64_t* counts) {
-    if (!t || (n && (!keys_hi || !keys_lo || !counts))) return KATGPU_ERR_INVALID_ARG;
-    katgpu_ctx* c = t->ctx;
-    if (!t->dev().keys_b) return fail(c, KATGPU_ERR_K, "katgpu_table_get_wide is for k > 32 tables (k = %u): use katgpu_table_get", t->dev().k);
-    if (!n) return KATGPU_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = refresh_counters(t); if (rc) return rc;
-    DevBuf buf; HIPCHK(c, buf.plain(3 * n * 8));
-    uint64_t* d = buf.as<uint64_t>();
-    hipMemcpyAsync(d, keys_hi, n * 8, hipMemcpyHostToDevice, c->stream);
-    hipMemcpyAsync(d + n, keys_lo, n * 8, hipMemcpyHostToDevice, c->stream);
-    hipLaunchKernelGGL(k_get_w, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, t->dev(), t->n_ovf, d, d + n, (uint64_t)n, canonicalise, d + 2 * n);
-    hipMemcpyAsync(counts, d + 2 * n, n * 8, hipMemcpyDeviceToHost, c->stream);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s", hipGetErrorString(e));
-    return KATGPU_OK;
+    return get_records<true>(t, {{keys_hi, keys_lo}, counts}, n, canonicalise, counts);
 }
 
 static int launch_profile(katgpu_table* t, const uint8_t* dev_bases, size_t n, int canonicalise, uint64_t* dev_counts) {

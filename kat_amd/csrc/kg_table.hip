@@ -2,7 +2,6 @@
 // (hash_counter::double_size), the counters and statistics, and the room made for records that are added in bulk (add_in_rooms).
 #include "kg_host.hpp"
 #include "kg_kernels.hpp"
-#include "kg_wide.hpp"
 
 static const uint32_t g_region_slots = (uint32_t)hook_u64("KATGPU_TEST_REGION_SLOTS", REGION_SLOTS);
 static const bool g_no_packed = hook("KATGPU_NO_PACKED") != nullptr;   // tests / A-B: every table in the KV12 layout
@@ -164,8 +163,9 @@ int regrow(katgpu_table* t, uint64_t new_cap) {
     if (rc) return rc;
     {
         ScopedTimer tm(c, KATGPU_K_REGROW, t->dev().cap);
-        if (t->dev().keys_b) hipLaunchKernelGGL(k_regrow_w, dim3(grid_for(c, t->dev().cap, 256, 8)), dim3(256), 0, c->stream, nd, t->dev(), t->n_ovf);
-        else hipLaunchKernelGGL(k_regrow, dim3(grid_for(c, t->dev().cap, 256, 8)), dim3(256), 0, c->stream, nd, t->dev(), t->n_ovf);
+        launch_wide(t->dev().keys_b != nullptr, [&](auto W) {
+            hipLaunchKernelGGL(k_regrow<decltype(W)::value>, dim3(grid_for(c, t->dev().cap, 256, 8)), dim3(256), 0, c->stream, nd, t->dev(), t->n_ovf);
+        });
     }
     HIPCHK(c, hipMemcpyAsync(&nd.ctrs[CTR_ONES], &t->dev().ctrs[CTR_ONES], sizeof(uint64_t), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -6,7 +6,7 @@ that protocol need (tests/test_dist_gloo.py: world 2 / 3 / 4 over gloo, an oracl
 region-ordered, chunked, in-place protocol -- per-region counts all to all, the send list in chunks of consecutive regions with
 chunk c on the wire while chunk c-1 is applied, out-of-band records for counts above 32 bits -- written against a duck-typed shard
 (geometry / begin_exchange / exchange_buffers / extract / clear / merge_chunk / merge_big), plus shard_range (how reads and contigs
-are dealt to ranks) and owner_of / owner_of_wide (kg_device.hpp: owner_of, owner_of_w), which the GPU tests check the device against.
+are dealt to ranks) and owner_of / owner_of_wide (kg_device.hpp: owner_of at both key widths), which the GPU tests check the device against.
 """
 import numpy as np
 import torch
@@ -184,7 +184,7 @@ def _revcomp_wide(hi, lo, k):
 
 
 def owner_of_wide(hi, lo, k, n_parts):
-    """Host mirror of kg_device.hpp: owner_of_w -- a second mix of the canonical form's table hash."""
+    """Host mirror of kg_device.hpp: owner_of for two-word keys -- a second mix of the canonical form's table hash."""
     from .synth import mulhi64
     hi = np.asarray(hi, dtype=np.uint64)
     lo = np.asarray(lo, dtype=np.uint64)

@@ -162,7 +162,7 @@ def test_shard_range_covers_everything():
 # ---------------------------------------------------------------- k > 32: exchange_merge_wide --------------------------------
 
 def exchange_merge_wide(shard, group=None, force=False):
-    """exchange_merge for wide tables: every (k-mer, count) record goes to owner_of_w(k-mer); on return shard.table holds exactly
+    """exchange_merge for wide tables: every (k-mer, count) record goes to owner_of_wide(k-mer); on return shard.table holds exactly
     the k-mers this rank owns, counts summed over ranks (exact integer sums: bit-identical to one process).  The shard is
     duck-typed (part_sizes / partition / rebuild) like the one-word exchange's."""
     world = dist.get_world_size(group) if dist.is_initialized() else 1
