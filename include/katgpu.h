@@ -421,6 +421,18 @@ int  katgpu_exchange_begin(katgpu_comm* comm, katgpu_table* t);
 int  katgpu_exchange_finish(katgpu_comm* comm, katgpu_table* t);
 /* buf[i] = sum over ranks of buf[i], on every rank (host memory; collective) */
 int  katgpu_allreduce_u64(katgpu_comm* comm, uint64_t* buf, size_t n);
+/* katgpu_jf_dump for the tables of all ranks, after the exchange.  Collective: every rank calls it with its own table; rank 0 writes
+ * the one "binary/sorted" file katgpu_jf_dump would write for the union (the header's "time" apart); `path` is read on rank 0 only.
+ * PRECONDITION, not checked: the tables hold disjoint k-mers (each k-mer on one rank, as katgpu_exchange_merge leaves them), with one
+ * k and one canonical flag; a k-mer on two ranks would appear twice in the file.
+ * The geometry is that of the summed distinct counts.  Range of positions by range, every rank orders and packs its records on its
+ * device, the runs travel to rank 0 over the communicator's transport, rank 0 orders their union on its device and streams it out
+ * through two pinned buffers: no host's memory grows with the tables.  All ranks allocate what a range needs first and agree on it:
+ * when one cannot, every rank returns KATGPU_ERR_NOMEM (katgpu_last_error names the rank), nothing has been created at `path` and
+ * the communicator is as usable as before; KATGPU_ERR_NOMEM is returned on every rank or on none.  A later failure is an error on
+ * every rank (rank 0 cannot open the file: KATGPU_ERR_IO on all, agreed before a run travels), and the file is removed.
+ * KATGPU_TIMING: rank 0 prints one line, katgpu_timing {"phase": "jf_dump_gathered", ...}. */
+int  katgpu_jf_dump_gathered(katgpu_comm* comm, katgpu_table* t, const char* path);
 /* wall time spent so far in extraction / on the wire (posting + waiting) / merging / all-reducing (ms), bytes sent, merge calls */
 int  katgpu_comm_stats(katgpu_comm* comm, double* ms_extract, double* ms_exchange, double* ms_merge, double* ms_allreduce,
                        uint64_t* bytes_sent, uint64_t* merge_launches);

@@ -42,7 +42,7 @@ EXPORTS = (
     "katgpu_table_filter", "katgpu_table_seq_hits_host", "katgpu_table_seq_hits_device",
     "katgpu_table_record_stats_host", "katgpu_table_record_stats_device", "katgpu_table_jf_records_device", "katgpu_table_jf_records_device_wide",
     "katgpu_table_add_jf_records_device", "katgpu_jf_load_part",
-    "katgpu_table_record_regions_host", "katgpu_table_record_regions_device",
+    "katgpu_table_record_regions_host", "katgpu_table_record_regions_device", "katgpu_jf_dump_gathered",
 )
 
 # katgpu_record_stats: one record of Table.record_stats
@@ -855,6 +855,7 @@ class Comm:
         L.katgpu_exchange_begin.argtypes = [C.c_void_p, C.c_void_p]
         L.katgpu_exchange_finish.argtypes = [C.c_void_p, C.c_void_p]
         L.katgpu_allreduce_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.katgpu_jf_dump_gathered.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
         L.katgpu_comm_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_uint64)] * 2
         L.katgpu_comm_wire.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         h = C.c_void_p()
@@ -902,6 +903,12 @@ class Comm:
             out.append(flat[o:o + n].reshape(a.shape).copy())
             o += n
         return out
+
+    def jf_dump_gathered(self, table, path):
+        """Collective: the ranks' tables (disjoint k-mers, as exchange_merge leaves them) in the one .jf file rank 0 writes at `path`."""
+        rc = self.engine.L.katgpu_jf_dump_gathered(self.h, table.h, os.fsencode(path))
+        if rc:
+            raise KatGpuError(rc, self.engine.L.katgpu_jf_last_error().decode(errors="replace") or self.engine.L.katgpu_last_error(self.engine.h).decode(errors="replace"))
 
     def stats(self):
         d = [C.c_double() for _ in range(4)]

@@ -228,8 +228,10 @@ void InputHandler::validateMerLen(uint16_t expected) {                      // l
                                  ".  Key length was " + std::to_string(katgpu_table_k(hash)) + " for : " + input[0]);
 }
 
-// --gpus N: every rank holds the k-mers it owns.  The ranks are processes of one node (kat_main.cc forks them): the others leave their
-// records in a file beside the output, rank 0 puts them together with its own and writes the one sorted .jf the reference writes.
+// --gpus N: every rank holds the k-mers it owns, and katgpu_jf_dump_gathered writes the one sorted .jf the reference writes from the
+// ranks' devices.  This is what is left for the case that a rank has no memory for that (all ranks then agree to come here): the
+// ranks are processes of one node (kat_main.cc forks them), the others leave their records in a file beside the output, rank 0 puts
+// them together with its own on the host.
 static int dump_gathered(katgpu_table* hash, const std::string& outputPath) {
     const int rank = Engine::rank(), world = Engine::world();
     const bool wide = katgpu_table_k(hash) > 32;
@@ -280,7 +282,11 @@ void InputHandler::dump(const std::string& outputPath, uint16_t threads) {  // l
         auto t0 = std::chrono::steady_clock::now();
         std::cout << "Dumping hash to " << outputPath << " ...";
         std::cout.flush();
-        int rc = Engine::dist() && Engine::world() > 1 ? dump_gathered(hash, outputPath) : katgpu_jf_dump(hash, outputPath.c_str());
+        int rc;
+        if (Engine::dist() && Engine::world() > 1) {
+            rc = katgpu_jf_dump_gathered(Engine::comm(), hash, outputPath.c_str());
+            if (rc == KATGPU_ERR_NOMEM) rc = dump_gathered(hash, outputPath);      // (the library returns it on every rank or on none, and before anything exists at the path)
+        } else rc = katgpu_jf_dump(hash, outputPath.c_str());
         if (rc) throw JellyfishException(*katgpu_jf_last_error() ? katgpu_jf_last_error() : katgpu_last_error(Engine::ctx()));
         std::cout << " done.";
         double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();

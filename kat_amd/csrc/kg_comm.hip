@@ -131,7 +131,7 @@ static const double g_comm_gone_grace_ms = 1e3 * (getenv("KATGPU_COMM_GONE_GRACE
 static double comm_max_wait_ms() { static const double v = 1e3 * (getenv("KATGPU_COMM_MAX_WAIT_S") ? std::max(0.0, atof(getenv("KATGPU_COMM_MAX_WAIT_S"))) : 0.0); return v; }
 constexpr int BEAT_PERIOD_MS = 50;
 
-struct Msg { int peer; void* dev; size_t bytes; };          // one side of a point-to-point transfer (device memory)
+using Msg = CommMsg;                                        // one side of a point-to-point transfer (kg_host.hpp)
 
 }  // namespace
 
@@ -370,6 +370,14 @@ uint32_t host_owner_of(uint64_t key, uint32_t k, uint32_t n_parts) {          //
 double wall_ms() { return now_ms(); }
 
 }  // namespace
+
+// ---- what kg_jf_device.hip uses (kg_host.hpp) ----
+int comm_transfer(katgpu_comm* m, const std::vector<CommMsg>& sends, const std::vector<CommMsg>& recvs) {
+    int rc = transfer(m, sends, recvs, m->ev[0]);
+    if (!rc) rc = transfer_wait(m, m->ev[0]);
+    return rc;
+}
+void comm_abort(katgpu_comm* m) { if (m->hdr) m->hdr->aborted.store(1, std::memory_order_release); }
 
 // ------------------------------------------------------------------ the communicator ------------------
 

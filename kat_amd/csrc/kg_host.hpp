@@ -335,6 +335,14 @@ int for_record_batches(katgpu_ctx* c, const char* bases, size_t n, const uint64_
     return KATGPU_OK;
 }
 
+// What the gathered .jf dump (kg_jf_device.hip) asks of the communicator (kg_comm.hip): the transport's grouped point-to-point transfer.
+struct CommMsg { int peer; void* dev; size_t bytes; };          // one side of a point-to-point transfer (device memory)
+// A group of transfers, every rank of the communicator together, done when it returns (waited for under the liveness checks).  A
+// message of no bytes is not sent; the n-th message to a peer meets the n-th from it.
+int comm_transfer(katgpu_comm* m, const std::vector<CommMsg>& sends, const std::vector<CommMsg>& recvs);
+// this rank gives up inside a collective: its peers leave their waits with an error instead of waiting for it
+void comm_abort(katgpu_comm* m);
+
 // What a stream of .jf records between a file and the device runs on: a copy stream beside the context's and up to two slots of a device buffer, a
 // pinned buffer of that size and four events.  alloc(void**, bytes) makes a device buffer; pooled: pool_release gives it back, else hipFree.
 // Going out of scope waits for both streams and gives everything back.

@@ -397,3 +397,44 @@ extern "C" int katgpu_jf_dump(katgpu_table* t, const char* path) {
     if (n) { rc = katgpu_table_export(t, keys.data(), counts.data(), n, &n); if (rc) return rc; }
     return katgpu_jf_write_records(path, katgpu_table_k(t), katgpu_table_canonical(t), keys.data(), counts.data(), n);
 }
+
+// Host, rank 0: the two pinned buffers of a range (at most 2^25 records each) and the 2^16 position counters; the other ranks: the
+// counters.  Device, rank 0: a range's gathered runs, the scratch that orders them and two output buffers; the others: their run of a
+// range and its scratch.  None of it grows with the tables.
+extern "C" int katgpu_jf_dump_gathered(katgpu_comm* comm, katgpu_table* t, const char* path) {
+    if (!comm || !t) return KATGPU_ERR_INVALID_ARG;
+    const int rank = katgpu_comm_rank(comm), world = katgpu_comm_world(comm);
+    if (rank == 0 && !path) return KATGPU_ERR_INVALID_ARG;
+    g_jf_err.clear();
+    timespec t0, t1;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    size_t n = 0;
+    const uint32_t k = katgpu_table_k(t);
+    int rc = k > 32 ? katgpu_table_export_wide(t, nullptr, nullptr, nullptr, 0, &n) : katgpu_table_export(t, nullptr, nullptr, 0, &n);
+    // (a rank that cannot count its table says so where its peers will look: the sum then cannot be a table's)
+    uint64_t sums[2] = {rc ? 0 : (uint64_t)n, rc ? 1u : 0u};
+    const int crc = katgpu_allreduce_u64(comm, sums, 2);
+    if (rc || crc) return rc ? rc : crc;
+    if (sums[1]) return KATGPU_ERR_DEVICE;
+    const uint64_t n_total = sums[0];
+    const JfGeometry g = jf_geometry(k, (size_t)n_total);       // what one process holding the union would write
+    FILE* f = nullptr;
+    JfGatherTiming tm;
+    rc = jf_stream_gathered(comm, t, g.r, g.cols.data(), n_total, [&]() -> FILE* {
+        f = fopen(path, "wb");
+        if (f && !write_header(f, k, katgpu_table_canonical(t), g)) { fclose(f); f = nullptr; unlink(path); }
+        if (!f) g_jf_err = std::string("cannot open ") + path + " for writing";
+        return f;
+    }, &tm);
+    if (f) {
+        const bool ok = fclose(f) == 0;
+        if (rc == KATGPU_OK && !ok) { rc = KATGPU_ERR_IO; tm.write_failed = true; }
+        if (rc) unlink(path);                                    // (not a file to be taken for a hash)
+        if (tm.write_failed) g_jf_err = std::string("write error on ") + path;      // (any other failure: katgpu_last_error says which)
+    }
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    if (rc == KATGPU_OK && rank == 0 && getenv("KATGPU_TIMING"))
+        fprintf(stderr, "katgpu_timing {\"phase\": \"jf_dump_gathered\", \"records\": %llu, \"ranges\": %u, \"ranks\": %d, \"device_s\": %.3f, \"wire_s\": %.3f, \"copy_s\": %.3f, \"write_s\": %.3f, \"total_s\": %.3f}\n",
+                (unsigned long long)n_total, tm.ranges, world, tm.device_s, tm.wire_s, tm.copy_s, tm.write_s, (double)(t1.tv_sec - t0.tv_sec) + (t1.tv_nsec - t0.tv_nsec) * 1e-9);
+    return rc;
+}

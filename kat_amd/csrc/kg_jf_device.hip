@@ -1,5 +1,6 @@
 // kg_jf_device.hip -- the device side of the .jf writer and reader (kg_jf.cpp): a table's records selected, ordered by their position in
-// the file and packed (katgpu_table_jf_records_device[_wide]; jf_stream_records, range by range into a file), and packed records unpacked and
+// the file and packed (katgpu_table_jf_records_device[_wide]; jf_stream_records, range by range into a file; jf_stream_gathered,
+// the same for the disjoint tables of a communicator's ranks, their runs gathered on rank 0's device), and packed records unpacked and
 // added to a table (katgpu_table_add_jf_records_device; jf_stream_load, chunk by chunk out of a file).
 #include "kg_host.hpp"
 #include "kg_jf_records.hpp"
@@ -32,6 +33,7 @@ struct JfScratch {
     }
 };
 struct JfRange { uint64_t lo, hi, n; };
+struct JfRuns { const uint8_t* recs; uint64_t n; };   // n packed records of the table's k in device memory, from any byte address on: sorted runs behind one another
 template <bool W> constexpr size_t jf_scratch_bytes = W ? 28 : 20;
 }
 
@@ -56,18 +58,30 @@ static uint32_t jf_bucket_shift(uint64_t distinct, uint32_t r) {
     return s;
 }
 
-template <bool W>
-static void jf_launch_select_hist(katgpu_table* t, const JfRows<W>& m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift, uint32_t* hist) {
+// J1 over either source: the table's slots, or (runs) packed records in device memory
+template <int MODE, bool W>
+static void jf_launch_select(katgpu_table* t, const JfRuns* runs, const JfRows<W>& m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift,
+                             uint32_t* hist_or_cursor, unsigned long long* total, uint64_t* d_pos, uint64_t* d_hi, uint64_t* d_key, uint32_t* d_cnt) {
     katgpu_ctx* c = t->ctx;
-    hipLaunchKernelGGL((k_jf_select<0, W>), dim3(grid_for(c, t->dev().cap + 1, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, t->dev(), t->n_ovf, m, r, pos_lo, pos_hi, shift,
-                       hist, (unsigned long long*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
+    if (runs) {
+        const dim3 grid((unsigned)std::max<uint64_t>(std::min<uint64_t>((runs->n + JR_TILE - 1) / JR_TILE, (uint64_t)c->n_cu * 8), 1));
+        hipLaunchKernelGGL((k_jf_select_runs<MODE, W>), grid, dim3(JF_BLOCK), 0, c->stream, runs->recs, runs->n, 2 * t->dv.k, m, r, pos_lo, pos_hi, shift,
+                           hist_or_cursor, total, d_pos, d_hi, d_key, d_cnt);
+    } else
+        hipLaunchKernelGGL((k_jf_select<MODE, W>), dim3(grid_for(c, t->dev().cap + 1, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, t->dev(), t->n_ovf, m, r, pos_lo, pos_hi, shift,
+                           hist_or_cursor, total, d_pos, d_hi, d_key, d_cnt);
+}
+template <bool W>
+static void jf_launch_select_hist(katgpu_table* t, const JfRows<W>& m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift, uint32_t* hist, const JfRuns* runs = nullptr) {
+    jf_launch_select<0, W>(t, runs, m, r, pos_lo, pos_hi, shift, hist, nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 // Select, order and pack the records of [pos_lo, pos_hi) into dev_out (room for `cap` records).  Synchronises once, to learn how many
-// the range holds (*n_out); the scatter, the sort and the pack are left running on the compute stream.
+// the range holds (*n_out); the scatter, the sort and the pack are left running on the compute stream.  The records are the table's, or
+// (runs) those of packed runs, of t's k, no two of them equal: t then lends its context and the result slot of its counters.
 template <bool W>
 static int jf_range(katgpu_table* t, const JfRows<W>& m, uint32_t r, uint32_t shift, uint64_t pos_lo, uint64_t pos_hi, uint8_t* dev_out, size_t cap,
-                    size_t* n_out, JfScratch& s) {
+                    size_t* n_out, JfScratch& s, const JfRuns* runs = nullptr) {
     katgpu_ctx* c = t->ctx;
     *n_out = 0;
     if (pos_lo == pos_hi) return KATGPU_OK;
@@ -79,7 +93,7 @@ static int jf_range(katgpu_table* t, const JfRows<W>& m, uint32_t r, uint32_t sh
     unsigned long long* res = (unsigned long long*)&t->dev().ctrs[CTR_SCRATCH];
     const DevTable dv = t->dev();
     HIPCHK(c, hipMemsetAsync(hist, 0, (size_t)nb * sizeof(uint32_t), c->stream));
-    jf_launch_select_hist(t, m, r, pos_lo, pos_hi, shift, hist);
+    jf_launch_select_hist(t, m, r, pos_lo, pos_hi, shift, hist, runs);
     hipLaunchKernelGGL(k_jf_scan, dim3(1), dim3(JF_SCAN_BLOCK), 0, c->stream, hist, nb, off, cursor, res);
     unsigned long long h[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -94,8 +108,7 @@ static int jf_range(katgpu_table* t, const JfRows<W>& m, uint32_t r, uint32_t sh
     uint32_t* d_cnt = (uint32_t*)(d_key + s.rec_cap);
     const uint32_t key_bytes = (2 * dv.k + 7) / 8;
     // (none of these launches is booked under a kernel class of katgpu_profile_get: the dump reports its own phases, katgpu_timing "jf_dump")
-    hipLaunchKernelGGL((k_jf_select<1, W>), dim3(grid_for(c, dv.cap + 1, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, dv, t->n_ovf, m, r, pos_lo, pos_hi, shift,
-                       cursor, (unsigned long long*)nullptr, d_pos, d_hi, d_key, d_cnt);
+    jf_launch_select<1, W>(t, runs, m, r, pos_lo, pos_hi, shift, cursor, nullptr, d_pos, d_hi, d_key, d_cnt);
     // The ranking path compares every record of an oversized bucket with the whole bucket.  That is for the odd run of equal positions,
     // not for a matrix that piles a table onto a few of them: beyond JF_RANK_MAX records in one bucket the range is refused.
     if (h[1] > JF_RANK_MAX)
@@ -124,8 +137,7 @@ static int jf_records_device(katgpu_table* t, uint32_t r, const uint64_t* cols, 
     if (!dev_out || !cap_records) {
         unsigned long long* total = (unsigned long long*)&t->dev().ctrs[CTR_SCRATCH];
         HIPCHK(c, hipMemsetAsync(total, 0, sizeof(uint64_t), c->stream));
-        hipLaunchKernelGGL((k_jf_select<2, W>), dim3(grid_for(c, t->dev().cap + 1, JF_BLOCK, 8)), dim3(JF_BLOCK), 0, c->stream, t->dev(), t->n_ovf, m, r, pos_lo, pos_hi, 0u,
-                           (uint32_t*)nullptr, total, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr);
+        jf_launch_select<2, W>(t, nullptr, m, r, pos_lo, pos_hi, 0u, nullptr, total, nullptr, nullptr, nullptr, nullptr);
         unsigned long long h = 0;
         HIPCHK(c, hipMemcpyAsync(&h, total, sizeof h, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -247,6 +259,226 @@ static int jf_stream(katgpu_table* t, uint32_t r, const uint64_t* cols, FILE* f,
 
 int jf_stream_records(katgpu_table* t, uint32_t r, const uint64_t* cols, FILE* f, JfDumpTiming* tm) {
     return t->dv.keys_b ? jf_stream<true>(t, r, cols, f, tm) : jf_stream<false>(t, r, cols, f, tm);
+}
+
+// ------------------------------------------------------------------ .jf records of several ranks' tables ----
+
+static const int64_t g_jf_gather_nomem = hook("KATGPU_TEST_JF_GATHER_NOMEM") ? atoll(hook("KATGPU_TEST_JF_GATHER_NOMEM")) : -1;   // tests: this rank reports that it could not allocate
+
+// one word per rank, all-reduced: *who = the first rank whose word is not 0, or -1, and *what = that word
+static int jf_gather_agree(katgpu_comm* m, uint64_t mine, int* who, uint64_t* what = nullptr) {
+    const int rank = katgpu_comm_rank(m), world = katgpu_comm_world(m);
+    std::vector<uint64_t> flags((size_t)world, 0);
+    flags[rank] = mine;
+    const int rc = katgpu_allreduce_u64(m, flags.data(), flags.size());
+    *who = -1;
+    for (int p = world - 1; p >= 0; --p) if (flags[p]) { *who = p; if (what) *what = flags[p]; }
+    return rc;
+}
+
+// The ranks' tables hold disjoint k-mers: every rank orders and packs its records of a range of positions (jf_range), the runs travel
+// to rank 0 (one grouped transfer per range), which orders and packs their union from the runs (jf_range over JfRuns, buckets sized
+// for n_total) and streams it into the file as jf_stream does.  kg_jf.hpp says what the callers see.
+template <bool W>
+static int jf_gather(katgpu_comm* m, katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t n_total, const std::function<FILE*()>& open, JfGatherTiming* tm) {
+    katgpu_ctx* c = t->ctx;
+    const int rank = katgpu_comm_rank(m), world = katgpu_comm_world(m);
+    const uint32_t k = t->dv.k, rb = (2 * k + 7) / 8 + 4;
+    const JfRows<W> rows = jf_rows<W>(k, r, cols);
+    JfScratch s;
+    int who = -1;
+    FILE* f = nullptr;
+    uint64_t written = 0;
+    std::vector<JfRange> ranges;
+    std::vector<uint64_t> per_rank;                               // [world x n_ranges]: the records of rank p in range g
+    // what went wrong on this rank is kept until everyone has heard of it: a rank that left early would leave its peers in a collective
+    auto current = [&]() -> int { HIPCHK(c, hipSetDevice(c->device)); return refresh_counters(t); };
+    int rc = current();
+    const uint64_t distinct = rc ? 0 : t->distinct;
+    // senders size their buckets for their own records, rank 0 for the union it orders (its own run comes out the same under either)
+    const uint32_t shift = jf_bucket_shift(rank == 0 ? n_total : distinct, r);
+
+    // ---- cuts everyone agrees on: the all-reduced histogram over 2^min(r, 16) stretches, cut from rank 0's target of records per range ----
+    const uint32_t cb = std::min<uint32_t>(r, 16), cshift = r - cb;
+    const size_t nbins = (size_t)1 << cb;
+    std::vector<uint32_t> bins(nbins, 0);
+    std::vector<uint64_t> all(nbins + 1, 0);
+    auto histogram = [&]() -> int {
+        if (!distinct) return KATGPU_OK;
+        if (!s.ensure(c, s.hist, s.nb_cap, nbins, (nbins * 3 + 1) * sizeof(uint32_t))) return fail(c, KATGPU_ERR_NOMEM, "jf dump: no device memory for %zu position counters", nbins);
+        HIPCHK(c, hipMemsetAsync(s.hist, 0, nbins * sizeof(uint32_t), c->stream));
+        jf_launch_select_hist(t, rows, r, 0, 1ULL << r, cshift, s.hist);
+        HIPCHK(c, hipMemcpyAsync(bins.data(), s.hist, nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        uint64_t sum = 0;
+        for (uint32_t b : bins) sum += b;
+        if (sum != distinct) return fail(c, KATGPU_ERR_DEVICE, "jf dump: the position histogram holds %llu records, the table %llu", (unsigned long long)sum, (unsigned long long)distinct);
+        return KATGPU_OK;
+    };
+    if (!rc) rc = histogram();
+    if (rc) std::fill(bins.begin(), bins.end(), 0);
+    for (size_t b = 0; b < nbins; ++b) all[b] = bins[b];
+    if (rank == 0) {
+        // a range's records on rank 0: 20 bytes (wide: 28) to order them, 4 should they need ranking, their bytes as gathered runs and in each of the
+        // two output buffers.  Half of what is free, and at most 2^25 records, as jf_stream has it.
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+        uint64_t want = std::min<uint64_t>(std::max<uint64_t>(free_b / 2 / (jf_scratch_bytes<W> + 4 + 3 * rb), 1 << 16), 1 << 25);
+        if (g_jf_range_records) want = g_jf_range_records;
+        all[nbins] = want;
+    }
+    const std::string err_local = rc ? c->err : std::string();
+    int crc = katgpu_allreduce_u64(m, all.data(), all.size());
+    uint64_t what = 0;                                            // 1: no memory for the position counters (as collective as the agreement below), 2: anything else
+    if (!crc) crc = jf_gather_agree(m, rc == KATGPU_ERR_NOMEM ? 1 : rc ? 2 : 0, &who, &what);
+    if (crc) return rc ? rc : crc;                                // (the communicator itself failed: its waits have ended on every rank)
+    if (who >= 0) {
+        if (rc) { c->err = err_local; return rc; }
+        if (what == 1) return fail(c, KATGPU_ERR_NOMEM, "jf dump: rank %d of %d has no device memory for its position counters", who, world);
+        return fail(c, KATGPU_ERR_DEVICE, "jf dump: rank %d could not read its table's positions", who);
+    }
+    {
+        const uint64_t want = std::max<uint64_t>(all[nbins], 1);
+        uint64_t acc = 0, start = 0, sum = 0;
+        for (size_t b = 0; b < nbins; ++b) {
+            if (acc && acc + all[b] > want) { ranges.push_back({start << cshift, (uint64_t)b << cshift, acc}); start = b; acc = 0; }
+            acc += all[b]; sum += all[b];
+        }
+        ranges.push_back({start << cshift, 1ULL << r, acc});
+        if (sum != n_total) return fail(c, KATGPU_ERR_DEVICE, "jf dump: the ranks' position histograms hold %llu records, their tables %llu", (unsigned long long)sum, (unsigned long long)n_total);
+    }
+    const size_t G = ranges.size();
+    per_rank.assign((size_t)world * G, 0);
+    for (size_t g = 0; g < G; ++g)
+        for (uint64_t b = ranges[g].lo >> cshift; b < (ranges[g].hi >> cshift); ++b) per_rank[(size_t)rank * G + g] += bins[b];
+    crc = katgpu_allreduce_u64(m, per_rank.data(), per_rank.size());     // every receive's size is known before it is posted
+    if (crc) return crc;
+    auto of = [&](int p, size_t g) { return per_rank[(size_t)p * G + g]; };
+
+    // ---- everything a range can need, before a byte is written: all ranks go on, or none does ----
+    uint64_t max_all = 0, max_own = 0, max_gather = 0, max_nb = 1;
+    for (size_t g = 0; g < G; ++g) {
+        max_all = std::max(max_all, ranges[g].n); max_own = std::max(max_own, of(rank, g));
+        if (ranges[g].n > of(0, g)) max_gather = std::max(max_gather, ranges[g].n);
+        max_nb = std::max(max_nb, ((ranges[g].hi - ranges[g].lo - 1) >> shift) + 1);
+    }
+    const uint64_t max_n = rank == 0 ? max_all : max_own;         // the most records this rank orders at once
+    const int nbuf = G > 1 ? 2 : 1;
+    JfSlots io(c);                                                // rank 0: events of a slot: range started, produced, copied; senders: one device buffer, their run
+    struct Dev { uint8_t* p = nullptr; ~Dev() { hipFree(p); } } gather;
+    hipEvent_t wire_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // rank 0, per slot: its own run done, the runs' ordering started
+    struct Events { hipEvent_t (&e)[2][2]; ~Events() { for (auto& a : e) for (hipEvent_t x : a) if (x) hipEventDestroy(x); } } wire_events{wire_ev};
+    bool have = max_all < (1ULL << 31) && max_nb < (1ULL << 31);  // (a matrix that piles the tables onto one stretch of positions)
+    if (have && max_n) have = s.ensure(c, s.hist, s.nb_cap, (size_t)max_nb, ((size_t)max_nb * 3 + 1) * sizeof(uint32_t)) && s.ensure(c, s.recs, s.rec_cap, (size_t)max_n, (size_t)max_n * jf_scratch_bytes<W>) &&
+                             s.ensure(c, s.rank, s.rank_cap, (size_t)max_n, (size_t)max_n * sizeof(uint32_t));   // (should a bucket need ranking: nothing is allocated once the file is open)
+    if (have && rank == 0) {
+        have = io.setup(nbuf, std::max<size_t>((size_t)max_all * rb, 1), false, [&](void** p, size_t bytes) { return jf_malloc(c, p, bytes); });
+        if (have && max_gather) have = jf_malloc(c, (void**)&gather.p, (size_t)max_gather * rb) == hipSuccess;
+        for (auto& a : wire_ev) for (hipEvent_t& x : a) if (have) have = hipEventCreate(&x) == hipSuccess;
+    } else if (have && max_own) have = jf_malloc(c, (void**)&io.slot[0].dev, (size_t)max_own * rb) == hipSuccess;
+    if (!have) (void)hipGetLastError();
+    if (g_jf_gather_nomem == rank) have = false;
+    crc = jf_gather_agree(m, have ? 0 : 1, &who);
+    if (crc) return crc;
+    if (who >= 0) return fail(c, KATGPU_ERR_NOMEM, "jf dump: rank %d of %d has no device or pinned memory for the buffers of a range (%llu records at most)", who, world, (unsigned long long)max_all);
+
+    // ---- the ranges.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end, and the last
+    // all-reduce tells everyone that the file is not to be trusted ----
+    int pend = -1, slot = 0;
+    size_t pend_n = 0;
+    bool pend_remote = false;
+    auto drain = [&]() -> int {                                   // the copy of the range before this one has landed: write it
+        if (pend < 0) return KATGPU_OK;
+        const hipEvent_t* ev = io.slot[pend].ev;
+        HIPCHK(c, hipEventSynchronize(ev[2]));
+        float ms = 0;
+        if (!pend_remote) { if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) tm->device_s += ms * 1e-3; }
+        else {
+            if (hipEventElapsedTime(&ms, ev[0], wire_ev[pend][0]) == hipSuccess) tm->device_s += ms * 1e-3;
+            if (hipEventElapsedTime(&ms, wire_ev[pend][1], ev[1]) == hipSuccess) tm->device_s += ms * 1e-3;
+        }
+        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) tm->copy_s += ms * 1e-3;
+        const double t0 = now_ms();
+        const bool ok = fwrite(io.slot[pend].pinned, rb, pend_n, f) == pend_n;
+        tm->write_s += (now_ms() - t0) * 1e-3;
+        written += pend_n; pend = -1;
+        if (!ok) { tm->write_failed = true; return fail(c, KATGPU_ERR_IO, "jf dump: short write to the output file"); }
+        return KATGPU_OK;
+    };
+    // this rank's run of a range, ordered and packed into dst
+    auto own_run = [&](const JfRange& g, uint64_t expect, uint8_t* dst) -> int {
+        size_t n = 0;
+        int x = jf_range(t, rows, r, shift, g.lo, g.hi, dst, (size_t)max_n, &n, s);
+        if (!x && n != expect) x = fail(c, KATGPU_ERR_DEVICE, "jf dump: positions [%llu, %llu) hold %zu records on rank %d, their histogram said %llu", (unsigned long long)g.lo, (unsigned long long)g.hi, n, rank, (unsigned long long)expect);
+        return x;
+    };
+    // before a transfer: the run to travel is packed, and (rank 0) the range before this one has been read out of the gather buffer
+    auto settled = [&]() -> int { HIPCHK(c, hipStreamSynchronize(c->stream)); return KATGPU_OK; };
+    // rank 0 opens the file, and everyone hears of it before a run is posted: a sender must not be left with a transfer nobody takes
+    crc = jf_gather_agree(m, rank == 0 && !(f = open()) ? 1 : 0, &who);
+    if (crc) return crc;
+    if (who >= 0) return fail(c, KATGPU_ERR_IO, "jf dump: rank 0 cannot open the output file");
+    for (size_t gi = 0; !rc && gi < G && n_total; ++gi) {
+        const JfRange& g = ranges[gi];
+        const uint64_t own = of(rank, gi), remote = g.n - of(0, gi);
+        if (rank != 0) {
+            if (own) rc = own_run(g, own, io.slot[0].dev);
+            if (!rc && own) rc = settled();
+            std::vector<CommMsg> sends;
+            if (own) sends.push_back({0, io.slot[0].dev, (size_t)own * rb});
+            if (!rc && remote) rc = comm_transfer(m, sends, {});
+            continue;
+        }
+        const JfSlots::Slot& b = io.slot[slot];
+        hipEventRecord(b.ev[0], c->stream);
+        if (own) rc = own_run(g, own, remote ? gather.p : b.dev);
+        if (!rc && remote) {
+            // the remote runs behind rank 0's own, in rank order: a run starts wherever the one before it ended
+            hipEventRecord(wire_ev[slot][0], c->stream);
+            rc = settled();
+            if (rc) break;
+            std::vector<CommMsg> recvs;
+            uint64_t at = own;
+            for (int p = 1; p < world; ++p) { recvs.push_back({p, gather.p + at * rb, (size_t)of(p, gi) * rb}); at += of(p, gi); }
+            const double t0 = now_ms();
+            rc = comm_transfer(m, {}, recvs);
+            tm->wire_s += (now_ms() - t0) * 1e-3;
+            if (rc) break;
+            hipEventRecord(wire_ev[slot][1], c->stream);
+            const JfRuns runs{gather.p, g.n};
+            size_t n = 0;
+            rc = jf_range(t, rows, r, shift, g.lo, g.hi, b.dev, (size_t)max_n, &n, s, &runs);
+            if (!rc && n != g.n) rc = fail(c, KATGPU_ERR_DEVICE, "jf dump: %zu of the %llu gathered records lie in positions [%llu, %llu)", n, (unsigned long long)g.n, (unsigned long long)g.lo, (unsigned long long)g.hi);
+        }
+        if (rc) break;
+        if (g.n) {
+            hipEventRecord(b.ev[1], c->stream);
+            hipStreamWaitEvent(io.copy, b.ev[1], 0);
+            const hipError_t e = hipMemcpyAsync(b.pinned, b.dev, g.n * rb, hipMemcpyDeviceToHost, io.copy);
+            hipEventRecord(b.ev[2], io.copy);
+            if (e != hipSuccess) { rc = fail(c, KATGPU_ERR_DEVICE, "jf dump: %s", hipGetErrorString(e)); break; }
+        }
+        rc = drain();                                             // (while this range is ordered and copied)
+        if (rc) break;
+        if (g.n) { pend = slot; pend_n = (size_t)g.n; pend_remote = remote != 0; slot = (slot + 1) % nbuf; }
+        ++tm->ranges;
+    }
+    if (rank == 0 && f) {
+        if (!rc) rc = drain();
+        if (!rc && written != n_total) rc = fail(c, KATGPU_ERR_DEVICE, "jf dump: wrote %llu of %llu records", (unsigned long long)written, (unsigned long long)n_total);
+    }
+    if (rc == KATGPU_ERR_NOMEM) rc = KATGPU_ERR_DEVICE;           // (not the collective one: the file is open, the peers get an error too)
+    const std::string err_mine = rc ? c->err : std::string();
+    if (rc) comm_abort(m);
+    crc = jf_gather_agree(m, rc ? 1 : 0, &who);
+    if (rc) { c->err = err_mine; return rc; }
+    if (crc) return crc;
+    if (who >= 0) return fail(c, KATGPU_ERR_DEVICE, "jf dump: rank %d failed, the file is incomplete", who);
+    return KATGPU_OK;
+}
+
+int jf_stream_gathered(katgpu_comm* m, katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t n_total, const std::function<FILE*()>& open, JfGatherTiming* tm) {
+    return t->dv.keys_b ? jf_gather<true>(m, t, r, cols, n_total, open, tm) : jf_gather<false>(m, t, r, cols, n_total, open, tm);
 }
 
 // ------------------------------------------------------------------ .jf records into a table ----

@@ -35,6 +35,24 @@ __device__ __forceinline__ uint64_t lds_u64(const uint32_t* img, uint32_t at) {
 
 __device__ __forceinline__ uint64_t low_bits(uint32_t n) { return n >= 64 ? ~0ULL : (1ULL << n) - 1; }     // n = 0: none
 
+// The n_words aligned 16-byte words from `base` on, which cover a tile of the packed records in [first, last), to LDS: one 16-byte load
+// per lane (a wave reads 1 KB in a row).  Words inside the buffer, the ones a tile shares with its neighbours included, are loaded
+// whole; the at most two words that hang over the buffer's ends are put together from the bytes that belong to it.
+__device__ __forceinline__ void jf_tile_image(uint4* s_img, uintptr_t first, uintptr_t last, uintptr_t base, uint32_t n_words, uint32_t tid, uint32_t block) {
+    for (uint32_t w = tid; w < n_words; w += block) {
+        const uintptr_t a = base + (uintptr_t)w * 16;
+        uint4 v;
+        if (a >= first && a + 16 <= last) v = *reinterpret_cast<const uint4*>(a);
+        else {
+            uint32_t d[4] = {0, 0, 0, 0};
+            for (uint32_t x = 0; x < 16; ++x)
+                if (a + x >= first && a + x < last) d[x >> 2] |= (uint32_t)*reinterpret_cast<const uint8_t*>(a + x) << (8 * (x & 3));
+            v = make_uint4(d[0], d[1], d[2], d[3]);
+        }
+        s_img[w] = v;
+    }
+}
+
 // L1.  recs .. recs + n * (key_bytes + counter_len) is device memory; nothing outside it is read.
 template <bool W>
 __global__ void __launch_bounds__(JL_BLOCK)
@@ -53,20 +71,7 @@ k_jf_add(DevTable dst, const uint8_t* __restrict__ recs, uint64_t n, uint32_t ke
         const uintptr_t from = first + r0 * rb, base = from & ~(uintptr_t)15;
         const uint32_t mis = (uint32_t)(from - base);
         const uint32_t n_words = (mis + n_tile * rb + 15) / 16;                               // <= JL_IMG_WORDS - 1
-        // Words inside the buffer, the ones a tile shares with its neighbours included, are loaded whole; the at most two words that
-        // hang over the buffer's ends are put together from the bytes that belong to it.
-        for (uint32_t w = tid; w < n_words; w += JL_BLOCK) {
-            const uintptr_t a = base + (uintptr_t)w * 16;
-            uint4 v;
-            if (a >= first && a + 16 <= last) v = *reinterpret_cast<const uint4*>(a);
-            else {
-                uint32_t d[4] = {0, 0, 0, 0};
-                for (uint32_t x = 0; x < 16; ++x)
-                    if (a + x >= first && a + x < last) d[x >> 2] |= (uint32_t)*reinterpret_cast<const uint8_t*>(a + x) << (8 * (x & 3));
-                v = make_uint4(d[0], d[1], d[2], d[3]);
-            }
-            s_img[w] = v;
-        }
+        jf_tile_image(s_img, first, last, base, n_words, tid, JL_BLOCK);
         __syncthreads();
         for (uint32_t i = tid; i < n_tile; i += JL_BLOCK) {
             const uint32_t at = mis + i * rb;

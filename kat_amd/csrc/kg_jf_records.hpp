@@ -9,6 +9,7 @@
 //  J1 k_jf_select     slot walk: rebuild the key, position = parity(key & row) per matrix row, keep [pos_lo, pos_hi);
 //                     <2> counts the range, <0> histograms it over buckets of 2^shift positions, <1> scatters (pos, [hi,] key, count)
 //                     records to their bucket's stretch of the scratch segment
+//     k_jf_select_runs  the same three modes over packed records in device memory (sorted runs gathered from several tables)
 //  J2 k_jf_scan       exclusive scan of the bucket histogram (one workgroup), the total and the largest bucket
 //  J3 k_jf_rank       buckets beyond one LDS tile only: a record's rank among its bucket, by comparison with all of it (global memory)
 //  J4 k_jf_sort_pack  one workgroup per bucket: bitonic sort of the bucket on (pos, [hi,] key) in LDS (or, for a ranked bucket, a gather
@@ -19,6 +20,7 @@
 // maps many keys to few positions sends work through J3.  Integer and byte work bound by the table walk; no MFMA.
 #pragma once
 #include "kg_device.hpp"
+#include "kg_jf_load.hpp"
 
 namespace kg {
 
@@ -50,13 +52,40 @@ __device__ __forceinline__ bool jf_less(uint64_t pa, uint64_t ha, uint64_t ka, u
     return pa != pb ? pa < pb : ha != hb ? ha < hb : ka < kb;
 }
 
-// J1.  MODE 2: *total += records of the range.  MODE 0: ++hist[bucket].  MODE 1: record -> scratch[cursor[bucket]++].
-// A wide table is walked as k_export walks it, and every k-mer of it is in a slot (the all-T 63-mer's first word is 2^63 - 1, not EMPTY).
+// J1, what either source does with one record at position `pos`.  MODE 2: count it.  MODE 0: ++hist[bucket].  MODE 1: record ->
+// scratch[cursor[bucket]++]; count32() is the record's count, saturated to 32 bits, asked for only here.
+struct JfSink {
+    uint32_t* __restrict__ hist_or_cursor; unsigned long long* __restrict__ total;
+    uint64_t* __restrict__ out_pos; uint64_t* __restrict__ out_hi; uint64_t* __restrict__ out_key; uint32_t* __restrict__ out_cnt;
+};
+template <int MODE, bool W, typename Count32>
+__device__ __forceinline__ void jf_put(const JfSink& o, uint64_t pos, uint64_t hi, uint64_t key, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift, uint64_t& mine, Count32&& count32) {
+    if (pos < pos_lo || pos >= pos_hi) return;
+    if (MODE == 2) { ++mine; return; }
+    const uint64_t b = (pos - pos_lo) >> shift;
+    const uint32_t at = atomicAdd(&o.hist_or_cursor[b], 1u);
+    if (MODE == 1) {
+        if constexpr (W) o.out_hi[at] = hi;
+        o.out_pos[at] = pos; o.out_key[at] = key;
+        o.out_cnt[at] = count32();
+    }
+}
+template <int MODE>
+__device__ __forceinline__ void jf_put_total(const JfSink& o, uint64_t mine) {
+    if (MODE == 2) {
+        for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
+        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(o.total, (unsigned long long)mine);
+    }
+}
+
+// J1 over a table.  A wide table is walked as k_export walks it, and every k-mer of it is in a slot (the all-T 63-mer's first word is
+// 2^63 - 1, not EMPTY).
 template <int MODE, bool W>
 __global__ void __launch_bounds__(JF_BLOCK)
 k_jf_select(DevTable t, uint32_t n_ovf, JfRows<W> m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift,
             uint32_t* __restrict__ hist_or_cursor, unsigned long long* __restrict__ total,
             uint64_t* __restrict__ out_pos, uint64_t* __restrict__ out_hi, uint64_t* __restrict__ out_key, uint32_t* __restrict__ out_cnt) {
+    const JfSink o{hist_or_cursor, total, out_pos, out_hi, out_key, out_cnt};
     uint64_t mine = 0;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     const uint64_t end = W ? t.cap : t.cap + 1;
@@ -70,23 +99,53 @@ k_jf_select(DevTable t, uint32_t n_ovf, JfRows<W> m, uint32_t r, uint64_t pos_lo
         }
         else if (i < t.cap) { const SlotView v = slot_view(t, i); if (!v.occ) continue; key = v.key; in_slot = v.cnt; }
         else if (!t.ctrs[CTR_ONES]) continue;                                  // the all-ones k-mer lives beside the slots
-        const uint64_t pos = jf_pos<W>(m, r, hi, key);
-        if (pos < pos_lo || pos >= pos_hi) continue;
-        if (MODE == 2) { ++mine; continue; }
-        const uint64_t b = (pos - pos_lo) >> shift;
-        const uint32_t at = atomicAdd(&hist_or_cursor[b], 1u);
-        if (MODE == 1) {
+        jf_put<MODE, W>(o, jf_pos<W>(m, r, hi, key), hi, key, pos_lo, pos_hi, shift, mine, [&]() {
             uint64_t c;
-            if constexpr (W) { c = slot_count(t, i, n_ovf); out_hi[at] = hi; }
+            if constexpr (W) c = slot_count(t, i, n_ovf);
             else c = i < t.cap ? slot_total(t, i, key, in_slot, n_ovf) : t.ctrs[CTR_ONES];
-            out_pos[at] = pos; out_key[at] = key;
-            out_cnt[at] = c > 0xFFFFFFFFULL ? 0xFFFFFFFFu : (uint32_t)c;       // binary_writer::write saturates
+            return c > 0xFFFFFFFFULL ? 0xFFFFFFFFu : (uint32_t)c;              // binary_writer::write saturates
+        });
+    }
+    jf_put_total<MODE>(o, mine);
+}
+
+// J1 over packed records: the same three modes for n records of key_bytes + 4 bytes that start at any byte address -- sorted runs of
+// several tables laid behind one another (katgpu_jf_dump_gathered).  A workgroup takes JR_TILE consecutive records through LDS as
+// k_jf_add does (kg_jf_load.hpp: 16-byte loads of the aligned words around the tile, a record put together from LDS dwords with
+// shifts); its count is carried as it stands, a packed count is saturated already.  Bound by those reads and by the scatter.
+constexpr uint32_t JR_TILE = 1024;            // records per workgroup pass: 12 KB of LDS (wide: 20 KB)
+template <bool W> constexpr uint32_t JR_IMG_WORDS = JR_TILE * JF_MAX_REC_BYTES<W> / 16 + 2;   // + the tile's misalignment and the slack lds_u64 reads into
+template <int MODE, bool W>
+__global__ void __launch_bounds__(JF_BLOCK)
+k_jf_select_runs(const uint8_t* __restrict__ recs, uint64_t n, uint32_t key_len, JfRows<W> m, uint32_t r, uint64_t pos_lo, uint64_t pos_hi, uint32_t shift,
+                 uint32_t* __restrict__ hist_or_cursor, unsigned long long* __restrict__ total,
+                 uint64_t* __restrict__ out_pos, uint64_t* __restrict__ out_hi, uint64_t* __restrict__ out_key, uint32_t* __restrict__ out_cnt) {
+    __shared__ uint4 s_img[JR_IMG_WORDS<W>];
+    const JfSink o{hist_or_cursor, total, out_pos, out_hi, out_key, out_cnt};
+    const uint32_t* img = reinterpret_cast<const uint32_t*>(s_img);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t key_bytes = (key_len + 7) / 8, rb = key_bytes + 4;          // (the host sends W = false for key_len <= 64 only: rb <= JF_MAX_REC_BYTES<W>)
+    const uint64_t lo_mask = low_bits(key_len), hi_mask = key_len > 64 ? low_bits(key_len - 64) : 0;
+    const uintptr_t first = reinterpret_cast<uintptr_t>(recs), last = first + n * rb;
+    uint64_t mine = 0;
+    const uint64_t n_tiles = (n + JR_TILE - 1) / JR_TILE;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t r0 = tile * JR_TILE;
+        const uint32_t n_tile = n - r0 < JR_TILE ? (uint32_t)(n - r0) : JR_TILE;
+        const uintptr_t from = first + r0 * rb, base = from & ~(uintptr_t)15;
+        const uint32_t mis = (uint32_t)(from - base);
+        jf_tile_image(s_img, first, last, base, (mis + n_tile * rb + 15) / 16, tid, JF_BLOCK);   // <= JR_IMG_WORDS - 1 words
+        __syncthreads();
+        for (uint32_t i = tid; i < n_tile; i += JF_BLOCK) {
+            const uint32_t at = mis + i * rb;
+            const uint64_t key = lds_u64(img, at) & lo_mask;
+            uint64_t hi = 0;
+            if constexpr (W) hi = lds_u64(img, at + 8) & hi_mask;
+            jf_put<MODE, W>(o, jf_pos<W>(m, r, hi, key), hi, key, pos_lo, pos_hi, shift, mine, [&]() { return (uint32_t)lds_u64(img, at + key_bytes); });
         }
+        __syncthreads();
     }
-    if (MODE == 2) {
-        for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off, 64);
-        if ((threadIdx.x & 63) == 0 && mine) atomicAdd(total, (unsigned long long)mine);
-    }
+    jf_put_total<MODE>(o, mine);
 }
 
 // J2.  off[i] = cursor[i] = sum of hist[0..i), off[nb] = the total; res[0] = total (64 bits), res[1] = largest bucket.
