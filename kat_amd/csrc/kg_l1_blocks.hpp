@@ -57,6 +57,27 @@ __device__ __forceinline__ uint32_t l1b_hi_at(uint32_t B, uint32_t s) { return 2
 __device__ __host__ __forceinline__ uint64_t l1b_item_lo(uint64_t i) { const uint64_t blk = i / L1B_ITEMS; const uint32_t s = (uint32_t)(i - blk * L1B_ITEMS); return blk * L1B_BYTES + 12 * (s >> 1) + 4 * (s & 1); }
 __device__ __host__ __forceinline__ uint64_t l1b_item_hi(uint64_t i) { const uint64_t blk = i / L1B_ITEMS; const uint32_t s = (uint32_t)(i - blk * L1B_ITEMS); return blk * L1B_BYTES + 12 * (s >> 1) + 8 + 2 * (s & 1); }
 
+// The per-bucket phase's copy, for both block editions (kg_l2_blocks.hpp's too): a bucket's waiting items move in front of its first block -- a
+// QUAD of lanes per bucket, sixteen bytes each, so that a wave reads a contiguous kilobyte of waiting images per step (one lane copying its
+// bucket's 64 bytes met the same banks as fifteen others, read and write).  A wave copies its OWN lanes' buckets, from the words gb[] it has
+// just written (x's low half non-zero: a block leaves; y: the image of the first): the LDS takes a wave's operations in order.  Called by whole
+// waves.  (The waiting image's dword 15 travels along, unused in a pool image.)
+template <typename Lds>
+__device__ __forceinline__ void blk_move_waiting(Lds& L, uint32_t tid_o) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+        const uint32_t b = (tid_o & ~63u) + 16 * i + ((tid_o & 63) >> 2);
+        const uint2 d = L.gb[b];
+        if (d.x & 0xFFFFu) {
+            const u32x4 a = *reinterpret_cast<const u32x4*>(&L.img[b * 16 + (tid_o & 3) * 4]);
+            *reinterpret_cast<u32x4*>(&L.img[d.y * 16 + (tid_o & 3) * 4]) = a;
+        }
+    }
+}
+
 template <bool STAMP = false /* diagnostic (KATGPU_L1B_STAMP): wave 0's cycles per phase, summed over the workgroups into stamps[0 .. 9] */>
 __global__ void __launch_bounds__(L1B_THREADS)          // four waves per SIMD: one workgroup per CU, 128 registers
 k_p1b_scatter(DevTable t, PartGeom g, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_tiles, uint64_t tiles_per_wg,
@@ -178,10 +199,6 @@ k_p1b_scatter(DevTable t, PartGeom g, const uint8_t* __restrict__ bases, uint64_
                 const bool stuck = nblk != 0 && nst == 0;
                 L.gb[tid_o] = uint2{(L1B_ITEMS * nst) | ((stuck ? 0xFFFFu : L1B_ITEMS * nblk) << 16), PB + excl};
                 if (nst) {
-                    const u32x4* src = reinterpret_cast<const u32x4*>(&L.img[tid_o * 16]);
-                    u32x4* dst = reinterpret_cast<u32x4*>(&L.img[(PB + excl) * 16]);
-                    const u32x4 a0 = src[0], a1 = src[1], a2 = src[2], a3 = src[3];
-                    dst[0] = a0; dst[1] = a1; dst[2] = a2; dst[3] = a3;
                     const uint32_t first = tid_o * stride_b + cur;
                     for (uint32_t q = 0; q < nst; ++q) L.where[excl + q] = first + q;
                 }
@@ -189,6 +206,7 @@ k_p1b_scatter(DevTable t, PartGeom g, const uint8_t* __restrict__ bases, uint64_
                 L.img[tid_o * 16 + 15] = (cur + nst) | (cn << 28);
                 L.hist[tid_o] = cn;                       // the next tile's k-mers rank behind what waits
             } else if (tid < PB + 64) L.hist[tid_o] = 0;  // (buckets the table does not have, the dump counters: a rank is kept in sixteen bits)
+            if (tid < PB) blk_move_waiting(L, tid_o);     // (wave-uniform; the words of buckets the table does not have stay {0, 0})
         }
         stamp(5);
         lds_barrier();

@@ -139,10 +139,6 @@ k_p2x_fast(PartGeom g, const uint64_t* __restrict__ l1_off, const uint8_t* __res
                     const bool stuck = nblk != 0 && nst == 0;
                     L.gb[tid_o] = uint2{(L2_BLOCK_ITEMS * nst) | ((stuck ? 0xFFFFu : L2_BLOCK_ITEMS * nblk) << 16), PB + excl};
                     if (nst) {
-                        const u32x4* src = reinterpret_cast<const u32x4*>(&L.img[tid_o * 16]);
-                        u32x4* dst = reinterpret_cast<u32x4*>(&L.img[(PB + excl) * 16]);
-                        const u32x4 a0 = src[0], a1 = src[1], a2 = src[2], a3 = src[3];
-                        dst[0] = a0; dst[1] = a1; dst[2] = a2; dst[3] = a3;
                         const uint32_t first = tid_o * capb + cur;
                         for (uint32_t q = 0; q < nst; ++q) L.where[excl + q] = first + q;
                     }
@@ -151,6 +147,7 @@ k_p2x_fast(PartGeom g, const uint64_t* __restrict__ l1_off, const uint8_t* __res
                     L.hist[tid_o] = cn;                                         // the next tile's k-mers rank behind what waits
                 } else L.hist[tid_o] = 0;
                 if (tid < 64) L.hist[PB + tid_o] = 0;                           // (the dump counters: a rank is kept in sixteen bits)
+                blk_move_waiting(L, tid_o);                                 // the waiting items move in front of the first block (kg_l1_blocks.hpp)
             }
             stamp(4);
             lds_barrier();

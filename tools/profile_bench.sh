@@ -7,7 +7,16 @@
 # runs, with --kernel-trace only).  The other workloads: plain, --kernel-trace --stats, and the same two --pmc passes (tools/profile_pmc_workload.sh: the two
 # counters cannot be collected in one pass on gfx950 -- rocprofv3 aborts with "exceeds the capabilities of the hardware" and then hangs).
 # Config 4 from files to files at full size is the plain line's `end_to_end` leg (bench.py; tools/e2e_config4.py runs it on its own).
+# Every step that uses the GPU runs under a time limit of its own and the script ENDS at the first one that fails (a fault, an abort, a
+# time limit: nothing more is started on that card; what the step wrote to <tag>_*.err says why).  NO_LINE=1 leaves out the --full line
+# (minutes of CPU baseline and end-to-end legs) when only the profiles are retaken.
 set -u
+gpu_step() {                                 # gpu_step <seconds> <stdout file> <stderr file> <command ...>
+  local secs=$1 so=$2 se=$3; shift 3
+  timeout -k 10 "$secs" "$@" > "$so" 2> "$se"
+  local rc=$?
+  if [ $rc -ne 0 ]; then echo "profile_bench.sh: exit $rc from: $* (stderr: $se) -- stopping here" >&2; tail -n 5 "$se" >&2; exit $rc; fi
+}
 tag=${1:-r05_final}
 root=$PWD
 out=$PWD/gpurun_out
@@ -16,11 +25,11 @@ cd /tmp && export TMPDIR=/tmp
 quiet="--steps 1 --warmup 0 --no-cpu-baseline --no-e2e --no-workloads"
 if [ "${SKIP_MAIN:-0}" != 1 ]; then        # (SKIP_MAIN=1: only the other workloads and the SQ view, after an ONLY_MAIN=1 run)
 rm -rf /tmp/prof_stats /tmp/prof_fetch /tmp/prof_write
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python "$root/bench.py" $quiet > /dev/null 2> "$out/${tag}_stats.err"
+gpu_step 600 /dev/null "$out/${tag}_stats.err" rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python "$root/bench.py" $quiet
 find /tmp/prof_stats -name '*kernel_stats.csv' -exec cp {} "$out/${tag}_kernel_stats.csv" \;
 for c in FETCH_SIZE WRITE_SIZE; do
   d=/tmp/prof_$(echo $c | tr 'A-Z' 'a-z' | cut -d_ -f1)
-  timeout 900 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $d -- python "$root/bench.py" $quiet > /dev/null 2> "$out/${tag}_pmc_$c.err"
+  gpu_step 900 /dev/null "$out/${tag}_pmc_$c.err" rocprofv3 --pmc $c --kernel-trace --output-format csv -d $d -- python "$root/bench.py" $quiet
 done
 python - "$out/${tag}_pmc_fetch_write.json" "$root" <<'PY'
 import csv, glob, json, re, sys
@@ -43,21 +52,21 @@ json.dump(agg, open(sys.argv[1], "w"), indent=1)
 PY
 # the plain line comes after the counters: its roofline.traffic is read from the profile that was just taken (same sources: bench.py checks)
 mkdir -p "$root/profiles" && cp "$out/${tag}_pmc_fetch_write.json" "$root/profiles/${tag}_pmc_fetch_write.json"
-timeout 900 python "$root/bench.py" --steps 3 --warmup 1 --full > "$out/${tag}_bench.json" 2> "$out/${tag}_bench.err"
+[ "${NO_LINE:-0}" = 1 ] || gpu_step 900 "$out/${tag}_bench.json" "$out/${tag}_bench.err" python "$root/bench.py" --steps 3 --warmup 1 --full
 fi
 [ "${ONLY_MAIN:-0}" = 1 ] && { ls -la "$out" | grep "$tag"; exit 0; }
 for w in hist gcp comp-rr; do
   rm -rf /tmp/prof_w /tmp/prof_wp
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_w -- python "$root/bench.py" --workload $w $quiet > /dev/null 2> "$out/${tag}_${w}_stats.err"
+  gpu_step 600 /dev/null "$out/${tag}_${w}_stats.err" rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_w -- python "$root/bench.py" --workload $w $quiet
   find /tmp/prof_w -name '*kernel_stats.csv' -exec cp {} "$out/${tag}_${w}_kernel_stats.csv" \;
-  bash "$root/tools/profile_pmc_workload.sh" "$tag" $w
+  bash "$root/tools/profile_pmc_workload.sh" "$tag" $w || exit $?
   cp "$out/${tag}_${w}_pmc_fetch_write.json" "$root/profiles/${tag}_${w}_pmc_fetch_write.json"
-  timeout 600 python "$root/bench.py" --workload $w --steps 3 --warmup 1 --full --no-e2e --no-cpu-baseline > "$out/${tag}_${w}_bench.json" 2> "$out/${tag}_${w}_bench.err"
+  gpu_step 600 "$out/${tag}_${w}_bench.json" "$out/${tag}_${w}_bench.err" python "$root/bench.py" --workload $w --steps 3 --warmup 1 --full --no-e2e --no-cpu-baseline
 done
 # (config 4 from files to files at full size is part of the plain line above since round 5: end_to_end, with its result_check)
 # SQ view of the stage kernels (one partition round of a reduced config): wave cycles, waits, issue, LDS conflicts
 rm -rf /tmp/prof_sq
-timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d /tmp/prof_sq -- python "$root/bench.py" --reads 60000000 --genome 200000000 $quiet > /dev/null 2> "$out/${tag}_sq.err"
+gpu_step 600 /dev/null "$out/${tag}_sq.err" rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d /tmp/prof_sq -- python "$root/bench.py" --reads 60000000 --genome 200000000 $quiet
 python - "$out/${tag}_sq_counters.txt" <<'PY'
 import csv, glob, re, sys
 agg = {}

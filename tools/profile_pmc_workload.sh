@@ -9,7 +9,9 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/prof_wp_$c
-  timeout -s KILL 120 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/prof_wp_$c -- python "$root/bench.py" --workload $w --steps 1 --warmup 0 --no-cpu-baseline --no-e2e > /dev/null 2> "$out/${tag}_${w}_pmc_$c.err"
+  timeout -k 10 120 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/prof_wp_$c -- python "$root/bench.py" --workload $w --steps 1 --warmup 0 --no-cpu-baseline --no-e2e > /dev/null 2> "$out/${tag}_${w}_pmc_$c.err"
+  rc=$?
+  if [ $rc -ne 0 ]; then echo "profile_pmc_workload.sh: exit $rc from the $c pass of $w (stderr: $out/${tag}_${w}_pmc_$c.err) -- stopping here" >&2; exit $rc; fi
 done
 python - "$out/${tag}_${w}_pmc_fetch_write.json" "$root" <<'PY'
 import csv, glob, json, re, sys
