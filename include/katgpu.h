@@ -433,6 +433,27 @@ int  katgpu_allreduce_u64(katgpu_comm* comm, uint64_t* buf, size_t n);
  * every rank (rank 0 cannot open the file: KATGPU_ERR_IO on all, agreed before a run travels), and the file is removed.
  * KATGPU_TIMING: rank 0 prints one line, katgpu_timing {"phase": "jf_dump_gathered", ...}. */
 int  katgpu_jf_dump_gathered(katgpu_comm* comm, katgpu_table* t, const char* path);
+/* katgpu_table_profile_host for the tables of all ranks, after the exchange (`katgpu sect|cold --gpus N`).  Collective: every rank calls
+ * it with its own table and the SAME bases; on rank 0, counts[i] for i in [0, n - k] is what katgpu_table_profile_host would write
+ * for one table holding the union -- the full 64-bit count, the side table included, 0 for a window with a byte outside ACGTacgt and
+ * for an absent k-mer; `counts` is ignored on the other ranks and may be NULL there.  Nothing is written when n < k.  Both key
+ * widths, both table layouts, canonical and non-canonical tables; a world of one rank runs the whole protocol.
+ * PRECONDITION, not checked: the tables hold disjoint k-mers, each on the rank katgpu_exchange_merge leaves it on (the owner is a mix
+ * of the k-mer's CANONICAL form whatever the strand mode of the tables; the lookup itself follows `canonicalise`).
+ * The sequence goes through in batches of 2^25 window starts, each re-sending the k-1 bases it shares with the next.  Per batch every
+ * rank looks up the windows whose k-mer it owns and keeps (window index in the batch: u32, count: u64) where the count is not 0; the
+ * runs' lengths go round, the runs to rank 0 in one grouped transfer (12 bytes per present window of another rank's; an empty run
+ * sends nothing), and rank 0 scatters them into the batch's dense array, which reaches `counts` through the stream.
+ * Device memory, from the context's pool and beside the table, for a batch of B = min(n - k + 1, 2^25) window starts: B + 126 bytes
+ * of bases and 12 B + 32 bytes of run on every rank, 8 B bytes of counts more on rank 0 -- at most 672 MiB there, 416 MiB elsewhere.
+ * The ranks agree on n and k before the first batch: a mismatch is KATGPU_ERR_INVALID_ARG on every rank.  They allocate first and
+ * agree on that too: when one cannot, every rank returns KATGPU_ERR_NOMEM (katgpu_last_error names the rank); either way the
+ * communicator is as usable as before.  A rank that fails later raises the communicator's abort flag, so that its peers leave their
+ * waits: an error on every rank.
+ * KATGPU_TIMING: rank 0 prints one line per call,
+ * katgpu_timing {"phase": "profile_gathered", "batches": .., "ranks": .., "records": .., "wire_bytes": ..}. */
+int  katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_table* t, const char* bases, size_t n, int canonicalise,
+                                        uint64_t* counts /* rank 0; ignored elsewhere, may be NULL */);
 /* wall time spent so far in extraction / on the wire (posting + waiting) / merging / all-reducing (ms), bytes sent, merge calls */
 int  katgpu_comm_stats(katgpu_comm* comm, double* ms_extract, double* ms_exchange, double* ms_merge, double* ms_allreduce,
                        uint64_t* bytes_sent, uint64_t* merge_launches);

@@ -43,6 +43,7 @@ EXPORTS = (
     "katgpu_table_record_stats_host", "katgpu_table_record_stats_device", "katgpu_table_jf_records_device", "katgpu_table_jf_records_device_wide",
     "katgpu_table_add_jf_records_device", "katgpu_jf_load_part",
     "katgpu_table_record_regions_host", "katgpu_table_record_regions_device", "katgpu_jf_dump_gathered",
+    "katgpu_table_profile_gathered_host",
 )
 
 # katgpu_record_stats: one record of Table.record_stats
@@ -856,6 +857,7 @@ class Comm:
         L.katgpu_exchange_finish.argtypes = [C.c_void_p, C.c_void_p]
         L.katgpu_allreduce_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.katgpu_jf_dump_gathered.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
+        L.katgpu_table_profile_gathered_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.katgpu_comm_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_uint64)] * 2
         L.katgpu_comm_wire.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         h = C.c_void_p()
@@ -909,6 +911,18 @@ class Comm:
         rc = self.engine.L.katgpu_jf_dump_gathered(self.h, table.h, os.fsencode(path))
         if rc:
             raise KatGpuError(rc, self.engine.L.katgpu_jf_last_error().decode(errors="replace") or self.engine.L.katgpu_last_error(self.engine.h).decode(errors="replace"))
+
+    def profile_gathered(self, table, bases, canonicalise=None):
+        """Collective, after exchange_merge: Table.profile of `bases` (bytes / str / uint8 array, the same on every rank) against the
+        union of the ranks' tables.  Rank 0 gets the u64[len - k + 1] array, the other ranks None."""
+        if isinstance(bases, str):
+            bases = bases.encode()
+        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
+        out = np.zeros(max(0, b.size - table.k + 1), np.uint64) if self.rank == 0 else None
+        canon = table.canonical if canonicalise is None else canonicalise
+        self.engine._chk(self.engine.L.katgpu_table_profile_gathered_host(self.h, table.h, b.ctypes.data, b.size, int(bool(canon)),
+                                                                          out.ctypes.data if out is not None else None))
+        return out
 
     def stats(self):
         d = [C.c_double() for _ in range(4)]

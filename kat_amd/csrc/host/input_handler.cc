@@ -84,6 +84,10 @@ void Engine::exchange(katgpu_table* t) { if (dist_) { finishPending(); check(kat
 void Engine::exchangeBegin(katgpu_table* t) { if (dist_) { while (g_pending.size() >= 2) finish_oldest(); check(katgpu_exchange_begin(comm(), t)); g_pending.push_back(t); } }
 void Engine::barrier() { if (dist_) { finishPending(); check(katgpu_comm_barrier(comm())); } }
 void Engine::allreduce(uint64_t* buf, size_t n) { if (dist_) { finishPending(); check(katgpu_allreduce_u64(comm(), buf, n)); } }
+void Engine::profileGathered(katgpu_table* t, const char* bases, size_t n, bool canonicalise, uint64_t* counts) {
+    finishPending();
+    check(katgpu_table_profile_gathered_host(comm(), t, bases, n, canonicalise ? 1 : 0, counts));
+}
 
 void Engine::shutdown() {
     if (g_comm) { katgpu_comm_free(g_comm); g_comm = nullptr; }

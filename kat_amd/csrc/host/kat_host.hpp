@@ -79,6 +79,8 @@ public:
     static void finishPending();                    // ... and are applied here (katgpu_exchange_begin / _finish); every other collective finishes it first
     static void allreduce(uint64_t* buf, size_t n); // idem
     static void barrier();                          // idem
+    // the per-position counts of `bases` against a table that lies on the ranks by owner, on rank 0 (katgpu_table_profile_gathered_host); idem
+    static void profileGathered(katgpu_table* t, const char* bases, size_t n, bool canonicalise, uint64_t* counts);
 private:
     static int rank_, world_;
     static bool dist_;

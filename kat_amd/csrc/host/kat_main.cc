@@ -62,7 +62,7 @@ int main(int argc, char* argv[]) {
     if (argc < 2 || !strcmp(argv[1], "--help") || !strcmp(argv[1], "-h")) { usage(); return 1; }
     const std::string mode = argv[1];
     // the katgpu-only switch, valid in every counting mode:
-    //   --gpus N                    N processes, one per GPU (hist, gcp, comp)
+    //   --gpus N                    N processes, one per GPU (hist, gcp, comp, sect, cold)
     int kept = 2, gpus = 0;
     bool gpus_given = false;
     for (int i = 2; i < argc; ++i) {
@@ -73,7 +73,7 @@ int main(int argc, char* argv[]) {
     argc = kept;
     if (gpus_given && (gpus < 1 || gpus > 256)) { std::cerr << "Error: Parsing Command Line: --gpus takes 1 .. 256" << std::endl; return 1; }
     if (!gpus_given) return guarded(mode, argc - 1, argv + 1);
-    if (mode != "hist" && mode != "gcp" && mode != "comp") { std::cerr << "Error: Parsing Command Line: --gpus applies to hist, gcp and comp" << std::endl; return 1; }
+    if (mode != "hist" && mode != "gcp" && mode != "comp" && mode != "sect" && mode != "cold") { std::cerr << "Error: Parsing Command Line: --gpus applies to hist, gcp and comp, sect and cold" << std::endl; return 1; }
     // A peer that is alive but wedged (its heartbeat thread still ticking) would hang the run for ever: no single wait inside a collective
     // lasts longer than this (two hours -- a rank dealt a whole-genome .gz reaches the exchange many minutes after the others), unless the
     // caller says otherwise.  The library reads it at its first wait.

@@ -7,6 +7,7 @@
 // device's too (katgpu_table_record_stats_host) and no count comes back.  Records are read with the semantics of the vendored SeqAn 2.0.0 reader
 // (deps/seqan-library-2.0.0/include/seqan/seq_io/fasta_fastq.h:306-380, CharString target).
 #include "kat_host.hpp"
+#include "record_stats_host.hpp"
 
 #include <sys/stat.h>
 #include <zlib.h>
@@ -46,11 +47,6 @@ bool endsWithNoCase(const string& s, const char* suffix) {
     for (size_t i = 0; i < n; i++) if (tolower((unsigned char)s[s.size() - n + i]) != suffix[i]) return false;
     return true;
 }
-
-inline bool isBase(char c) {                    // lib/include/kat/str_utils.hpp:183-201 (validKmer)
-    switch (c) { case 'A': case 'a': case 'C': case 'c': case 'G': case 'g': case 'T': case 't': return true; default: return false; }
-}
-inline bool isGC(char c) { return c == 'G' || c == 'g' || c == 'C' || c == 'c'; }
 
 inline void appendU64(string& s, uint64_t v) {
     char tmp[24]; int n = 0;
@@ -252,36 +248,15 @@ void Sect::processSeq(Record& r, const uint64_t* cnt) {                         
     const string& seq = *r.seq;
     const uint64_t seqLength = seq.size();
     const int64_t nbCounts = (int64_t)seqLength - k + 1;
-    uint64_t nbNonZero = 0, nbInvalid = 0;
     r.median = 0; r.mean = 0.0;
     const size_t nb = nbCounts > 0 ? (size_t)nbCounts : 0;
     vector<int16_t> gc;
+    const katgpu_record_stats st = recordStatsFromCounts(seq.data(), seqLength, k, cnt, &gc);   // (record_stats_host.hpp: shared with Cold under --gpus)
     if (nb) {
-        // validity and GC of every window by a rolling scan (the reference re-reads k characters per window)
-        gc.resize(nb);
-        uint32_t bad = 0, g = 0;
-        for (size_t i = 0; i < seqLength; i++) {
-            bad += !isBase(seq[i]); g += isGC(seq[i]);
-            if (i >= k) { bad -= !isBase(seq[i - k]); g -= isGC(seq[i - k]); }
-            if (i + 1 >= k) gc[i + 1 - k] = bad ? (int16_t)-1 : (int16_t)g;
-        }
-        uint64_t sum = 0;
-        for (size_t i = 0; i < nb; i++) {
-            if (gc[i] < 0) nbInvalid++;
-            else { sum += cnt[i]; if (cnt[i]) nbNonZero++; }
-        }
-        vector<uint64_t> sorted(cnt, cnt + nb);
-        std::nth_element(sorted.begin(), sorted.begin() + nb / 2, sorted.end());                // == sort()[size/2] (:540-542)
-        r.median = (uint32_t)(double)sorted[nb / 2];
-        r.mean = (double)sum / (double)nbCounts;
+        r.median = (uint32_t)(double)st.median;
+        r.mean = (double)st.sum / (double)nbCounts;
     }
-    uint64_t gs = 0, cs = 0, ns = 0;
-    for (char c : seq) {
-        if (c == 'G' || c == 'g') gs++;
-        else if (c == 'C' || c == 'c') cs++;
-        else if (c == 'N' || c == 'n') ns++;
-    }
-    recordScalars(r, nbNonZero, nbInvalid, gs + cs, ns);
+    recordScalars(r, st.non_zero, st.invalid, st.gc_bases, st.n_bases);
 
     if (!noCountStats) {                                                                        // printCounts, :328-346
         string& o = r.cvg_txt;
@@ -363,13 +338,20 @@ void Sect::processSeqFile() {                                                   
 
     SeqRecordReader reader(seqFile);
     if (verbose) std::cerr << endl;
-    std::ofstream count_path_stream, gc_count_path_stream, nr_path_stream, r_path_stream;
-    if (!noCountStats) count_path_stream.open((outputPrefix + "-counts.cvg").c_str());
-    if (outputGCStats) gc_count_path_stream.open((outputPrefix + "-counts.gc").c_str());
-    if (extractNR) nr_path_stream.open((outputPrefix + "-non_repetitive.fa").c_str());
-    if (extractR) r_path_stream.open((outputPrefix + "-repetitive.fa").c_str());
-    std::ofstream cvg_gc_stream((outputPrefix + "-stats.tsv").c_str());
-    cvg_gc_stream << "seq_name\tmedian\tmean\tgc%\tseq_length\tkmers_in_seq\tinvalid_kmers\t%_invalid\tnon_zero_kmers\t%_non_zero\t%_non_zero_corrected" << endl;
+    // --gpus N: after the exchange a k-mer lives on one rank.  Every rank reads the sequence file and takes part in one collective
+    // profile per batch (katgpu_table_profile_gathered_host); the per-position counts arrive on rank 0, which alone opens the outputs
+    // and runs processSeq on them -- whatever the options: processSeq makes every output from the counts.  The other ranks create,
+    // truncate and write nothing.
+    const bool dist = Engine::dist(), speak = !dist || Engine::speaker();
+    std::ofstream count_path_stream, gc_count_path_stream, nr_path_stream, r_path_stream, cvg_gc_stream;
+    if (speak) {
+        if (!noCountStats) count_path_stream.open((outputPrefix + "-counts.cvg").c_str());
+        if (outputGCStats) gc_count_path_stream.open((outputPrefix + "-counts.gc").c_str());
+        if (extractNR) nr_path_stream.open((outputPrefix + "-non_repetitive.fa").c_str());
+        if (extractR) r_path_stream.open((outputPrefix + "-repetitive.fa").c_str());
+        cvg_gc_stream.open((outputPrefix + "-stats.tsv").c_str());
+        cvg_gc_stream << "seq_name\tmedian\tmean\tgc%\tseq_length\tkmers_in_seq\tinvalid_kmers\t%_invalid\tnon_zero_kmers\t%_non_zero\t%_non_zero_corrected" << endl;
+    }
 
     // The reference reads 1024 records at a time (BATCH_SIZE, src/sect.hpp:66); the batch only bounds memory there and is
     // invisible in the outputs.  Here a batch is bounded by bases instead, so that one device call has enough to do.
@@ -380,7 +362,8 @@ void Sect::processSeqFile() {                                                   
     vector<uint64_t> counts, offs, lens;
     vector<katgpu_record_stats> stats;
     // -n: nothing per position is written.  The device reduces the counts per record, and with -E / -F it finds the regions as well
-    const bool stats_only = noCountStats;
+    // (one GPU: the statistics and regions kernels look a window up in the table of their own rank only)
+    const bool stats_only = noCountStats && !dist;
     vector<katgpu_count_range> ranges;
     if (stats_only && extractNR) ranges.push_back({1, minRepeat});
     if (stats_only && extractR) ranges.push_back({minRepeat, maxRepeat});
@@ -427,6 +410,10 @@ void Sect::processSeqFile() {                                                   
                 if (extractNR) index(first_nr, found, n_found[0]);
                 if (extractR) index(first_r, found + (extractNR ? n_found[0] : 0), n_found[extractNR ? 1 : 0]);
             }
+        } else if (dist) {
+            if (speak && counts.size() < joined.size()) counts.resize(joined.size());
+            Engine::profileGathered(input.hash, joined.data(), joined.size(), input.canonical, speak ? counts.data() : nullptr);
+            if (!speak) continue;
         } else {
             if (counts.size() < joined.size()) counts.resize(joined.size());
             Engine::check(katgpu_table_profile_host(input.hash, joined.data(), joined.size(), input.canonical ? 1 : 0, counts.data()));
@@ -471,7 +458,7 @@ void Sect::processSeqFile() {                                                   
         lap(4);
         if (verbose) std::cerr << "done" << endl;
     }
-    if (getenv("KATGPU_TIMING"))
+    if (getenv("KATGPU_TIMING") && speak)
         fprintf(stderr, "katgpu_timing {\"phase\": \"sect_coverage\", \"read_s\": %.3f, \"join_s\": %.3f, \"device_call_s\": %.3f, \"records_s\": %.3f, \"text_s\": %.3f}\n",
                 t_part[0], t_part[1], t_part[2], t_part[3], t_part[4]);
     cout << " done.";
@@ -519,7 +506,9 @@ int Sect::main(int argc, char* argv[]) {                                        
 
 // ================================================================ Cold (src/cold.cc) ==============================
 // Every record of the assembly against the reads hash and against the assembly's own hash: two
-// katgpu_table_record_stats_host calls per batch, one -stats.tsv row per record.
+// katgpu_table_record_stats_host calls per batch, one -stats.tsv row per record.  --gpus N: the hashes lie on the ranks by owner, so
+// the two calls are collective per-position profiles gathered on rank 0 (katgpu_table_profile_gathered_host), which reduces them per
+// record on the host (record_stats_host.hpp) and writes the rows; the other ranks write nothing.
 
 Cold::Cold(const vector<string>& reads_files, const string& asm_file) {                          // src/cold.cc:67-77
     reads.setMultipleInputs(reads_files);
@@ -574,15 +563,17 @@ void Cold::processSeqFile() {                                                   
     cout.flush();
     SeqRecordReader reader(assembly.pathString());
     if (verbose) std::cerr << endl;
-    std::ofstream cvg_gc_stream((outputPrefix + "-stats.tsv").c_str());
-    cvg_gc_stream << "seq_name\tread_median_cvg\tread_mean_cvg\tasm_cn\tgc%\tseq_length\tkmers_in_seq\tinvalid_kmers\t%_invalid\tnon_zero_kmers\t%_non_zero\t%_non_zero_corrected" << endl;
+    const bool dist = Engine::dist(), speak = !dist || Engine::speaker();
+    std::ofstream cvg_gc_stream;
+    if (speak) cvg_gc_stream.open((outputPrefix + "-stats.tsv").c_str());
+    if (speak) cvg_gc_stream << "seq_name\tread_median_cvg\tread_mean_cvg\tasm_cn\tgc%\tseq_length\tkmers_in_seq\tinvalid_kmers\t%_invalid\tnon_zero_kmers\t%_non_zero\t%_non_zero_corrected" << endl;
 
     const size_t BATCH_BASES = (size_t)64 << 20;
     vector<string> names, seqs;
     vector<Row> rows;
     string joined;
     vector<katgpu_record_stats> rstats, astats;
-    vector<uint64_t> offs, lens;
+    vector<uint64_t> offs, lens, counts;
     while (!reader.atEnd()) {
         if (verbose) std::cerr << "Loading Batch of sequences... ";
         names.clear(); seqs.clear();
@@ -599,8 +590,19 @@ void Cold::processSeqFile() {                                                   
         for (size_t i = 0; i < n; i++) { offs[i] = joined.size(); lens[i] = seqs[i].size(); joined += seqs[i]; joined += '\n'; }
         rstats.resize(n); astats.resize(n);
         // the device reduces every record's counts: everything from the reads hash, the median (asm_cn) from the assembly's
-        Engine::check(katgpu_table_record_stats_host(reads.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, reads.canonical ? 1 : 0, rstats.data()));
-        Engine::check(katgpu_table_record_stats_host(assembly.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, assembly.canonical ? 1 : 0, astats.data()));
+        if (dist) {
+            if (speak && counts.size() < joined.size()) counts.resize(joined.size());
+            auto gathered = [&](InputHandler& in, vector<katgpu_record_stats>& st) {
+                Engine::profileGathered(in.hash, joined.data(), joined.size(), in.canonical, speak ? counts.data() : nullptr);
+                for (size_t i = 0; speak && i < n; i++) st[i] = recordStatsFromCounts(seqs[i].data(), seqs[i].size(), in.merLen, counts.data() + offs[i]);
+            };
+            gathered(reads, rstats);
+            gathered(assembly, astats);
+            if (!speak) continue;
+        } else {
+            Engine::check(katgpu_table_record_stats_host(reads.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, reads.canonical ? 1 : 0, rstats.data()));
+            Engine::check(katgpu_table_record_stats_host(assembly.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, assembly.canonical ? 1 : 0, astats.data()));
+        }
 
         rows.assign(n, Row());
         for (size_t i = 0; i < n; i++) processSeq(rows[i], seqs[i], rstats[i], astats[i]);

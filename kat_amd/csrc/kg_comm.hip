@@ -371,7 +371,8 @@ double wall_ms() { return now_ms(); }
 
 }  // namespace
 
-// ---- what kg_jf_device.hip uses (kg_host.hpp) ----
+// ---- what kg_jf_device.hip and kg_query.hip use (kg_host.hpp) ----
+int comm_allgather_u64(katgpu_comm* m, const uint64_t* mine, size_t n, uint64_t* out) { return allgather_u64(m, mine, n, out); }
 int comm_transfer(katgpu_comm* m, const std::vector<CommMsg>& sends, const std::vector<CommMsg>& recvs) {
     int rc = transfer(m, sends, recvs, m->ev[0]);
     if (!rc) rc = transfer_wait(m, m->ev[0]);

@@ -2,7 +2,7 @@
 // handles of include/katgpu.h, error plumbing, the allocation pool, launch timing.  The library is split by concern:
 //   kg_context.hip   context, pool, profile counters, device buffers, the synthetic workload
 //   kg_table.hip     table life cycle: geometry, create / regrow / free, counters and statistics, room for records to come
-//   kg_query.hip     a sequence or keys against a table: lookups, profiles, per-record hits, coverage statistics and count-range regions
+//   kg_query.hip     a sequence or keys against a table: lookups, profiles (one table, or the ranks' tables gathered), per-record hits, coverage statistics and count-range regions
 //   kg_records.hip   records out of a table and into one: partition / export / merge, the k-mer filter
 //   kg_jf_device.hip .jf records in file order out of a table, and streamed from a file into one
 //   kg_count.hip     counting: the direct kernel, the partitioned counter's host loop, the host feeder, katgpu_count*
@@ -335,11 +335,14 @@ int for_record_batches(katgpu_ctx* c, const char* bases, size_t n, const uint64_
     return KATGPU_OK;
 }
 
-// What the gathered .jf dump (kg_jf_device.hip) asks of the communicator (kg_comm.hip): the transport's grouped point-to-point transfer.
+// What the gathered .jf dump (kg_jf_device.hip) and the gathered profile (kg_query.hip) ask of the communicator (kg_comm.hip): the
+// transport's grouped point-to-point transfer, and small host values from every rank to every rank.
 struct CommMsg { int peer; void* dev; size_t bytes; };          // one side of a point-to-point transfer (device memory)
 // A group of transfers, every rank of the communicator together, done when it returns (waited for under the liveness checks).  A
 // message of no bytes is not sent; the n-th message to a peer meets the n-th from it.
 int comm_transfer(katgpu_comm* m, const std::vector<CommMsg>& sends, const std::vector<CommMsg>& recvs);
+// allgather_u64: out[r * n ..) = rank r's n words (host arrays), every rank together
+int comm_allgather_u64(katgpu_comm* m, const uint64_t* mine, size_t n, uint64_t* out);
 // this rank gives up inside a collective: its peers leave their waits with an error instead of waiting for it
 void comm_abort(katgpu_comm* m);
 

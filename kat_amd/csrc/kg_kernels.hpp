@@ -9,6 +9,7 @@
 //  K6 k_partition, k_extract_count, k_extract_write                              owner-partitioned export for the multi-GPU merge
 //  K7 k_merge, k_merge32, k_merge_apply, k_merge_deferred                        add (key,count) records into a table
 //  K8 k_profile        per-position lookup of a sequence's windows               (replaces the lookups of Sect::processSeq)
+//     k_profile_owned, k_profile_scatter                                        the same across ranks: runs of (window, count) by owner, made dense on rank 0
 // K1, K2, K6 (k_partition), K7 (k_merge), K8, k_get and the probe forms of K5 are one body each for one-word and wide k-mers (k <= 32,
 // 33 <= k <= 63: the template parameter W; kg_device.hpp "one body for both key widths"); k_export is the wide tables' own export.
 //
@@ -1008,6 +1009,75 @@ k_profile(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restric
             }
         }
         __syncthreads();
+    }
+}
+
+// K8 across ranks (katgpu_table_profile_gathered_host): after the exchange a k-mer lives on one rank, so every rank walks the same
+// windows and looks up the ones whose k-mer it OWNS -- owner_of mixes the canonical form whatever the table's strand mode; the lookup
+// follows `canonicalise` as in K8 -- and appends (window index, count) to its run wherever the count is not 0: two arrays, so that both
+// stay naturally aligned.  A wave reserves its slots with one add: the ballot of its hits, their number, added by the first of them;
+// the order within a run is free.  Every lane of a wave goes through the window loop (the ballots want them all; the pad words of the
+// tile cover the last lanes' reads), and those that own no window start never hit.  n_ranks == 1: every window is this rank's.
+// The run arrays hold a record per window start of the batch: there is no more room to check.
+template <bool ALIGNED, bool W>
+__global__ void __launch_bounds__(COUNT_BLOCK)
+k_profile_owned(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
+                uint32_t rank, uint32_t n_ranks, uint32_t* __restrict__ run_idx, uint64_t* __restrict__ run_cnt,
+                unsigned long long* __restrict__ run_len) {
+    __shared__ typename Chunk<W>::Tile s;
+    const uint32_t tid = threadIdx.x, lane = tid & 63;
+    const uint32_t k = t.k;
+    const uint64_t n_out = n - k + 1;
+    s.pad();
+
+    for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const uint64_t off = chunk * Chunk<W>::STARTS + (uint64_t)tid * BASES_PER_LANE;
+        uint32_t w[4];
+        load16<ALIGNED>(bases, n, off, w);
+        uint32_t code, bad;
+        encode16(w, code, bad);
+        s.stage(code, bad);
+        __syncthreads();
+
+        const bool has_starts = tid < Chunk<W>::LANES;
+        typename Chunk<W>::Window lw;
+        lw.init(s.code, s.bad, tid, k);
+        for (int j = 0; j < BASES_PER_LANE; ++j, lw.step()) {
+            uint64_t c = 0;
+            if (has_starts && off + j < n_out && lw.valid()) {
+                auto key = lw.fwd();
+                if (n_ranks == 1 || owner_of(key, k, n_ranks) == rank) {
+                    if (canonicalise) key = kmer_canonical(key, k);
+                    c = table_get(t, key, n_ovf);
+                }
+            }
+            const unsigned long long hits = __ballot(c != 0);
+            if (!hits) continue;
+            const int first = __ffsll((long long)hits) - 1;
+            unsigned long long base = 0;
+            if (lane == (uint32_t)first) base = atomicAdd(run_len, (unsigned long long)__popcll(hits));
+            base = __shfl(base, first, 64);
+            if (c) {
+                const unsigned long long at = base + __popcll(hits & ((1ULL << lane) - 1));
+                run_idx[at] = (uint32_t)(off + j);
+                run_cnt[at] = c;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Rank 0 of the same: the batch's dense array from the runs.  CLEAR: out[0, n_out) = 0, a launch of its own -- a record's store must
+// not be overtaken by another workgroup's zeros.  Otherwise out[run_idx[i]] = run_cnt[i] for the n_rec records of the runs laid behind
+// one another: the ranks own disjoint k-mers, so no two records name one window, and plain stores do.  An index that names no window
+// of the batch (the runs came over the wire) is dropped.
+template <bool CLEAR>
+static __global__ void __launch_bounds__(256)
+k_profile_scatter(uint64_t* __restrict__ out, uint64_t n_out, const uint32_t* __restrict__ run_idx, const uint64_t* __restrict__ run_cnt, uint64_t n_rec) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (CLEAR ? n_out : n_rec); i += stride) {
+        if (CLEAR) out[i] = 0;
+        else { const uint32_t at = run_idx[i]; if (at < n_out) out[at] = run_cnt[i]; }
     }
 }
 

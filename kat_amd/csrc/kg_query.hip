@@ -1,5 +1,5 @@
 // kg_query.hip -- a sequence or keys against a table, which is left as it is: batch lookups (katgpu_table_get*), per-position profiles
-// (katgpu_table_profile_*), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*), the per-record coverage statistics
+// (katgpu_table_profile_*; _gathered_host: of a table that lies on several ranks, gathered on rank 0), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*), the per-record coverage statistics
 // of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*) and the count-range regions of `kat sect -n -E / -F` (katgpu_table_record_regions_*).  The host forms send their input through the device in batches.
 #include "kg_host.hpp"
 #include "kg_kernels.hpp"
@@ -92,6 +92,138 @@ extern "C" int katgpu_table_profile_host(katgpu_table* t, const char* bases, siz
     }
     if (rc) return rc;
     if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s", hipGetErrorString(e));
+    return KATGPU_OK;
+}
+
+// ------------------------------------------------------------------ the profile of a table that lies on several ranks ----
+
+static const size_t g_gather_batch = (size_t)std::min<uint64_t>(std::max<uint64_t>(hook_u64("KATGPU_TEST_GATHER_BATCH", (uint64_t)32 << 20), 1), (uint64_t)1 << 31);   // tests: window starts per batch of profile_gathered_host (a run names a window in 32 bits)
+static const int64_t g_gather_nomem = hook("KATGPU_TEST_GATHER_NOMEM") ? atoll(hook("KATGPU_TEST_GATHER_NOMEM")) : -1;   // tests: this rank reports that it could not allocate
+
+// one word per rank, gathered: *who = the first rank whose word is not 0, or -1, and *what = that word
+static int gather_agree(katgpu_comm* m, uint64_t mine, int* who, uint64_t* what) {
+    std::vector<uint64_t> all((size_t)katgpu_comm_world(m), 0);
+    const int rc = comm_allgather_u64(m, &mine, 1, all.data());
+    *who = -1;
+    for (int p = (int)all.size() - 1; p >= 0 && !rc; --p) if (all[p]) { *who = p; *what = all[p]; }
+    return rc;
+}
+
+// Collective, after katgpu_exchange_merge: every rank walks the same bases in batches of g_gather_batch window starts (each batch
+// re-sends the k-1 bases it shares with the next one, as katgpu_table_profile_host does) and keeps (window, count) of the windows
+// whose k-mer it owns and counts (k_profile_owned); the runs' lengths go round, the runs themselves to rank 0 -- one grouped
+// transfer per batch, indices and counts of a run as two messages, behind rank 0's own run in the buffer that run was written to:
+// the runs of a batch hold at most a record per window start between them, so one buffer of that size takes them all -- and rank 0
+// scatters them into the batch's dense array (k_profile_scatter), which goes to `counts` through the stream.
+// From the pool, per window start of a batch: 12 bytes of run on every rank and 8 of dense counts on rank 0, beside the batch's bases.
+extern "C" int katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_table* t, const char* bases, size_t n, int canonicalise, uint64_t* counts) {
+    if (!comm || !t) return KATGPU_ERR_INVALID_ARG;
+    katgpu_ctx* c = t->ctx;
+    const int rank = katgpu_comm_rank(comm), world = katgpu_comm_world(comm);
+    const uint32_t k = t->dv.k;
+    const bool wide = t->dv.keys_b != nullptr;
+    // ---- one sequence length, one k and usable pointers everywhere, before anything else: all ranks go on, or none does ----
+    {
+        const uint64_t mine[3] = {(uint64_t)n, k, (uint64_t)((n && !bases) || (rank == 0 && n >= k && !counts))};
+        std::vector<uint64_t> all((size_t)world * 3, 0);
+        const int crc = comm_allgather_u64(comm, mine, 3, all.data());
+        if (crc) return crc;
+        for (int p = 0; p < world; ++p) {
+            if (all[(size_t)p * 3] != all[0] || all[(size_t)p * 3 + 1] != all[1])
+                return fail(c, KATGPU_ERR_INVALID_ARG, "profile gathered: the ranks disagree: rank 0 has %llu bases at k = %llu, rank %d %llu at k = %llu",
+                            (unsigned long long)all[0], (unsigned long long)all[1], p, (unsigned long long)all[(size_t)p * 3], (unsigned long long)all[(size_t)p * 3 + 1]);
+            if (all[(size_t)p * 3 + 2]) return fail(c, KATGPU_ERR_INVALID_ARG, "profile gathered: rank %d was given no bases, or rank 0 no room for the counts", p);
+        }
+    }
+    if (n < k) return KATGPU_OK;
+    const size_t n_out = n - k + 1;
+    const size_t batch = std::min(n_out, g_gather_batch);
+    // ---- everything a batch needs: the run's counts | its indices | its length, the dense array on rank 0 ----
+    DevBuf db, run, dense;
+    const size_t idx_off = batch * sizeof(uint64_t), len_off = align_up(idx_off + batch * sizeof(uint32_t), 16);
+    auto prepare = [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        int rc = refresh_counters(t); if (rc) return rc;
+        if (g_gather_nomem == rank || db.pooled(c, batch + k - 1 + 64) != hipSuccess || run.pooled(c, len_off + 16) != hipSuccess ||
+            (rank == 0 && dense.pooled(c, batch * sizeof(uint64_t)) != hipSuccess)) {
+            (void)hipGetLastError();
+            return fail(c, KATGPU_ERR_NOMEM, "profile gathered: no device memory for a batch of %zu window starts", batch);
+        }
+        return KATGPU_OK;
+    };
+    int rc = prepare();
+    const std::string err_local = rc ? c->err : std::string();
+    int who = -1;
+    uint64_t what = 0;                                            // 1: no memory, 2: anything else
+    int crc = gather_agree(comm, rc == KATGPU_ERR_NOMEM ? 1 : rc ? 2 : 0, &who, &what);
+    if (crc) return rc ? rc : crc;
+    if (who >= 0) {
+        if (rc) { c->err = err_local; return rc; }
+        if (what == 1) return fail(c, KATGPU_ERR_NOMEM, "profile gathered: rank %d of %d has no device memory for a batch of %zu window starts", who, world, batch);
+        return fail(c, KATGPU_ERR_DEVICE, "profile gathered: rank %d could not read its table", who);
+    }
+    uint64_t* run_cnt = run.as<uint64_t>();
+    uint32_t* run_idx = (uint32_t*)(run.as<uint8_t>() + idx_off);
+    unsigned long long* run_len = (unsigned long long*)(run.as<uint8_t>() + len_off);
+
+    // ---- the batches.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end ----
+    uint64_t n_batches = 0, records = 0, wire_bytes = 0;
+    std::vector<uint64_t> lens((size_t)world, 0);
+    auto one_batch = [&](size_t pos) -> int {
+        const size_t starts = std::min(batch, n_out - pos), nb = starts + k - 1;
+        unsigned long long own = 0;
+        HIPCHK(c, hipMemcpyAsync(db.p, bases + pos, nb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(run_len, 0, sizeof own, c->stream));
+        {
+            ScopedTimer tm(c, KATGPU_K_PROFILE, starts);
+            launch_aligned_wide(c, aligned16(db.p), wide, starts, chunk_starts(wide), [&](auto A, auto W, dim3 grid, uint64_t n_chunks) {
+                hipLaunchKernelGGL((k_profile_owned<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, t->dev(), t->n_ovf, canonicalise, db.as<uint8_t>(), (uint64_t)nb, n_chunks, (uint32_t)rank, (uint32_t)world, run_idx, run_cnt, run_len);
+            });
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipMemcpyAsync(&own, run_len, sizeof own, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));             // (the run is whole before it travels)
+        if (own > starts) return fail(c, KATGPU_ERR_DEVICE, "profile gathered: a run of %llu records from %zu windows", own, starts);
+        const uint64_t mine = own;
+        int rc = comm_allgather_u64(comm, &mine, 1, lens.data());
+        if (rc) return rc;
+        uint64_t total = 0;
+        for (uint64_t l : lens) total += l;
+        const uint64_t remote = total - lens[0];
+        if (total > starts) return fail(c, KATGPU_ERR_DEVICE, "profile gathered: the ranks' runs hold %llu records, the batch %zu windows", (unsigned long long)total, starts);
+        if (remote) {                                            // (every rank knows: all take part in the transfer, or none does)
+            std::vector<CommMsg> sends, recvs;
+            if (rank != 0) { sends.push_back({0, run_idx, (size_t)own * sizeof(uint32_t)}); sends.push_back({0, run_cnt, (size_t)own * sizeof(uint64_t)}); }
+            else {
+                uint64_t at = lens[0];                           // the remote runs behind rank 0's own, in rank order
+                for (int p = 1; p < world; at += lens[p++]) { recvs.push_back({p, run_idx + at, (size_t)lens[p] * sizeof(uint32_t)}); recvs.push_back({p, run_cnt + at, (size_t)lens[p] * sizeof(uint64_t)}); }
+            }
+            rc = comm_transfer(comm, sends, recvs);
+            if (rc) return rc;
+        }
+        ++n_batches; records += total; wire_bytes += remote * (sizeof(uint32_t) + sizeof(uint64_t));
+        if (rank != 0) return KATGPU_OK;
+        uint64_t* d = dense.as<uint64_t>();
+        {
+            ScopedTimer tm(c, KATGPU_K_PROFILE, 0);
+            hipLaunchKernelGGL(k_profile_scatter<true>, dim3((unsigned)grid_for(c, starts, 256, 8)), dim3(256), 0, c->stream, d, (uint64_t)starts, run_idx, run_cnt, (uint64_t)0);
+            if (total) hipLaunchKernelGGL(k_profile_scatter<false>, dim3((unsigned)grid_for(c, total, 256, 8)), dim3(256), 0, c->stream, d, (uint64_t)starts, run_idx, run_cnt, total);
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipMemcpyAsync(counts + pos, d, starts * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KATGPU_OK;
+    };
+    for (size_t pos = 0; pos < n_out && !rc; pos += batch) rc = one_batch(pos);
+    const std::string err_mine = rc ? c->err : std::string();
+    if (rc) comm_abort(comm);
+    crc = gather_agree(comm, rc ? 1 : 0, &who, &what);
+    if (rc) { c->err = err_mine; return rc == KATGPU_ERR_NOMEM ? KATGPU_ERR_DEVICE : rc; }   // (not the collective one: the peers get an error too)
+    if (crc) return crc;
+    if (who >= 0) return fail(c, KATGPU_ERR_DEVICE, "profile gathered: rank %d failed", who);
+    if (rank == 0 && g_timing)
+        fprintf(stderr, "katgpu_timing {\"phase\": \"profile_gathered\", \"batches\": %llu, \"ranks\": %d, \"records\": %llu, \"wire_bytes\": %llu}\n",
+                (unsigned long long)n_batches, world, (unsigned long long)records, (unsigned long long)wire_bytes);
     return KATGPU_OK;
 }
 
