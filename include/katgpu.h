@@ -376,7 +376,7 @@ int katgpu_table_extract_packed(katgpu_table* t, uint32_t n_parts, const uint32_
 typedef struct { const uint32_t* dev_rem_lo; const uint8_t* dev_rem_hi; const uint32_t* dev_counts; const uint32_t* dev_region_counts; uint64_t n_records; uint32_t p1, p2; } katgpu_merge_source_packed;
 int katgpu_table_merge_regions_packed(katgpu_table* t, uint32_t g_lo, uint32_t g_hi, uint32_t n_src, const katgpu_merge_source_packed* src);
 
-/* ---- the exchange itself, over RCCL: one process per GPU (kat_amd/csrc/kg_comm.hip) ----
+/* ---- the exchange itself, over RCCL: one process per GPU (kat_amd/csrc/kg_comm.hip, kg_comm_exchange.hip) ----
  * Replaces, across GPUs, what the reference does across threads of one process at the end of a run:
  * ThreadedSparseMatrix::mergeThreadedMatricies (lib/include/kat/sparse_matrix.hpp:324-335), ThreadedCompCounters::merge
  * (lib/src/comp_counters.cc:230-254), Histogram::merge (src/histogram.cc:146-160) -- and, before them, makes every k-mer's count

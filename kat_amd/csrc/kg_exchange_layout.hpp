@@ -1,4 +1,4 @@
-// kg_exchange_layout.hpp -- where the arrays of the multi-GPU exchange (kg_comm.hip, struct Exchange) lie in its buffer: the send list
+// kg_exchange_layout.hpp -- where the arrays of the multi-GPU exchange (kg_comm_exchange.hip, struct Exchange) lie in its buffer: the send list
 // and the receive sets, each a group of record arrays.  Host arithmetic only (no device code): exchange_bytes, the split buffer's size
 // and Exchange::plan's carve-up all come from here, and tests/native/exchange_layout_check.cc checks it on the CPU.
 //

@@ -8,7 +8,8 @@
 //   kg_count.hip     counting: the direct kernel, the partitioned counter's host loop, the host feeder, katgpu_count*
 //   kg_scan.hip      device-side record scan of raw FASTQ / FASTA bytes (katgpu_count_files' fast path)
 //   kg_exchange.hip  region-ordered extraction / merge for the multi-GPU exchange
-//   kg_comm.hip      the exchange itself over RCCL (katgpu_comm_*)
+//   kg_comm.hip      the communicator: RCCL or /dev/shm transports, liveness, small collectives, all-or-none agreements (katgpu_comm_*; kg_comm.hpp)
+//   kg_comm_exchange.hip  the exchange itself, above the communicator (katgpu_exchange_*)
 //   kg_reduce.hip    hist / gcp / comp
 // gfx950 only; there is no CPU path in this library.
 #pragma once
@@ -334,17 +335,6 @@ int for_record_batches(katgpu_ctx* c, const char* bases, size_t n, const uint64_
     if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
     return KATGPU_OK;
 }
-
-// What the gathered .jf dump (kg_jf_device.hip) and the gathered profile (kg_query.hip) ask of the communicator (kg_comm.hip): the
-// transport's grouped point-to-point transfer, and small host values from every rank to every rank.
-struct CommMsg { int peer; void* dev; size_t bytes; };          // one side of a point-to-point transfer (device memory)
-// A group of transfers, every rank of the communicator together, done when it returns (waited for under the liveness checks).  A
-// message of no bytes is not sent; the n-th message to a peer meets the n-th from it.
-int comm_transfer(katgpu_comm* m, const std::vector<CommMsg>& sends, const std::vector<CommMsg>& recvs);
-// allgather_u64: out[r * n ..) = rank r's n words (host arrays), every rank together
-int comm_allgather_u64(katgpu_comm* m, const uint64_t* mine, size_t n, uint64_t* out);
-// this rank gives up inside a collective: its peers leave their waits with an error instead of waiting for it
-void comm_abort(katgpu_comm* m);
 
 // What a stream of .jf records between a file and the device runs on: a copy stream beside the context's and up to two slots of a device buffer, a
 // pinned buffer of that size and four events.  alloc(void**, bytes) makes a device buffer; pooled: pool_release gives it back, else hipFree.

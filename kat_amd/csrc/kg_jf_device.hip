@@ -3,6 +3,7 @@
 // the same for the disjoint tables of a communicator's ranks, their runs gathered on rank 0's device), and packed records unpacked and
 // added to a table (katgpu_table_add_jf_records_device; jf_stream_load, chunk by chunk out of a file).
 #include "kg_host.hpp"
+#include "kg_comm.hpp"
 #include "kg_jf_records.hpp"
 #include "kg_jf_load.hpp"
 #include "kg_jf.hpp"
@@ -265,17 +266,6 @@ int jf_stream_records(katgpu_table* t, uint32_t r, const uint64_t* cols, FILE* f
 
 static const int64_t g_jf_gather_nomem = hook("KATGPU_TEST_JF_GATHER_NOMEM") ? atoll(hook("KATGPU_TEST_JF_GATHER_NOMEM")) : -1;   // tests: this rank reports that it could not allocate
 
-// one word per rank, all-reduced: *who = the first rank whose word is not 0, or -1, and *what = that word
-static int jf_gather_agree(katgpu_comm* m, uint64_t mine, int* who, uint64_t* what = nullptr) {
-    const int rank = katgpu_comm_rank(m), world = katgpu_comm_world(m);
-    std::vector<uint64_t> flags((size_t)world, 0);
-    flags[rank] = mine;
-    const int rc = katgpu_allreduce_u64(m, flags.data(), flags.size());
-    *who = -1;
-    for (int p = world - 1; p >= 0; --p) if (flags[p]) { *who = p; if (what) *what = flags[p]; }
-    return rc;
-}
-
 // The ranks' tables hold disjoint k-mers: every rank orders and packs its records of a range of positions (jf_range), the runs travel
 // to rank 0 (one grouped transfer per range), which orders and packs their union from the runs (jf_range over JfRuns, buckets sized
 // for n_total) and streams it into the file as jf_stream does.  kg_jf.hpp says what the callers see.
@@ -291,7 +281,7 @@ static int jf_gather(katgpu_comm* m, katgpu_table* t, uint32_t r, const uint64_t
     uint64_t written = 0;
     std::vector<JfRange> ranges;
     std::vector<uint64_t> per_rank;                               // [world x n_ranges]: the records of rank p in range g
-    // what went wrong on this rank is kept until everyone has heard of it: a rank that left early would leave its peers in a collective
+    // (what went wrong on this rank is kept until everyone has heard of it: comm_agree_to_start)
     auto current = [&]() -> int { HIPCHK(c, hipSetDevice(c->device)); return refresh_counters(t); };
     int rc = current();
     const uint64_t distinct = rc ? 0 : t->distinct;
@@ -327,16 +317,13 @@ static int jf_gather(katgpu_comm* m, katgpu_table* t, uint32_t r, const uint64_t
         if (g_jf_range_records) want = g_jf_range_records;
         all[nbins] = want;
     }
-    const std::string err_local = rc ? c->err : std::string();
     int crc = katgpu_allreduce_u64(m, all.data(), all.size());
-    uint64_t what = 0;                                            // 1: no memory for the position counters (as collective as the agreement below), 2: anything else
-    if (!crc) crc = jf_gather_agree(m, rc == KATGPU_ERR_NOMEM ? 1 : rc ? 2 : 0, &who, &what);
     if (crc) return rc ? rc : crc;                                // (the communicator itself failed: its waits have ended on every rank)
-    if (who >= 0) {
-        if (rc) { c->err = err_local; return rc; }
-        if (what == 1) return fail(c, KATGPU_ERR_NOMEM, "jf dump: rank %d of %d has no device memory for its position counters", who, world);
-        return fail(c, KATGPU_ERR_DEVICE, "jf dump: rank %d could not read its table's positions", who);
-    }
+    rc = comm_agree_to_start(m, rc, [&](int p, int code) {        // (no memory for the position counters is as collective as the agreement below)
+        if (code == KATGPU_ERR_NOMEM) return fail(c, code, "jf dump: rank %d of %d has no device memory for its position counters", p, world);
+        return fail(c, code, "jf dump: rank %d could not read its table's positions", p);
+    });
+    if (rc) return rc;
     {
         const uint64_t want = std::max<uint64_t>(all[nbins], 1);
         uint64_t acc = 0, start = 0, sum = 0;
@@ -378,12 +365,12 @@ static int jf_gather(katgpu_comm* m, katgpu_table* t, uint32_t r, const uint64_t
     } else if (have && max_own) have = jf_malloc(c, (void**)&io.slot[0].dev, (size_t)max_own * rb) == hipSuccess;
     if (!have) (void)hipGetLastError();
     if (g_jf_gather_nomem == rank) have = false;
-    crc = jf_gather_agree(m, have ? 0 : 1, &who);
+    crc = comm_agree(m, have ? 0 : 1, &who);
     if (crc) return crc;
     if (who >= 0) return fail(c, KATGPU_ERR_NOMEM, "jf dump: rank %d of %d has no device or pinned memory for the buffers of a range (%llu records at most)", who, world, (unsigned long long)max_all);
 
     // ---- the ranges.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end, and the last
-    // all-reduce tells everyone that the file is not to be trusted ----
+    // agreement tells everyone that the file is not to be trusted (comm_agree_done) ----
     int pend = -1, slot = 0;
     size_t pend_n = 0;
     bool pend_remote = false;
@@ -415,7 +402,7 @@ static int jf_gather(katgpu_comm* m, katgpu_table* t, uint32_t r, const uint64_t
     // before a transfer: the run to travel is packed, and (rank 0) the range before this one has been read out of the gather buffer
     auto settled = [&]() -> int { HIPCHK(c, hipStreamSynchronize(c->stream)); return KATGPU_OK; };
     // rank 0 opens the file, and everyone hears of it before a run is posted: a sender must not be left with a transfer nobody takes
-    crc = jf_gather_agree(m, rank == 0 && !(f = open()) ? 1 : 0, &who);
+    crc = comm_agree(m, rank == 0 && !(f = open()) ? 1 : 0, &who);
     if (crc) return crc;
     if (who >= 0) return fail(c, KATGPU_ERR_IO, "jf dump: rank 0 cannot open the output file");
     for (size_t gi = 0; !rc && gi < G && n_total; ++gi) {
@@ -426,7 +413,7 @@ static int jf_gather(katgpu_comm* m, katgpu_table* t, uint32_t r, const uint64_t
             if (!rc && own) rc = settled();
             std::vector<CommMsg> sends;
             if (own) sends.push_back({0, io.slot[0].dev, (size_t)own * rb});
-            if (!rc && remote) rc = comm_transfer(m, sends, {});
+            if (!rc && remote) rc = transfer_sync(m, sends, {});
             continue;
         }
         const JfSlots::Slot& b = io.slot[slot];
@@ -441,7 +428,7 @@ static int jf_gather(katgpu_comm* m, katgpu_table* t, uint32_t r, const uint64_t
             uint64_t at = own;
             for (int p = 1; p < world; ++p) { recvs.push_back({p, gather.p + at * rb, (size_t)of(p, gi) * rb}); at += of(p, gi); }
             const double t0 = now_ms();
-            rc = comm_transfer(m, {}, recvs);
+            rc = transfer_sync(m, {}, recvs);
             tm->wire_s += (now_ms() - t0) * 1e-3;
             if (rc) break;
             hipEventRecord(wire_ev[slot][1], c->stream);
@@ -467,14 +454,7 @@ static int jf_gather(katgpu_comm* m, katgpu_table* t, uint32_t r, const uint64_t
         if (!rc) rc = drain();
         if (!rc && written != n_total) rc = fail(c, KATGPU_ERR_DEVICE, "jf dump: wrote %llu of %llu records", (unsigned long long)written, (unsigned long long)n_total);
     }
-    if (rc == KATGPU_ERR_NOMEM) rc = KATGPU_ERR_DEVICE;           // (not the collective one: the file is open, the peers get an error too)
-    const std::string err_mine = rc ? c->err : std::string();
-    if (rc) comm_abort(m);
-    crc = jf_gather_agree(m, rc ? 1 : 0, &who);
-    if (rc) { c->err = err_mine; return rc; }
-    if (crc) return crc;
-    if (who >= 0) return fail(c, KATGPU_ERR_DEVICE, "jf dump: rank %d failed, the file is incomplete", who);
-    return KATGPU_OK;
+    return comm_agree_done(m, rc, "jf dump: rank %d failed, the file is incomplete");      // (no memory now is not the collective kind: the file is open)
 }
 
 int jf_stream_gathered(katgpu_comm* m, katgpu_table* t, uint32_t r, const uint64_t* cols, uint64_t n_total, const std::function<FILE*()>& open, JfGatherTiming* tm) {

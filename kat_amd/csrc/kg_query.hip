@@ -2,6 +2,7 @@
 // (katgpu_table_profile_*; _gathered_host: of a table that lies on several ranks, gathered on rank 0), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*), the per-record coverage statistics
 // of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*) and the count-range regions of `kat sect -n -E / -F` (katgpu_table_record_regions_*).  The host forms send their input through the device in batches.
 #include "kg_host.hpp"
+#include "kg_comm.hpp"
 #include "kg_kernels.hpp"
 #include "kg_filter.hpp"
 #include "kg_record_stats.hpp"
@@ -100,15 +101,6 @@ extern "C" int katgpu_table_profile_host(katgpu_table* t, const char* bases, siz
 static const size_t g_gather_batch = (size_t)std::min<uint64_t>(std::max<uint64_t>(hook_u64("KATGPU_TEST_GATHER_BATCH", (uint64_t)32 << 20), 1), (uint64_t)1 << 31);   // tests: window starts per batch of profile_gathered_host (a run names a window in 32 bits)
 static const int64_t g_gather_nomem = hook("KATGPU_TEST_GATHER_NOMEM") ? atoll(hook("KATGPU_TEST_GATHER_NOMEM")) : -1;   // tests: this rank reports that it could not allocate
 
-// one word per rank, gathered: *who = the first rank whose word is not 0, or -1, and *what = that word
-static int gather_agree(katgpu_comm* m, uint64_t mine, int* who, uint64_t* what) {
-    std::vector<uint64_t> all((size_t)katgpu_comm_world(m), 0);
-    const int rc = comm_allgather_u64(m, &mine, 1, all.data());
-    *who = -1;
-    for (int p = (int)all.size() - 1; p >= 0 && !rc; --p) if (all[p]) { *who = p; *what = all[p]; }
-    return rc;
-}
-
 // Collective, after katgpu_exchange_merge: every rank walks the same bases in batches of g_gather_batch window starts (each batch
 // re-sends the k-1 bases it shares with the next one, as katgpu_table_profile_host does) and keeps (window, count) of the windows
 // whose k-mer it owns and counts (k_profile_owned); the runs' lengths go round, the runs themselves to rank 0 -- one grouped
@@ -126,7 +118,7 @@ extern "C" int katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_tabl
     {
         const uint64_t mine[3] = {(uint64_t)n, k, (uint64_t)((n && !bases) || (rank == 0 && n >= k && !counts))};
         std::vector<uint64_t> all((size_t)world * 3, 0);
-        const int crc = comm_allgather_u64(comm, mine, 3, all.data());
+        const int crc = allgather_u64(comm, mine, 3, all.data());
         if (crc) return crc;
         for (int p = 0; p < world; ++p) {
             if (all[(size_t)p * 3] != all[0] || all[(size_t)p * 3 + 1] != all[1])
@@ -151,22 +143,16 @@ extern "C" int katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_tabl
         }
         return KATGPU_OK;
     };
-    int rc = prepare();
-    const std::string err_local = rc ? c->err : std::string();
-    int who = -1;
-    uint64_t what = 0;                                            // 1: no memory, 2: anything else
-    int crc = gather_agree(comm, rc == KATGPU_ERR_NOMEM ? 1 : rc ? 2 : 0, &who, &what);
-    if (crc) return rc ? rc : crc;
-    if (who >= 0) {
-        if (rc) { c->err = err_local; return rc; }
-        if (what == 1) return fail(c, KATGPU_ERR_NOMEM, "profile gathered: rank %d of %d has no device memory for a batch of %zu window starts", who, world, batch);
-        return fail(c, KATGPU_ERR_DEVICE, "profile gathered: rank %d could not read its table", who);
-    }
+    int rc = comm_agree_to_start(comm, prepare(), [&](int p, int code) {
+        if (code == KATGPU_ERR_NOMEM) return fail(c, code, "profile gathered: rank %d of %d has no device memory for a batch of %zu window starts", p, world, batch);
+        return fail(c, code, "profile gathered: rank %d could not read its table", p);
+    });
+    if (rc) return rc;
     uint64_t* run_cnt = run.as<uint64_t>();
     uint32_t* run_idx = (uint32_t*)(run.as<uint8_t>() + idx_off);
     unsigned long long* run_len = (unsigned long long*)(run.as<uint8_t>() + len_off);
 
-    // ---- the batches.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end ----
+    // ---- the batches.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end (comm_agree_done) ----
     uint64_t n_batches = 0, records = 0, wire_bytes = 0;
     std::vector<uint64_t> lens((size_t)world, 0);
     auto one_batch = [&](size_t pos) -> int {
@@ -185,7 +171,7 @@ extern "C" int katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_tabl
         HIPCHK(c, hipStreamSynchronize(c->stream));             // (the run is whole before it travels)
         if (own > starts) return fail(c, KATGPU_ERR_DEVICE, "profile gathered: a run of %llu records from %zu windows", own, starts);
         const uint64_t mine = own;
-        int rc = comm_allgather_u64(comm, &mine, 1, lens.data());
+        int rc = allgather_u64(comm, &mine, 1, lens.data());
         if (rc) return rc;
         uint64_t total = 0;
         for (uint64_t l : lens) total += l;
@@ -198,7 +184,7 @@ extern "C" int katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_tabl
                 uint64_t at = lens[0];                           // the remote runs behind rank 0's own, in rank order
                 for (int p = 1; p < world; at += lens[p++]) { recvs.push_back({p, run_idx + at, (size_t)lens[p] * sizeof(uint32_t)}); recvs.push_back({p, run_cnt + at, (size_t)lens[p] * sizeof(uint64_t)}); }
             }
-            rc = comm_transfer(comm, sends, recvs);
+            rc = transfer_sync(comm, sends, recvs);
             if (rc) return rc;
         }
         ++n_batches; records += total; wire_bytes += remote * (sizeof(uint32_t) + sizeof(uint64_t));
@@ -215,12 +201,8 @@ extern "C" int katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_tabl
         return KATGPU_OK;
     };
     for (size_t pos = 0; pos < n_out && !rc; pos += batch) rc = one_batch(pos);
-    const std::string err_mine = rc ? c->err : std::string();
-    if (rc) comm_abort(comm);
-    crc = gather_agree(comm, rc ? 1 : 0, &who, &what);
-    if (rc) { c->err = err_mine; return rc == KATGPU_ERR_NOMEM ? KATGPU_ERR_DEVICE : rc; }   // (not the collective one: the peers get an error too)
-    if (crc) return crc;
-    if (who >= 0) return fail(c, KATGPU_ERR_DEVICE, "profile gathered: rank %d failed", who);
+    rc = comm_agree_done(comm, rc, "profile gathered: rank %d failed");
+    if (rc) return rc;
     if (rank == 0 && g_timing)
         fprintf(stderr, "katgpu_timing {\"phase\": \"profile_gathered\", \"batches\": %llu, \"ranks\": %d, \"records\": %llu, \"wire_bytes\": %llu}\n",
                 (unsigned long long)n_batches, world, (unsigned long long)records, (unsigned long long)wire_bytes);

@@ -9,6 +9,8 @@ argv: rank world id_file out_dir k mode
                holds the union), and prints the plan's name; KATGPU_TIMING=1 puts rank 0's jf_dump_gathered lines beside them
         nomem: KATGPU_TEST_JF_GATHER_NOMEM names a rank that reports it could not allocate: every rank must get KATGPU_ERR_NOMEM, no
                file may appear, and the communicator must still carry an all-reduce
+        noopen: rank 0's path lies in a directory that does not exist: every rank must get KATGPU_ERR_IO (rank 0 with the path, its
+               peers naming rank 0), nothing may exist at the path, and the communicator must still carry an all-reduce
 The test imports plans() to know what every rank inserted."""
 import os
 import sys
@@ -174,6 +176,22 @@ def main():
         assert not os.path.exists(path), "a file was created"
         assert int(comm.allreduce_u64([np.array([rank + 1], U64)])[0][0]) == world * (world + 1) // 2
         print("nomem ok rank %d" % rank)
+        t.free()
+    elif mode == "noopen":
+        name, plan = cases[0]
+        t = table(*plan[rank])
+        comm.exchange_merge(t)
+        path = os.path.join(out_dir, "no_such_dir", "noopen.jf")
+        try:
+            comm.jf_dump_gathered(t, path)
+            raise SystemExit("rank %d: the dump went through" % rank)
+        except kat_amd.KatGpuError as e:
+            assert e.code == 2, (rank, e.code, e.message)
+            assert ("cannot open " + path if rank == 0 else "rank 0 cannot open the output file") in e.message, e.message
+        comm.barrier()
+        assert not os.path.lexists(path) and not os.path.lexists(os.path.dirname(path)), "something was created"
+        assert int(comm.allreduce_u64([np.array([rank + 1], U64)])[0][0]) == world * (world + 1) // 2
+        print("noopen ok rank %d" % rank)
         t.free()
     else:
         for ci, (name, plan) in enumerate(cases):

@@ -162,6 +162,21 @@ def test_no_go_is_collective_and_leaves_no_file(tmp_path, fake_rccl, world, tran
     assert not any("jf_dump_gathered" in o for o in outs)
 
 
+@pytest.mark.parametrize("world,transport,k", [(2, "shm", 27), (3, "rccl", 45)])
+def test_unopenable_output_is_collective_and_leaves_no_file(tmp_path, fake_rccl, world, transport, k):  # noqa: F811
+    """Rank 0's path lies in a directory that does not exist: every rank returns KATGPU_ERR_IO -- rank 0 naming the path, its peers
+    rank 0 -- none hangs (a rank that reaches _launch's time limit fails the test), nothing exists at the path, and the communicator
+    carries an all-reduce afterwards (asserted in the rank script).  50 to 60 k-mers a rank at 64 records a range: more than one range."""
+    env = {"KATGPU_COMM_TRANSPORT": transport, "KATGPU_JF_RANGE_RECORDS": "64"}
+    if transport == "rccl":
+        env["KATGPU_RCCL_LIB"] = fake_rccl
+    outs = _launch(tmp_path, world, k, "noopen", env, 120 if world == 2 else 150)
+    for r, o in enumerate(outs):
+        assert "noopen ok rank %d" % r in o, o[-2000:]
+    assert not (tmp_path / "no_such_dir").exists()
+    assert not any("jf_dump_gathered" in o for o in outs)
+
+
 @pytest.mark.parametrize("k", [27, 45])
 def test_records_of_a_table_are_what_they_were(engine, tmp_path, k):
     """katgpu_table_jf_records_device[_wide], whose range producer now takes its records from a table or from packed runs: the bytes of
