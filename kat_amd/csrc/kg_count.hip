@@ -253,12 +253,14 @@ static int with_stamps(katgpu_ctx* c, unsigned long long* dev, int n, const Stam
 // Level 3 of a pass: one workgroup per region of buckets [g.b_lo, g.b_hi) -- region into LDS, its run applied, region written back
 // (kg_partition.hpp: k_p3_apply_pk for packed tables, k_p3_apply2 for KV12).  A table's first round claims its new k-mers inside
 // the probe rounds (INLINE_CLAIM); the test suite's spill hook has its own instantiations.
+struct ApplyForm { bool packed; int block, kp; bool fresh /* inline claims */, hooked; };      // the instantiation that ran, for KATGPU_TRACE's "partition forms" line
 struct ApplyLaunch {                                         // what every instantiation is launched with
     katgpu_table* t; const PartGeom& g; const uint64_t* off2; const uint8_t* l2_buf; uint64_t* spill_buf; unsigned long long* spill_n; const uint32_t* run_len; const uint64_t* bucket_end;
-    dim3 grid; size_t lds; uint32_t qcap; uint64_t seg_len; uint32_t zero_fill;
+    dim3 grid; size_t lds; uint32_t qcap; uint64_t seg_len; uint32_t zero_fill; ApplyForm* form;
 };
 template <int B, int KP, int HB, bool INL, bool HK, bool PF, int NR, bool STAMP = false>
 static int apply_pk(const ApplyLaunch& a) {
+    if (a.form) *a.form = ApplyForm{true, B, KP, INL, HK};
     return launch_lds(a.t->ctx, k_p3_apply_pk<B, KP, HB, INL, HK, PF, NR, STAMP>, a.grid, dim3(B), a.lds, LDS_BYTES - 256, a.t->dv, a.g, a.off2, a.l2_buf, a.spill_buf, a.spill_n, a.run_len, a.bucket_end,
                       a.qcap, a.seg_len, g_test_spill_mod, a.zero_fill);
 }
@@ -275,6 +277,7 @@ static int apply_pk_shape(const ApplyLaunch& a, uint32_t blk, bool fresh, bool h
 }
 template <int B, int KP, int HB, bool INL, int QC, bool HK>
 static int apply_kv12(const ApplyLaunch& a) {
+    if (a.form) *a.form = ApplyForm{false, B, KP, INL, HK};
     return launch_lds(a.t->ctx, k_p3_apply2<B, KP, 4, 3, HB, false, INL, true, QC, HK>, a.grid, dim3(B), a.lds, LDS_BYTES - 256, a.t->dev(), a.g, a.off2, a.l2_buf, a.spill_buf, a.spill_n, a.run_len, a.bucket_end,
                       (unsigned long long*)nullptr, g_test_spill_mod, a.seg_len);
 }
@@ -287,12 +290,12 @@ static int apply_kv12_shape(const ApplyLaunch& a, uint32_t blk, bool big, bool f
     return fresh ? apply_kv12<1024, 4, HB, true, AP2_QCAP, false>(a) : apply_kv12<1024, 4, HB, false, AP2_QCAP, false>(a);
 }
 static int launch_apply(katgpu_table* t, const PartGeom& g, const uint64_t* off2, const uint8_t* l2_buf, uint64_t* spill_buf, unsigned long long* spill_n,
-                        const uint32_t* run_len, const uint64_t* bucket_end) {
+                        const uint32_t* run_len, const uint64_t* bucket_end, ApplyForm* form = nullptr) {
     katgpu_ctx* c = t->ctx;
     const uint32_t n_cu = (uint32_t)c->n_cu, regions = (g.b_hi - g.b_lo) * g.P2;
     const bool fresh = t->distinct == 0;                     // (inline claims in a table's first round)
     const bool hooked = g_test_spill_mod != 0;
-    ApplyLaunch a{t, g, off2, l2_buf, spill_buf, spill_n, run_len, bucket_end, dim3(1), 0, 0, 0, 0};
+    ApplyLaunch a{t, g, off2, l2_buf, spill_buf, spill_n, run_len, bucket_end, dim3(1), 0, 0, 0, 0, form};
     int rc = KATGPU_OK;
     if (g.cbits) {
         // 512-thread workgroups, as many per CU as the LDS holds next to their queues (two at the bench's 9344-slot regions, four for
@@ -429,6 +432,7 @@ static size_t round_starts(size_t left, size_t round_items, double items_per_sta
 // (count + scan + scatter) otherwise, and for the rest of the call once a segmented round overflowed.  The segmented edition's BLOCK
 // form (kg_l1_blocks.hpp): 6-byte items in 64-byte blocks of ten, one 1024-thread workgroup per CU, 16 K-base tiles.
 enum class L1Edition { Blocks, SegLean512, SegLean1024, SegPlain512, SegPlain1024, ExactLean, ExactPlain };
+static const char* const L1_EDITION_NAME[] = {"Blocks", "SegLean512", "SegLean1024", "SegPlain512", "SegPlain1024", "ExactLean", "ExactPlain"};   // (KATGPU_TRACE)
 struct L1Plan {
     L1Edition edition; bool seg /* a segmented edition: level 2 reads segments (blocks of ten from Blocks, else groups) */; uint32_t wgs /* workgroups (<= W: the small arrays hold them) */; uint64_t n_tiles, tiles_per_wg;
     uint64_t seg_cap, cap_plain, stride64;   // segmented: slots of a segment; k-mers it is expected to take at most (what the spill list must hold: 8 bytes each); bytes of a bucket (l1_bucket_base's + 32)
@@ -519,7 +523,9 @@ static int level1(katgpu_table* t, const PartGeom& g, const L1Plan& l1, const Pa
 // One pass over the bucket when the runs are predictable (k_p2_fast, k_p2x_fast: fixed-capacity runs, an overflow list), else -- or when
 // that list did not hold -- the exact two-pass kernel (k_p2).  Which instantiation: the item width g.hb and what level 1 wrote.
 enum class L1Items { Groups /* of four items of at most 48 bits */, WideGroups /* g.hb1 == 4 */, Blocks /* of ten (kg_l1_blocks.hpp) */ };
-struct L2Pass { katgpu_ctx* c; const PartGeom& g; const PartArena& A; uint32_t grid; L1Items src; uint64_t seg_slots; };
+static const char* const L1_ITEMS_NAME[] = {"Groups", "WideGroups", "Blocks"};                                                            // (KATGPU_TRACE)
+enum L2Family : uint32_t { L2_BLOCKS = 1 /* kg_l2_blocks.hpp */, L2_ONE_PASS = 2 /* k_p2_fast */, L2_EXACT = 4 /* k_p2 */ };           // the kernel families of level 2, as bits
+struct L2Pass { katgpu_ctx* c; const PartGeom& g; const PartArena& A; uint32_t grid; L1Items src; uint64_t seg_slots; uint32_t* families /* |= what ran (KATGPU_TRACE) */; };
 template <typename K>
 static int p2_one_pass(const L2Pass& x, K kern, size_t lds, unsigned long long* stamps = nullptr) {
     return launch_lds(x.c, kern, dim3(x.grid), dim3(PART_BLOCK), lds, lds, x.g, x.A.l1_off, x.A.l1_buf, x.A.l2_buf, x.A.off2, x.A.cnt2, x.A.ovf_buf, x.A.ovf_n, x.A.ovf_cap, x.seg_slots, stamps);
@@ -532,6 +538,7 @@ template <int HB>
 static int launch_l2_hb(const L2Pass& x, bool one_pass) {
     constexpr size_t lds_e = sizeof(P2Lds<HB>), lds_f = sizeof(typename P2FastLds<HB>::type);
     unsigned long long* const stamps = x.A.spill_n + STAMP_AT;
+    if (x.families) *x.families |= !one_pass ? L2_EXACT : x.src == L1Items::Blocks && HB == 1 ? L2_BLOCKS : L2_ONE_PASS;
     switch (x.src) {
     case L1Items::Blocks:
         if constexpr (HB == 4) break;
@@ -609,6 +616,8 @@ static int level2_and_apply(katgpu_table* t, PartGeom& g, const L1Plan& l1, cons
     }
     const bool try_fast0 = *p2_fast_ok && (g_p2_fast == 2 || items / g.R >= 1024);
     unsigned long long ovf_total = ovf_l1;                                 // entries of the overflow list so far (level 1's, then every pass's)
+    uint32_t l2_families = 0;                                              // what ran, for the trace's "partition forms" line
+    ApplyForm ap{};
     if (g_trace && g.P1 > step) fprintf(stderr, "[katgpu]   level 2 + apply in %u passes of %u buckets (level-2 buffer: %zu items)\n", (g.P1 + step - 1) / step, step, A.l2_items);
     for (uint32_t b_lo = 0; b_lo < g.P1; b_lo += step) {
         g.b_lo = b_lo; g.b_hi = std::min(g.P1, b_lo + step);
@@ -618,7 +627,7 @@ static int level2_and_apply(katgpu_table* t, PartGeom& g, const L1Plan& l1, cons
         uint64_t* spill_buf = (uint64_t*)(A.l1_buf + l1_at(b_lo));
         g.spill_cap = (l1_at(g.b_hi) - l1_at(b_lo)) / 8;
         const bool try_fast = try_fast0 && *p2_fast_ok;
-        const L2Pass x{c, g, A, std::min<uint32_t>(g.b_hi - g.b_lo, (uint32_t)c->n_cu), src, seg_slots};      // one workgroup per CU
+        const L2Pass x{c, g, A, std::min<uint32_t>(g.b_hi - g.b_lo, (uint32_t)c->n_cu), src, seg_slots, &l2_families};      // one workgroup per CU
         HIPCHK(c, hipMemsetAsync(A.spill_n, 0, sizeof(unsigned long long), c->stream));
         int rc = KATGPU_OK;
         if (try_fast) { ScopedTimer tm(c, KATGPU_K_PART_L2, pass_items); rc = launch_l2(x, true); }
@@ -637,7 +646,7 @@ static int level2_and_apply(katgpu_table* t, PartGeom& g, const L1Plan& l1, cons
         ovf_total = overflowed;
         {   // (exact level 2: a bucket's runs stop short of the next bucket's -- bend)
             ScopedTimer tm(c, KATGPU_K_PART_APPLY, pass_items);
-            rc = launch_apply(t, g, A.off2, A.l2_buf, spill_buf, A.spill_n, runs ? A.cnt2 : nullptr, runs ? nullptr : A.bend);
+            rc = launch_apply(t, g, A.off2, A.l2_buf, spill_buf, A.spill_n, runs ? A.cnt2 : nullptr, runs ? nullptr : A.bend, &ap);
         }
         if (rc) return rc;
         HIPCHK(c, hipGetLastError());
@@ -649,6 +658,14 @@ static int level2_and_apply(katgpu_table* t, PartGeom& g, const L1Plan& l1, cons
         if (spilled) lists->push_back({spill_buf, spilled});
     }
     if (ovf_total) lists->push_back({A.ovf_buf, ovf_total});                // what level 1 / level 2 could not place
+    // the kernel forms this round ran (tests/test_gpu_partition_forms.py reads the line): level-1 edition, what level 2 read and the item widths,
+    // level 2's kernel families in the order blocks, one-pass, exact (more than one: a pass fell back), the apply instantiation
+    if (g_trace) {
+        char l2[32];
+        snprintf(l2, sizeof l2, "%s%s%s", l2_families & L2_BLOCKS ? "+blocks" : "", l2_families & L2_ONE_PASS ? "+one-pass" : "", l2_families & L2_EXACT ? "+exact" : "");
+        fprintf(stderr, "[katgpu] partition forms: l1=%s items=%s hb1=%u hb=%u l2=%s apply=%s B=%d KP=%d fresh=%d%s\n", L1_EDITION_NAME[(int)l1.edition], L1_ITEMS_NAME[(int)src], g.hb1, g.hb,
+                l2[0] ? l2 + 1 : "none", ap.packed ? "packed" : "KV12", ap.block, ap.kp, (int)ap.fresh, ap.hooked ? " hooked" : "");
+    }
     return KATGPU_OK;
 }
 // regions that ran out of slots, runs beyond their capacity: make room, then the direct path
