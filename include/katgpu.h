@@ -237,6 +237,29 @@ int katgpu_table_record_regions_host(katgpu_table* t, const char* bases, size_t 
 int katgpu_table_record_regions_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
                                        const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, const katgpu_count_range* ranges,
                                        uint32_t n_ranges, katgpu_region* dev_regions, size_t cap, size_t n_out[/* n_ranges */]);
+/* `kat sect` without -n: the text Sect::printCounts (src/sect.cc:328-346) writes to -counts.cvg for a record, without its ">name"
+ * line, rendered on the device.  Records are given as for katgpu_table_seq_hits_*; nb = rec_len - k + 1 when rec_len >= k, else 0;
+ * c[j] is what katgpu_table_profile_* writes for window j of a record (the full 64-bit count, side table included; 0 for a window
+ * holding a byte outside ACGTacgt and for an absent k-mer).  A record's text is c[0] ... c[nb - 1] in decimal with one space between
+ * them and '\n' behind the last, or "0\n" when nb == 0 (rec_len < k, rec_len == 0).  The call's text is the records' texts one after
+ * another; text_off[r], r = 0 .. n_rec, is the byte record r's text starts at, text_off[n_rec] the total.  Both key widths and both
+ * table layouts.  No per-position array crosses the bus in either form: the text and 8 bytes per record come back.
+ * Host form: validates the records (KATGPU_ERR_INVALID_ARG, the messages of katgpu_table_seq_hits_host) and returns one malloc'ed
+ * array of text_off[n_rec] bytes in *text (katgpu_free_host; never NULL on success), brought back through the context's two pinned
+ * buffers (64 MiB each, made on first use).  Device memory, beyond the table and from the context's pool: the records go through in
+ * batches of at most B = 2^25 bases and 2^20 records, a record longer than B being a batch of its own: max(B, L) + 64 bytes of
+ * bases, with L the longest record, and 32 bytes per record of a batch; 8 bytes per window start of a batch for the counts, 8 bytes
+ * per 4096 bases for the tile sums, and the batch's text: a count has at most 20 digits, so at most 21 bytes per window start --
+ * 704 MiB for a full batch -- and 2 to 3 where counts are coverage.  KATGPU_ERR_NOMEM, with a message, when that cannot be had.
+ * Device form: takes device pointers, does not validate the records, and takes the counts, tile sums and 8 bytes per record above,
+ * for all n bases, from the pool.  It writes the first min(*total, cap) bytes of the text to dev_text and always writes all of
+ * dev_text_off and reports the true total: a caller that sees *total > cap calls again with more room.  cap == 0 with dev_text ==
+ * NULL only sizes.  It returns when the work is done. */
+int katgpu_table_record_cvg_text_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                                      size_t n_rec, int canonicalise, char** text, uint64_t* text_off /* n_rec + 1 */);
+int katgpu_table_record_cvg_text_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                        const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, uint8_t* dev_text, size_t cap,
+                                        uint64_t* dev_text_off /* n_rec + 1 */, uint64_t* total);
 /* All (key,count) pairs in unspecified order (the eager_iterator walk, JF/.../large_hash_iterator.hpp:28-65).
  * Pass cap = 0 to query *n_out only. */
 int katgpu_table_export(katgpu_table* t, uint64_t* keys, uint64_t* counts, size_t cap, size_t* n_out);

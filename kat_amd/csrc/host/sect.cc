@@ -3,8 +3,10 @@
 // The reference walks each record with substr + validKmer + mer_dna + JellyfishHelper::getCount (src/sect.cc:516-535), one
 // record per std::thread.  Here a batch of records is joined into one base buffer and profiled by a single
 // katgpu_table_profile_host call; what stays on the host is what the reference also does after the lookups: the
-// per-record statistics and the text.  When no per-position output is asked for (-n without -E / -F) the statistics are the
-// device's too (katgpu_table_record_stats_host) and no count comes back.  Records are read with the semantics of the vendored SeqAn 2.0.0 reader
+// per-record statistics and the text.  When no per-position output is asked for (-n) the device keeps the counts to itself: the
+// per-record statistics (katgpu_table_record_stats_host) and the regions of -E / -F (katgpu_table_record_regions_host) come back.
+// With KATGPU_SECT_DEVICE_TEXT=1 that holds without -n as well: the lines of -counts.cvg are rendered on the device
+// (katgpu_table_record_cvg_text_host) and no count comes back in any one-GPU mode.  Records are read with the semantics of the vendored SeqAn 2.0.0 reader
 // (deps/seqan-library-2.0.0/include/seqan/seq_io/fasta_fastq.h:306-380, CharString target).
 #include "kat_host.hpp"
 #include "record_stats_host.hpp"
@@ -362,14 +364,19 @@ void Sect::processSeqFile() {                                                   
     vector<uint64_t> counts, offs, lens;
     vector<katgpu_record_stats> stats;
     // -n: nothing per position is written.  The device reduces the counts per record, and with -E / -F it finds the regions as well
-    // (one GPU: the statistics and regions kernels look a window up in the table of their own rank only)
-    const bool stats_only = noCountStats && !dist;
+    // (one GPU: the statistics, regions and text kernels look a window up in the table of their own rank only).
+    // KATGPU_SECT_DEVICE_TEXT=1: the same without -n, the lines of -counts.cvg rendered on the device too.  It is asked for, not the
+    // default: a one-GPU run without -n is pinned to the per-position profile by the suite (tests/test_gpu_record_stats.py).
+    const char* dt = getenv("KATGPU_SECT_DEVICE_TEXT");
+    const bool cvg_text = !dist && !noCountStats && dt && atoi(dt) != 0, stats_only = !dist && (noCountStats || cvg_text);
     vector<katgpu_count_range> ranges;
     if (stats_only && extractNR) ranges.push_back({1, minRepeat});
     if (stats_only && extractR) ranges.push_back({minRepeat, maxRepeat});
     katgpu_region* found = nullptr;
     size_t n_found[2] = {0, 0};
     vector<size_t> first_nr, first_r;                         // a record's regions: [first[i], first[i + 1]) of its range's
+    char* cvg = nullptr;                                      // the batch's -counts.cvg lines: record i's is [cvg_off[i], cvg_off[i + 1])
+    vector<uint64_t> cvg_off;
     // KATGPU_TIMING: where the phase's wall time goes (reader | joined buffer | device call | per-record host work | text), one line on stderr
     double t_part[5] = {0, 0, 0, 0, 0};
     auto lap = [&, t = std::chrono::steady_clock::now()](int part) mutable {
@@ -410,6 +417,11 @@ void Sect::processSeqFile() {                                                   
                 if (extractNR) index(first_nr, found, n_found[0]);
                 if (extractR) index(first_r, found + (extractNR ? n_found[0] : 0), n_found[extractNR ? 1 : 0]);
             }
+            if (cvg_text) {
+                cvg_off.resize(n + 1);
+                Engine::check(katgpu_table_record_cvg_text_host(input.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, input.canonical ? 1 : 0,
+                                                                &cvg, cvg_off.data()));
+            }
         } else if (dist) {
             if (speak && counts.size() < joined.size()) counts.resize(joined.size());
             Engine::profileGathered(input.hash, joined.data(), joined.size(), input.canonical, speak ? counts.data() : nullptr);
@@ -445,7 +457,8 @@ void Sect::processSeqFile() {                                                   
         char line[512];
         for (size_t i = 0; i < n; i++) {
             const Record& r = recs[i];
-            if (!noCountStats) count_path_stream << r.cvg_txt;
+            if (cvg_text) { count_path_stream << '>' << *r.name << '\n'; count_path_stream.write(cvg + cvg_off[i], (std::streamsize)(cvg_off[i + 1] - cvg_off[i])); }
+            else if (!noCountStats) count_path_stream << r.cvg_txt;
             if (outputGCStats) gc_count_path_stream << r.gc_txt;
             if (extractNR) nr_path_stream << r.nr_txt;
             if (extractR) r_path_stream << r.r_txt;
@@ -455,6 +468,8 @@ void Sect::processSeqFile() {                                                   
             cvg_gc_stream << *r.name << line;
             if (r.mx_x < gcBins && r.mx_y < cvgBins) contamination_mx.data()[(size_t)r.mx_x * cvgBins + r.mx_y] += seqs[i].size();
         }
+        katgpu_free_host(cvg);
+        cvg = nullptr;
         lap(4);
         if (verbose) std::cerr << "done" << endl;
     }

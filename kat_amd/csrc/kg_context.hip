@@ -262,6 +262,18 @@ void release_arena(katgpu_ctx* c) {
     c->arena_busy = false;
 }
 
+// the context's two pinned staging buffers and their events: made on first use, kept until katgpu_shutdown
+int ensure_pinned(katgpu_ctx* c) {
+    if (c->stage_bytes) return KATGPU_OK;
+    const size_t bytes = (size_t)64 << 20;
+    for (int i = 0; i < 2; ++i) {
+        if (!c->pinned[i]) HIPCHK(c, hipHostMalloc((void**)&c->pinned[i], bytes, hipHostMallocDefault));
+        if (!c->pin_free[i]) HIPCHK(c, hipEventCreateWithFlags(&c->pin_free[i], hipEventDisableTiming));
+    }
+    c->stage_bytes = bytes;
+    return KATGPU_OK;
+}
+
 // ------------------------------------------------------------------ device buffers + synthetic workload
 
 extern "C" int katgpu_dev_alloc(katgpu_ctx* c, size_t bytes, void** p) {

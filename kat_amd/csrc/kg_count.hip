@@ -937,14 +937,7 @@ static const size_t g_ring_bytes = (getenv("KATGPU_RING_MB") ? std::max<size_t>(
 // want: bytes of stream the caller expects (0: unknown): small inputs get small rings (two 1 GiB rings for a 100-base call, or for
 // the CLI on the reference's 1000-read test files, would be most of the call's time and could fail on a full device)
 static int ensure_staging(katgpu_ctx* c, size_t want = 0) {
-    if (!c->stage_bytes) {
-        const size_t bytes = (size_t)64 << 20;
-        for (int i = 0; i < 2; ++i) {
-            HIPCHK(c, hipHostMalloc((void**)&c->pinned[i], bytes, hipHostMallocDefault));
-            HIPCHK(c, hipEventCreateWithFlags(&c->pin_free[i], hipEventDisableTiming));
-        }
-        c->stage_bytes = bytes;
-    }
+    int rc = ensure_pinned(c); if (rc) return rc;
     size_t ring_want = g_ring_bytes;
     if (want) ring_want = std::min(g_ring_bytes, std::max<size_t>((size_t)16 << 20, align_up(want + 4096, (size_t)16 << 20)));
     if (c->ring_bytes && c->ring_bytes < ring_want) {              // grown for a bigger input

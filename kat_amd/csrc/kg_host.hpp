@@ -2,7 +2,7 @@
 // handles of include/katgpu.h, error plumbing, the allocation pool, launch timing.  The library is split by concern:
 //   kg_context.hip   context, pool, profile counters, device buffers, the synthetic workload
 //   kg_table.hip     table life cycle: geometry, create / regrow / free, counters and statistics, room for records to come
-//   kg_query.hip     a sequence or keys against a table: lookups, profiles (one table, or the ranks' tables gathered), per-record hits, coverage statistics and count-range regions
+//   kg_query.hip     a sequence or keys against a table: lookups, profiles (one table, or the ranks' tables gathered), per-record hits, coverage statistics, count-range regions and -counts.cvg text
 //   kg_records.hip   records out of a table and into one: partition / export / merge, the k-mer filter
 //   kg_jf_device.hip .jf records in file order out of a table, and streamed from a file into one
 //   kg_count.hip     counting: the direct kernel, the partitioned counter's host loop, the host feeder, katgpu_count*
@@ -171,6 +171,7 @@ void pool_trim(katgpu_ctx* c);
 hipError_t pool_alloc(katgpu_ctx* c, void** p, size_t bytes, bool take_reservation = false);
 void pool_release(katgpu_ctx* c, void* p);
 void release_arena(katgpu_ctx* c);
+int ensure_pinned(katgpu_ctx* c);              // c->pinned[0 .. 1] of c->stage_bytes each, c->pin_free[0 .. 1]
 
 // a string inside a JSON line (the katgpu_timing lines): quotes, backslashes and control characters escaped
 inline std::string json_escaped(const char* s) {

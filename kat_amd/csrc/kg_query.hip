@@ -1,12 +1,13 @@
 // kg_query.hip -- a sequence or keys against a table, which is left as it is: batch lookups (katgpu_table_get*), per-position profiles
 // (katgpu_table_profile_*; _gathered_host: of a table that lies on several ranks, gathered on rank 0), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*), the per-record coverage statistics
-// of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*) and the count-range regions of `kat sect -n -E / -F` (katgpu_table_record_regions_*).  The host forms send their input through the device in batches.
+// of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*) the count-range regions of `kat sect -E / -F` (katgpu_table_record_regions_*) and the -counts.cvg text of `kat sect` (katgpu_table_record_cvg_text_*).  The host forms send their input through the device in batches.
 #include "kg_host.hpp"
 #include "kg_comm.hpp"
 #include "kg_kernels.hpp"
 #include "kg_filter.hpp"
 #include "kg_record_stats.hpp"
 #include "kg_record_regions.hpp"
+#include "kg_cvg_text.hpp"
 
 static const bool g_forbid_profile_host = hook_u64("KATGPU_TEST_FORBID_PROFILE_HOST", 0) != 0;   // tests: a driver that should not need per-position counts asks for none
 static const size_t g_profile_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_PROFILE_BATCH", (uint64_t)32 << 20), 1);   // tests: window starts per batch of profile_host
@@ -531,5 +532,165 @@ extern "C" int katgpu_table_record_regions_host(katgpu_table* t, const char* bas
         at += found[q].size(); n_out[q] = found[q].size();
     }
     *regions = res;
+    return KATGPU_OK;
+}
+
+// ------------------------------------------------------------------ the -counts.cvg text of records (kat sect) ----
+
+static const size_t g_cvg_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_CVG_BATCH", (uint64_t)32 << 20), 1);   // tests: bases per batch of the host form
+
+// the workspace of one call or batch of n bases and n_rec records: a count per window start | a sum per tile | the window-less records' bytes
+// before every record | the two totals | (with_off: the host form's) a text offset per record and one more
+struct CvgWork {
+    DevBuf buf;
+    size_t bytes = 0;
+    uint64_t n_tiles = 0;
+    uint64_t *counts = nullptr, *extra = nullptr, *text_off = nullptr;
+    unsigned long long *tile_sum = nullptr, *totals = nullptr;
+    int fit(katgpu_ctx* c, size_t n, uint32_t k, size_t n_rec, bool with_off) {
+        n_tiles = n / CT_TILE + 1;                                 // positions 0 .. n
+        const size_t n_out = n >= k ? n - k + 1 : 0;
+        const size_t sum_off = align_up(n_out * 8, 16), extra_off = sum_off + n_tiles * 8, tot_off = extra_off + n_rec * 8, off_off = tot_off + 16;
+        const size_t need = off_off + (with_off ? (n_rec + 1) * 8 : 0);
+        if (need > bytes) {
+            bytes = 0;
+            if (buf.pooled(c, need) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(c, KATGPU_ERR_NOMEM, "cvg text: no %zu bytes of device memory for the counts of %zu bases and %zu records", need, n, n_rec);
+            }
+            bytes = need;
+        }
+        uint8_t* w = buf.as<uint8_t>();
+        counts = (uint64_t*)w; tile_sum = (unsigned long long*)(w + sum_off); extra = (uint64_t*)(w + extra_off);
+        totals = (unsigned long long*)(w + tot_off); text_off = (uint64_t*)(w + off_off);
+        return KATGPU_OK;
+    }
+};
+
+// On the stream: k_profile over the n bases, K18 without writing, K19; w.totals then holds the bytes of the windows and of the window-less records.
+static int launch_cvg_size(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec,
+                           int canonicalise, CvgWork& w) {
+    katgpu_ctx* c = t->ctx;
+    const uint32_t k = t->dev().k;
+    if (n >= k) { int rc = launch_profile(t, dev_bases, n, canonicalise, w.counts); if (rc) return rc; }
+    ScopedTimer tm(c, KATGPU_K_PROFILE, 0);                        // (launch_profile has counted the window starts)
+    const dim3 grid((unsigned)std::min<uint64_t>(w.n_tiles, (uint64_t)c->n_cu * 8));
+    hipLaunchKernelGGL(k_cvg_tiles<false>, grid, dim3(CT_BLOCK), 0, c->stream, w.counts, (uint64_t)n, k, dev_start, dev_len, (uint64_t)n_rec, w.n_tiles, w.tile_sum,
+                       w.extra, w.totals, (uint64_t)0, (uint8_t*)nullptr, (uint64_t)0, (uint64_t*)nullptr);
+    hipLaunchKernelGGL(k_cvg_scan, dim3(2), dim3(CT_SCAN_BLOCK), 0, c->stream, w.tile_sum, w.n_tiles, dev_len, (uint64_t)n_rec, k, w.extra, w.totals);
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+// K18 again behind it: the first `cap` bytes of the text to dev_text, the records' offsets (n_rec + 1, counted from text_base) to dev_text_off
+static int launch_cvg_write(katgpu_table* t, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec, const CvgWork& w, uint64_t text_base,
+                            uint8_t* dev_text, size_t cap, uint64_t* dev_text_off) {
+    katgpu_ctx* c = t->ctx;
+    ScopedTimer tm(c, KATGPU_K_PROFILE, 0);
+    const dim3 grid((unsigned)std::min<uint64_t>(w.n_tiles, (uint64_t)c->n_cu * 8));
+    hipLaunchKernelGGL(k_cvg_tiles<true>, grid, dim3(CT_BLOCK), 0, c->stream, w.counts, (uint64_t)n, t->dev().k, dev_start, dev_len, (uint64_t)n_rec, w.n_tiles, w.tile_sum,
+                       w.extra, w.totals, text_base, dev_text, (uint64_t)cap, dev_text_off);
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+extern "C" int katgpu_table_record_cvg_text_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                                   const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, uint8_t* dev_text, size_t cap,
+                                                   uint64_t* dev_text_off, uint64_t* total) {
+    if (!t || !total || !dev_text_off || (n_rec && (!dev_rec_start || !dev_rec_len)) || (n && !dev_bases) || (cap && !dev_text)) return KATGPU_ERR_INVALID_ARG;
+    *total = 0;
+    katgpu_ctx* c = t->ctx;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    if (!n_rec) {
+        HIPCHK(c, hipMemsetAsync(dev_text_off, 0, sizeof(uint64_t), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KATGPU_OK;
+    }
+    CvgWork w;
+    rc = w.fit(c, n, t->dev().k, n_rec, false); if (rc) return rc;
+    rc = launch_cvg_size(t, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, canonicalise, w);
+    if (!rc) rc = launch_cvg_write(t, n, dev_rec_start, dev_rec_len, n_rec, w, 0, dev_text, cap, dev_text_off);
+    unsigned long long totals[2] = {0, 0};
+    hipError_t e = hipMemcpyAsync(totals, w.totals, sizeof totals, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "cvg text: %s", hipGetErrorString(e));
+    *total = totals[0] + totals[1];
+    return KATGPU_OK;
+}
+
+// Host form: the records go through the device in batches of at most g_cvg_batch bases and 2^20 records (for_record_batches), so any input
+// fits next to the table.  Per batch the totals come back first, then room for the batch's text is found on the device and in the
+// result, K18 fills it, and it comes back through the context's two pinned buffers, one being copied out while the other fills;
+// the offsets of a batch count from the call's first byte.
+extern "C" int katgpu_table_record_cvg_text_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                                                 size_t n_rec, int canonicalise, char** text, uint64_t* text_off) {
+    if (!t || !text || !text_off || (n_rec && (!rec_start || !rec_len)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    katgpu_ctx* c = t->ctx;
+    *text = nullptr;
+    char* res = nullptr;
+    size_t have = 0, res_cap = 0;
+    if (n_rec) {
+        int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;
+        HIPCHK(c, hipSetDevice(c->device));
+        rc = refresh_counters(t); if (rc) return rc;
+        rc = ensure_pinned(c); if (rc) return rc;
+        const uint32_t k = t->dev().k;
+        const size_t max_recs = std::min(n_rec, (size_t)1 << 20);
+        DevBuf recs, out;                                          // start and length of every record of a batch; the text of a batch
+        size_t out_cap = 0;
+        if (recs.pooled(c, max_recs * 2 * sizeof(uint64_t)) != hipSuccess)
+            return fail(c, KATGPU_ERR_NOMEM, "cvg text: no device memory for the records of a batch");
+        uint64_t* dr = recs.as<uint64_t>();
+        CvgWork w;
+        size_t no_room = 0;
+        rc = for_record_batches(c, bases, n, rec_start, rec_len, n_rec, g_cvg_batch, max_recs, dr, dr + max_recs, "cvg text", &no_room,
+                                [](size_t, bool) { return true; },
+                                [&](const uint8_t* db, size_t nb, const uint64_t* ds, const uint64_t* dl, size_t m, size_t r0) {
+            int rc = w.fit(c, nb, k, m, true); if (rc) return rc;
+            rc = launch_cvg_size(t, db, nb, ds, dl, m, canonicalise, w); if (rc) return rc;
+            unsigned long long totals[2] = {0, 0};
+            hipError_t e = hipMemcpyAsync(totals, w.totals, sizeof totals, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "cvg text: %s", hipGetErrorString(e));
+            const size_t total = (size_t)(totals[0] + totals[1]);
+            if (total > out_cap) {
+                out_cap = 0;
+                if (out.pooled(c, total) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return fail(c, KATGPU_ERR_NOMEM, "cvg text: no %zu bytes of device memory for the text of a batch", total);
+                }
+                out_cap = total;
+            }
+            if (have + total > res_cap) {
+                const size_t want = std::max(have + total, res_cap + res_cap / 2);
+                char* grown = (char*)realloc(res, want);
+                if (!grown) return fail(c, KATGPU_ERR_NOMEM, "cvg text: no host memory for %zu bytes of text", want);
+                res = grown; res_cap = want;
+            }
+            rc = launch_cvg_write(t, nb, ds, dl, m, w, have, out.as<uint8_t>(), total, w.text_off); if (rc) return rc;
+            e = hipMemcpyAsync(text_off + r0, w.text_off, m * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+            const size_t piece = c->stage_bytes, n_pieces = (total + piece - 1) / piece;
+            for (size_t i = 0; i <= n_pieces && e == hipSuccess; ++i) {   // piece i on its way into one pinned buffer, piece i - 1 out of the other
+                if (i < n_pieces) {
+                    e = hipMemcpyAsync(c->pinned[i & 1], out.as<uint8_t>() + i * piece, std::min(piece, total - i * piece), hipMemcpyDeviceToHost, c->stream);
+                    if (e == hipSuccess) e = hipEventRecord(c->pin_free[i & 1], c->stream);
+                }
+                if (i && e == hipSuccess) {
+                    e = hipEventSynchronize(c->pin_free[(i - 1) & 1]);
+                    if (e == hipSuccess) memcpy(res + have + (i - 1) * piece, c->pinned[(i - 1) & 1], std::min(piece, total - (i - 1) * piece));
+                }
+            }
+            have += total;
+            return e == hipSuccess ? (int)KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "cvg text: %s", hipGetErrorString(e));
+        });
+        if (no_room) rc = fail(c, KATGPU_ERR_NOMEM, "cvg text: no %zu bytes of device memory for a batch of bases", no_room);
+        if (rc) { free(res); return rc; }
+    }
+    if (!res) res = (char*)malloc(1);
+    if (!res) return fail(c, KATGPU_ERR_NOMEM, "cvg text: no host memory for the text");
+    text_off[n_rec] = have;
+    *text = res;
     return KATGPU_OK;
 }
