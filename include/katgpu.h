@@ -477,6 +477,26 @@ int  katgpu_jf_dump_gathered(katgpu_comm* comm, katgpu_table* t, const char* pat
  * katgpu_timing {"phase": "profile_gathered", "batches": .., "ranks": .., "records": .., "wire_bytes": ..}. */
 int  katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_table* t, const char* bases, size_t n, int canonicalise,
                                         uint64_t* counts /* rank 0; ignored elsewhere, may be NULL */);
+/* katgpu_table_seq_hits_host for the tables of all ranks, after the exchange (`katgpu filter seq --gpus N`): FilterSeq::getProfile +
+ * processSeq, src/filter_sequence.cc:283-430, against a hash that lies on several devices.  Collective: every rank calls it with its own
+ * table and the SAME bases and records; on rank 0, hits[r] is what katgpu_table_seq_hits_host would write for one table holding the
+ * union; `hits` is ignored on the other ranks and may be NULL there.  Both key widths, both table layouts, canonical and
+ * non-canonical tables; a world of one rank runs the whole protocol.  The precondition of katgpu_table_profile_gathered_host holds here too.
+ * The records go through in the batches of the host form (at most 2^26 bases and 2^20 records).  Per batch every rank counts, per
+ * record, the hits among the windows whose k-mer it owns; hits add across owners, so the other ranks send their 8 bytes per record to
+ * rank 0, which adds them to its own and copies the sums to `hits`.  Every rank walks all the bases.
+ * Device memory, from the context's pool and beside the table, for a batch of M = min(n_rec, 2^20) records: 24 M bytes on every rank,
+ * 8 M (world - 1) more on rank 0, and the batch's bases.
+ * The ranks agree on n, n_rec, k and a checksum of the records before anything else: a mismatch, or a rank with unusable pointers, is
+ * KATGPU_ERR_INVALID_ARG on every rank (katgpu_last_error names the rank); the records are then validated as the host form does.
+ * n_rec == 0 is KATGPU_OK everywhere.  They allocate first and agree on that too: when one cannot, every rank returns KATGPU_ERR_NOMEM
+ * (katgpu_last_error names the rank); either way the communicator is as usable as before.  A rank that fails later raises the
+ * communicator's abort flag, so that its peers leave their waits: an error on every rank.
+ * KATGPU_TIMING: rank 0 prints one line per call with records,
+ * katgpu_timing {"phase": "seq_hits_gathered", "batches": .., "ranks": .., "records": .., "wire_bytes": 8 * records * (ranks - 1)}. */
+int  katgpu_table_seq_hits_gathered_host(katgpu_comm* comm, katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start,
+                                         const uint64_t* rec_len, size_t n_rec, int canonicalise,
+                                         uint64_t* hits /* rank 0; ignored elsewhere, may be NULL */);
 /* wall time spent so far in extraction / on the wire (posting + waiting) / merging / all-reducing (ms), bytes sent, merge calls */
 int  katgpu_comm_stats(katgpu_comm* comm, double* ms_extract, double* ms_exchange, double* ms_merge, double* ms_allreduce,
                        uint64_t* bytes_sent, uint64_t* merge_launches);

@@ -44,6 +44,7 @@ EXPORTS = (
     "katgpu_table_add_jf_records_device", "katgpu_jf_load_part",
     "katgpu_table_record_regions_host", "katgpu_table_record_regions_device", "katgpu_jf_dump_gathered",
     "katgpu_table_profile_gathered_host", "katgpu_table_record_cvg_text_host", "katgpu_table_record_cvg_text_device",
+    "katgpu_table_seq_hits_gathered_host",
 )
 
 # katgpu_record_stats: one record of Table.record_stats
@@ -890,6 +891,7 @@ class Comm:
         L.katgpu_allreduce_u64.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.katgpu_jf_dump_gathered.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
         L.katgpu_table_profile_gathered_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.katgpu_table_seq_hits_gathered_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.katgpu_comm_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_uint64)] * 2
         L.katgpu_comm_wire.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         h = C.c_void_p()
@@ -954,6 +956,20 @@ class Comm:
         canon = table.canonical if canonicalise is None else canonicalise
         self.engine._chk(self.engine.L.katgpu_table_profile_gathered_host(self.h, table.h, b.ctypes.data, b.size, int(bool(canon)),
                                                                           out.ctypes.data if out is not None else None))
+        return out
+
+    def seq_hits_gathered(self, table, bases, starts, lens, canonicalise=None):
+        """Collective, after exchange_merge: Table.seq_hits of the records (the same bases, starts and lengths on every rank) against
+        the union of the ranks' tables.  Rank 0 gets the u64[n_rec] array, the other ranks None."""
+        if isinstance(bases, str):
+            bases = bases.encode()
+        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
+        st, ln = np.ascontiguousarray(starts, np.uint64), np.ascontiguousarray(lens, np.uint64)
+        assert st.size == ln.size
+        out = np.zeros(st.size, np.uint64) if self.rank == 0 else None
+        canon = table.canonical if canonicalise is None else canonicalise
+        self.engine._chk(self.engine.L.katgpu_table_seq_hits_gathered_host(self.h, table.h, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size,
+                                                                           int(bool(canon)), out.ctypes.data if out is not None else None))
         return out
 
     def stats(self):

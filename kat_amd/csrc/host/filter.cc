@@ -6,6 +6,8 @@
 // filter seq: the reference looks every window of every record up in the hash (FilterSeq::getProfile) and counts the hits; here a batch of
 // records is joined into one base buffer and katgpu_table_seq_hits_host returns one hit count per record.  What stays on the host is
 // what the reference does after the lookups: the keep decision, the subsampling draw and the output records, in input order.
+// `katgpu filter seq --gpus N`: the hash lies on the ranks by owner and the per-record hits are summed over them on rank 0
+// (katgpu_table_seq_hits_gathered_host), which alone decides and writes.  `filter kmer` stays on one GPU.
 #include "kat_host.hpp"
 
 #include <sys/stat.h>
@@ -16,6 +18,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstring>
+#include <exception>
 #include <fstream>
 #include <iostream>
 #include <random>
@@ -61,14 +64,22 @@ string pathExtension(const string& p) {          // boost::filesystem::path::ext
 // thrown after the stream has been opened, which leaves an empty file behind.
 class SeqWriter {
 public:
-    explicit SeqWriter(const string& path) : os(path.c_str(), std::ios::binary | std::ios::trunc) {
-        if (!os) throw std::runtime_error("Could not open file " + path + ": iostream error");
+    enum Format { FASTA, FASTQ, RAW, UNKNOWN };
+    static Format formatOf(const string& path) {
         string base = path;
         for (const char* z : {".gz", ".bgzf", ".bz2"}) if (endsWithNoCase(base, z)) { base.resize(base.size() - strlen(z)); break; }
-        if (base.size() != path.size()) fmt = UNKNOWN;             // a compressed name is never followed by a sequence extension here (.in / .out / .R1 / .R2 come first)
-        else if (endsWithNoCase(base, ".fa") || endsWithNoCase(base, ".fasta")) fmt = FASTA;
-        else if (endsWithNoCase(base, ".fq") || endsWithNoCase(base, ".fastq")) fmt = FASTQ;
-        else if (endsWithNoCase(base, ".txt")) fmt = RAW;
+        if (base.size() != path.size()) return UNKNOWN;            // a compressed name is never followed by a sequence extension here (.in / .out / .R1 / .R2 come first)
+        if (endsWithNoCase(base, ".fa") || endsWithNoCase(base, ".fasta")) return FASTA;
+        if (endsWithNoCase(base, ".fq") || endsWithNoCase(base, ".fastq")) return FASTQ;
+        if (endsWithNoCase(base, ".txt")) return RAW;
+        return UNKNOWN;
+    }
+    // what opening `path` would throw, for a rank that opens nothing (--gpus: only rank 0 creates the files)
+    static void checkName(const string& path) {
+        if (formatOf(path) == UNKNOWN) throw std::runtime_error("Unknown file extension of " + path + ": iostream error");
+    }
+    explicit SeqWriter(const string& path) : os(path.c_str(), std::ios::binary | std::ios::trunc), fmt(formatOf(path)) {
+        if (!os) throw std::runtime_error("Could not open file " + path + ": iostream error");
         if (fmt == UNKNOWN) { os.close(); throw std::runtime_error("Unknown file extension of " + path + ": iostream error"); }
     }
     void write(const string& name, const string& seq, const string& qual) {
@@ -92,7 +103,7 @@ private:
     }
     std::ofstream os;
     string buf;
-    enum { FASTA, FASTQ, RAW, UNKNOWN } fmt = UNKNOWN;
+    Format fmt = UNKNOWN;
 };
 
 uint64_t nbKmers(size_t len, uint16_t k) { return len >= k ? (uint64_t)(len - k + 1) : 0; }   // getProfile's nbCounts, 0 when <= 0
@@ -211,21 +222,37 @@ void FilterSeq::processSeqFile() {                                              
     SeqRecordReader reader(seq_file_1);
     std::unique_ptr<SeqRecordReader> reader2;
     if (isPaired()) reader2.reset(new SeqRecordReader(seq_file_2));
+    // --gpus N: the hash lies on the ranks by owner, every rank reads the sequence file(s) and cuts the same batches, and the hits reach
+    // rank 0 through one collective per batch (katgpu_table_seq_hits_gathered_host).  Rank 0 alone opens the outputs, draws the random
+    // numbers, decides and writes; the other ranks create nothing -- but look at the output names as rank 0 does when it opens them, and one
+    // all-reduce in front of the batches tells every rank whether any was refused: all ranks end there with the plain run's error.
+    const bool dist = Engine::dist(), speak = !dist || Engine::speaker();
     std::ofstream stats;
-    if (doStats) {
+    if (doStats && speak) {
         stats.open((output_prefix + ".stats").c_str());
         stats << "index\tnb_bases\tnb_kmers\tnb_hits\tratio" << endl;
     }
     const string ext = pathExtension(seq_file_1);
     const string r1 = isPaired() ? ".R1" : "";
-    std::unique_ptr<SeqWriter> inW(new SeqWriter(output_prefix + ".in" + r1 + ext)), outW, inW2, outW2;
-    if (separate) outW.reset(new SeqWriter(output_prefix + ".out" + r1 + ext));
-    if (isPaired()) {
-        inW2.reset(new SeqWriter(output_prefix + ".in.R2" + ext));
-        if (separate) outW2.reset(new SeqWriter(output_prefix + ".out.R2" + ext));
+    std::unique_ptr<SeqWriter> inW, outW, inW2, outW2;
+    auto open = [&](std::unique_ptr<SeqWriter>& w, const string& path) { if (speak) w.reset(new SeqWriter(path)); else SeqWriter::checkName(path); };
+    std::exception_ptr refused;
+    try {
+        open(inW, output_prefix + ".in" + r1 + ext);
+        if (separate) open(outW, output_prefix + ".out" + r1 + ext);
+        if (isPaired()) {
+            open(inW2, output_prefix + ".in.R2" + ext);
+            if (separate) open(outW2, output_prefix + ".out.R2" + ext);
+        }
+    } catch (...) { refused = std::current_exception(); }
+    if (dist) {                                              // all go on, or none does: rank 0 has left what the plain run leaves by the time the others end
+        uint64_t n_refused = refused ? 1 : 0;
+        Engine::allreduce(&n_refused, 1);
+        if (n_refused && !refused) refused = std::make_exception_ptr(std::runtime_error("Could not open the output files of rank 0: iostream error"));
     }
+    if (refused) std::rethrow_exception(refused);
     std::random_device rd;
-    std::mt19937 gen(rd());
+    std::mt19937 gen(speak ? rd() : 0u);
     std::uniform_real_distribution<> urd;
     const uint16_t k = input.merLen;
     const int per = isPaired() ? 2 : 1;                      // device records per entry: R1 (and R2)
@@ -251,8 +278,9 @@ void FilterSeq::processSeqFile() {                                              
         joined.clear(); joined.reserve(bases);
         starts.resize(nr); lens.resize(nr); hits.assign(nr, 0);
         for (size_t i = 0; i < nr; i++) { starts[i] = joined.size(); lens[i] = seqs[i].size(); joined += seqs[i]; }
-        Engine::check(katgpu_table_seq_hits_host(input.hash, joined.data(), joined.size(), starts.data(), lens.data(), nr, input.canonical ? 1 : 0, hits.data()));
-        for (size_t e = 0; e < n; e++) {
+        if (dist) Engine::seqHitsGathered(input.hash, joined.data(), joined.size(), starts.data(), lens.data(), nr, input.canonical, speak ? hits.data() : nullptr);
+        else Engine::check(katgpu_table_seq_hits_host(input.hash, joined.data(), joined.size(), starts.data(), lens.data(), nr, input.canonical ? 1 : 0, hits.data()));
+        for (size_t e = 0; speak && e < n; e++) {
             const double val = urd(gen);                                                       // drawn for every entry, in input order
             uint64_t nbFound = 0, nb = 0, len = 0;
             for (int q = 0; q < per; q++) { nbFound += hits[e * per + q]; nb += nbKmers(seqs[e * per + q].size(), k); len += seqs[e * per + q].size(); }
@@ -279,7 +307,7 @@ void FilterSeq::processSeqFile() {                                              
     }
     if (isPaired() && !reader2->atEnd()) throw FilterSeqException("Second sequence file appears to be longer than the first.");
     inW.reset(); outW.reset(); inW2.reset(); outW2.reset();
-    if (doStats) stats.close();
+    if (stats.is_open()) stats.close();
     cout << "Finished filtering.";
     cout.flush();
 }

@@ -88,6 +88,11 @@ void Engine::profileGathered(katgpu_table* t, const char* bases, size_t n, bool 
     finishPending();
     check(katgpu_table_profile_gathered_host(comm(), t, bases, n, canonicalise ? 1 : 0, counts));
 }
+void Engine::seqHitsGathered(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec,
+                             bool canonicalise, uint64_t* hits) {
+    finishPending();
+    check(katgpu_table_seq_hits_gathered_host(comm(), t, bases, n, rec_start, rec_len, n_rec, canonicalise ? 1 : 0, hits));
+}
 
 void Engine::shutdown() {
     if (g_comm) { katgpu_comm_free(g_comm); g_comm = nullptr; }

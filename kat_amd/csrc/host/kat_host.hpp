@@ -81,6 +81,9 @@ public:
     static void barrier();                          // idem
     // the per-position counts of `bases` against a table that lies on the ranks by owner, on rank 0 (katgpu_table_profile_gathered_host); idem
     static void profileGathered(katgpu_table* t, const char* bases, size_t n, bool canonicalise, uint64_t* counts);
+    // the per-record hits of the records of `bases` against such a table, on rank 0 (katgpu_table_seq_hits_gathered_host); idem
+    static void seqHitsGathered(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec,
+                                bool canonicalise, uint64_t* hits);
 private:
     static int rank_, world_;
     static bool dist_;

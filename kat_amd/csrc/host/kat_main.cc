@@ -5,6 +5,7 @@
 #include <csignal>
 #include <cstdlib>
 #include <cstring>
+#include <strings.h>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -62,7 +63,7 @@ int main(int argc, char* argv[]) {
     if (argc < 2 || !strcmp(argv[1], "--help") || !strcmp(argv[1], "-h")) { usage(); return 1; }
     const std::string mode = argv[1];
     // the katgpu-only switch, valid in every counting mode:
-    //   --gpus N                    N processes, one per GPU (hist, gcp, comp, sect, cold)
+    //   --gpus N                    N processes, one per GPU (hist, gcp, comp, sect, cold, filter seq)
     int kept = 2, gpus = 0;
     bool gpus_given = false;
     for (int i = 2; i < argc; ++i) {
@@ -73,7 +74,17 @@ int main(int argc, char* argv[]) {
     argc = kept;
     if (gpus_given && (gpus < 1 || gpus > 256)) { std::cerr << "Error: Parsing Command Line: --gpus takes 1 .. 256" << std::endl; return 1; }
     if (!gpus_given) return guarded(mode, argc - 1, argv + 1);
-    if (mode != "hist" && mode != "gcp" && mode != "comp" && mode != "sect" && mode != "cold") { std::cerr << "Error: Parsing Command Line: --gpus applies to hist, gcp and comp, sect and cold" << std::endl; return 1; }
+    // filter: `filter seq` only.  The sub-mode is the first positional after `filter`, found as Filter::main finds it; with none,
+    // Filter::main prints its usage.  (`filter kmer` across ranks is another protocol: katgpu_table_filter per rank, its six counters
+    // summed, katgpu_jf_dump_gathered.)
+    bool filter_seq = false;
+    if (mode == "filter") {
+        int at = 2;
+        while (at < argc && (!strcmp(argv[at], "-v") || !strcmp(argv[at], "--verbose") || !strcmp(argv[at], "--help"))) ++at;
+        if (at >= argc) return guarded(mode, argc - 1, argv + 1);
+        filter_seq = !strcasecmp(argv[at], "seq");
+    }
+    if (mode != "hist" && mode != "gcp" && mode != "comp" && mode != "sect" && mode != "cold" && !filter_seq) { std::cerr << "Error: Parsing Command Line: --gpus applies to hist, gcp and comp, sect, cold and filter seq" << std::endl; return 1; }
     // A peer that is alive but wedged (its heartbeat thread still ticking) would hang the run for ever: no single wait inside a collective
     // lasts longer than this (two hours -- a rank dealt a whole-genome .gz reaches the exchange many minutes after the others), unless the
     // caller says otherwise.  The library reads it at its first wait.

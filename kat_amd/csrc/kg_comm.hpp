@@ -1,5 +1,5 @@
 // kg_comm.hpp -- the communicator as the units that speak through it see it: kg_comm.hip (the transports, liveness, the small
-// collectives), kg_comm_exchange.hip (the exchange protocol), and the two gathered paths, kg_jf_device.hip and kg_query.hip.
+// collectives), kg_comm_exchange.hip (the exchange protocol), and the gathered paths, kg_jf_device.hip and kg_query.hip.
 // Nobody else includes it: the rest of the library and its callers know katgpu_comm as the opaque handle of include/katgpu.h.
 #pragma once
 #include "kg_host.hpp"

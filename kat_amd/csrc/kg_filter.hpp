@@ -3,6 +3,7 @@
 //  K9  k_filter<SEP, W>        one pass over every slot of a table: count x GC box -> keep / drop tables  (replaces FilterKmer::filterSlice)
 //  K10 k_seq_hits              per-record number of windows found in a table                              (replaces FilterSeq::getProfile + the
 //                                                                                                          nbFound loop of processSeq)
+//      k_seq_hits_owned        the same over the windows whose k-mer this rank owns; k_hits_sum adds the ranks' arrays on rank 0
 // K9 rebuilds rather than clears: probing is linear inside a region (kg_device.hpp: Probe), so clearing a slot in place would cut the
 // probe chain of every k-mer placed after it.  The keep / drop tables are made with the source's region grid, so a k-mer lands in the
 // region of the same index it came from (a subset of a region's k-mers never probes further than the full set did) and the blocks that
@@ -97,10 +98,11 @@ __device__ __forceinline__ uint64_t hits_lower_bound(const uint64_t* __restrict_
     return lo;
 }
 
-template <bool ALIGNED, bool W>
-__global__ void __launch_bounds__(COUNT_BLOCK)
-k_seq_hits(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
-           const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len, uint64_t n_rec, unsigned long long* __restrict__ hits) {
+// One body for K10 and its owned form (OWNED: `rank` and `n_ranks` are read, and a window whose k-mer another rank owns is passed over).
+template <bool ALIGNED, bool W, bool OWNED>
+__device__ __forceinline__ void seq_hits_body(const DevTable& t, uint32_t n_ovf, int canonicalise, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
+                                              const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len, uint64_t n_rec,
+                                              unsigned long long* __restrict__ hits, uint32_t rank, uint32_t n_ranks) {
     constexpr int CS = Chunk<W>::STARTS;
     __shared__ typename Chunk<W>::Tile s;
     __shared__ uint32_t s_hits[HITS_LDS_RECS];
@@ -149,8 +151,12 @@ k_seq_hits(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restri
                 while (pos >= ns) { ++r; rs = ns; re = rs + rec_len[r]; ns = (uint64_t)(r + 1) < r_hi ? rec_start[r + 1] : ~0ULL; }
                 if (r >= (int64_t)r_lo && pos >= rs && pos + k <= re && lw.valid()) {
                     auto key = lw.fwd();
-                    if (canonicalise) key = kmer_canonical(key, k);
-                    if (table_get(t, key, n_ovf)) { if (r != cur) { flush(); cur = r; run = 0; } ++run; }
+                    bool mine = true;
+                    if constexpr (OWNED) mine = n_ranks == 1 || owner_of(key, k, n_ranks) == rank;
+                    if (mine) {
+                        if (canonicalise) key = kmer_canonical(key, k);
+                        if (table_get(t, key, n_ovf)) { if (r != cur) { flush(); cur = r; run = 0; } ++run; }
+                    }
                 }
             }
             flush();
@@ -162,6 +168,36 @@ k_seq_hits(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restri
             if (h) { atomicAdd(&hits[r_lo + i], (unsigned long long)h); s_hits[i] = 0; }
         }
         __syncthreads();
+    }
+}
+
+template <bool ALIGNED, bool W>
+__global__ void __launch_bounds__(COUNT_BLOCK)
+k_seq_hits(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
+           const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len, uint64_t n_rec, unsigned long long* __restrict__ hits) {
+    seq_hits_body<ALIGNED, W, false>(t, n_ovf, canonicalise, bases, n, n_chunks, rec_start, rec_len, n_rec, hits, 0, 1);
+}
+
+// K10 across ranks (katgpu_table_seq_hits_gathered_host): after the exchange a k-mer lives on one rank, so every rank walks the same
+// records and looks up the windows whose k-mer it OWNS -- owner_of mixes the canonical form whatever the table's strand mode; the lookup
+// follows `canonicalise` as in K10.  Hits add across owners: a record's hit count is the sum of the ranks' (k_hits_sum, on rank 0).
+// n_ranks == 1: every window is this rank's.
+template <bool ALIGNED, bool W>
+__global__ void __launch_bounds__(COUNT_BLOCK)
+k_seq_hits_owned(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
+                 const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len, uint64_t n_rec, unsigned long long* __restrict__ hits,
+                 uint32_t rank, uint32_t n_ranks) {
+    seq_hits_body<ALIGNED, W, true>(t, n_ovf, canonicalise, bases, n, n_chunks, rec_start, rec_len, n_rec, hits, rank, n_ranks);
+}
+
+// Rank 0 of the same: hits[r] += the n_parts arrays of m words that came from the other ranks, laid behind one another in `part`.
+static __global__ void __launch_bounds__(256)
+k_hits_sum(uint64_t* __restrict__ hits, const uint64_t* __restrict__ part, uint64_t m, uint32_t n_parts) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < m; r += stride) {
+        uint64_t s = hits[r];
+        for (uint32_t p = 0; p < n_parts; ++p) s += part[(uint64_t)p * m + r];
+        hits[r] = s;
     }
 }
 

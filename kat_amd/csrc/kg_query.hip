@@ -1,5 +1,5 @@
 // kg_query.hip -- a sequence or keys against a table, which is left as it is: batch lookups (katgpu_table_get*), per-position profiles
-// (katgpu_table_profile_*; _gathered_host: of a table that lies on several ranks, gathered on rank 0), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*), the per-record coverage statistics
+// (katgpu_table_profile_*; _gathered_host: of a table that lies on several ranks, gathered on rank 0), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*; _gathered_host: summed over the ranks' tables on rank 0), the per-record coverage statistics
 // of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*) the count-range regions of `kat sect -E / -F` (katgpu_table_record_regions_*) and the -counts.cvg text of `kat sect` (katgpu_table_record_cvg_text_*).  The host forms send their input through the device in batches.
 #include "kg_host.hpp"
 #include "kg_comm.hpp"
@@ -12,6 +12,8 @@
 static const bool g_forbid_profile_host = hook_u64("KATGPU_TEST_FORBID_PROFILE_HOST", 0) != 0;   // tests: a driver that should not need per-position counts asks for none
 static const size_t g_profile_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_PROFILE_BATCH", (uint64_t)32 << 20), 1);   // tests: window starts per batch of profile_host
 static const size_t g_hits_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_HITS_BATCH", (uint64_t)64 << 20), 1);        // tests: bases per batch of seq_hits_host
+
+static const size_t g_hits_recs = (size_t)std::min<uint64_t>(std::max<uint64_t>(hook_u64("KATGPU_TEST_HITS_RECS", (uint64_t)1 << 20), 1), (uint64_t)1 << 20);   // tests: records per batch of seq_hits_host and seq_hits_gathered_host
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static uint64_t chunk_starts(bool wide) { return wide ? WIDE_CHUNK_STARTS : CHUNK_STARTS; }   // window starts per chunk of the window kernels
@@ -247,7 +249,7 @@ extern "C" int katgpu_table_seq_hits_host(katgpu_table* t, const char* bases, si
     int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     rc = refresh_counters(t); if (rc) return rc;
-    const size_t SEQ_HITS_RECS = (size_t)1 << 20;
+    const size_t SEQ_HITS_RECS = g_hits_recs;
     DevBuf recs;                                                   // start, length and hits of every record of a batch
     HIPCHK(c, recs.pooled(c, SEQ_HITS_RECS * 3 * sizeof(uint64_t)));
     uint64_t* dr = recs.as<uint64_t>();
@@ -259,6 +261,114 @@ extern "C" int katgpu_table_seq_hits_host(katgpu_table* t, const char* bases, si
         const hipError_t e = hipMemcpyAsync(hits + r0, dr + 2 * SEQ_HITS_RECS, m * 8, hipMemcpyDeviceToHost, c->stream);
         return e == hipSuccess ? KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "seq hits: %s", hipGetErrorString(e));
     });
+}
+
+// ------------------------------------------------------------------ the hits of a table that lies on several ranks ----
+
+static const int64_t g_hits_gather_nomem = hook("KATGPU_TEST_HITS_GATHER_NOMEM") ? atoll(hook("KATGPU_TEST_HITS_GATHER_NOMEM")) : -1;   // tests: this rank reports that it could not allocate
+
+// what the ranks compare of their records: every start and length, in order, folded into one word
+static uint64_t records_checksum(const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec) {
+    uint64_t h = 0x9E3779B97F4A7C15ULL;
+    auto fold = [&](uint64_t x) { h ^= x; h *= 0xFF51AFD7ED558CCDULL; h ^= h >> 32; };
+    for (size_t r = 0; r < n_rec; ++r) { fold(rec_start[r]); fold(rec_len[r]); }
+    return h;
+}
+
+// Collective, after katgpu_exchange_merge: every rank walks the same records in the batches of katgpu_table_seq_hits_host (for_record_batches:
+// at most g_hits_batch bases and g_hits_recs records) and counts, per record, the hits among the windows whose k-mer it owns
+// (k_seq_hits_owned).  Hits add across owners, so what travels is a record's count: the other ranks send the batch's m words to rank 0,
+// which receives them behind one another, adds them to its own (k_hits_sum) and copies the sums to `hits`: 8 bytes per record and
+// rank on the wire, none per window.  The batches are cut from the records, so the ranks first make sure that they hold the same ones.
+// From the pool, per record of a batch: start, length and hits on every rank and world - 1 words of staging on rank 0, beside the
+// batch's bases (for_record_batches' own buffer: a rank that finds no room for it fails inside the batches, where comm_agree_done hears of it).
+extern "C" int katgpu_table_seq_hits_gathered_host(katgpu_comm* comm, katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start,
+                                                   const uint64_t* rec_len, size_t n_rec, int canonicalise, uint64_t* hits) {
+    if (!comm || !t) return KATGPU_ERR_INVALID_ARG;
+    katgpu_ctx* c = t->ctx;
+    const int rank = katgpu_comm_rank(comm), world = katgpu_comm_world(comm);
+    const uint32_t k = t->dv.k;
+    const bool wide = t->dv.keys_b != nullptr;
+    // ---- the same records, one k and usable pointers everywhere, before anything else: all ranks go on, or none does ----
+    {
+        const bool unusable = (n && !bases) || (n_rec && (!rec_start || !rec_len)) || (rank == 0 && n_rec && !hits);
+        const uint64_t mine[5] = {(uint64_t)n, (uint64_t)n_rec, k, unusable ? 0 : records_checksum(rec_start, rec_len, n_rec), (uint64_t)unusable};
+        std::vector<uint64_t> all((size_t)world * 5, 0);
+        const int crc = allgather_u64(comm, mine, 5, all.data());
+        if (crc) return crc;
+        for (int p = 0; p < world; ++p)
+            if (all[(size_t)p * 5 + 4]) return fail(c, KATGPU_ERR_INVALID_ARG, "seq hits gathered: rank %d was given no bases or no records, or rank 0 no room for the hits", p);
+        for (int p = 0; p < world; ++p) {
+            const uint64_t* a = &all[(size_t)p * 5];
+            if (a[0] != all[0] || a[1] != all[1] || a[2] != all[2])
+                return fail(c, KATGPU_ERR_INVALID_ARG, "seq hits gathered: the ranks disagree: rank 0 has %llu bases in %llu records at k = %llu, rank %d %llu in %llu at k = %llu",
+                            (unsigned long long)all[0], (unsigned long long)all[1], (unsigned long long)all[2], p, (unsigned long long)a[0], (unsigned long long)a[1], (unsigned long long)a[2]);
+            if (a[3] != all[3]) return fail(c, KATGPU_ERR_INVALID_ARG, "seq hits gathered: the ranks disagree: rank %d's %llu records are not where rank 0's are", p, (unsigned long long)a[1]);
+        }
+    }
+    if (!n_rec) return KATGPU_OK;
+    int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;      // (the same records everywhere: the same answer)
+    // ---- everything a batch needs: start | length | hits of its records, the other ranks' hits on rank 0 ----
+    const size_t cap = std::min(n_rec, g_hits_recs);               // records per batch
+    DevBuf recs, stage;
+    auto prepare = [&]() -> int {
+        HIPCHK(c, hipSetDevice(c->device));
+        int rc = refresh_counters(t); if (rc) return rc;
+        if (g_hits_gather_nomem == rank || recs.pooled(c, cap * 3 * sizeof(uint64_t)) != hipSuccess ||
+            (rank == 0 && world > 1 && stage.pooled(c, (size_t)(world - 1) * cap * sizeof(uint64_t)) != hipSuccess)) {
+            (void)hipGetLastError();
+            return fail(c, KATGPU_ERR_NOMEM, "seq hits gathered: no device memory for a batch of %zu records", cap);
+        }
+        return KATGPU_OK;
+    };
+    rc = comm_agree_to_start(comm, prepare(), [&](int p, int code) {
+        if (code == KATGPU_ERR_NOMEM) return fail(c, code, "seq hits gathered: rank %d of %d has no device memory for a batch of %zu records", p, world, cap);
+        return fail(c, code, "seq hits gathered: rank %d could not read its table", p);
+    });
+    if (rc) return rc;
+    uint64_t* dr = recs.as<uint64_t>();
+    uint64_t* d_hits = dr + 2 * cap;
+
+    // ---- the batches.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end (comm_agree_done) ----
+    uint64_t n_batches = 0, records = 0;
+    size_t no_room = 0;
+    rc = for_record_batches(c, bases, n, rec_start, rec_len, n_rec, g_hits_batch, cap, dr, dr + cap, "seq hits gathered", &no_room,
+                            [](size_t, bool) { return true; },
+                            [&](const uint8_t* db, size_t nb, const uint64_t* ds, const uint64_t* dl, size_t m, size_t r0) -> int {
+        HIPCHK(c, hipMemsetAsync(d_hits, 0, m * sizeof(uint64_t), c->stream));
+        if (nb >= k) {
+            const uint64_t n_out = nb - k + 1;
+            ScopedTimer tm(c, KATGPU_K_PROFILE, n_out);
+            launch_aligned_wide(c, aligned16(db), wide, n_out, chunk_starts(wide), [&](auto A, auto W, dim3 grid, uint64_t n_chunks) {
+                hipLaunchKernelGGL((k_seq_hits_owned<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, t->dev(), t->n_ovf, canonicalise, db, (uint64_t)nb, n_chunks, ds, dl, (uint64_t)m, (unsigned long long*)d_hits, (uint32_t)rank, (uint32_t)world);
+            });
+            HIPCHK(c, hipGetLastError());
+        }
+        if (world > 1) {
+            HIPCHK(c, hipStreamSynchronize(c->stream));             // (the hits are whole before they travel)
+            std::vector<CommMsg> sends, recvs;
+            if (rank != 0) sends.push_back({0, d_hits, m * sizeof(uint64_t)});
+            else for (int p = 1; p < world; ++p) recvs.push_back({p, stage.as<uint64_t>() + (size_t)(p - 1) * m, m * sizeof(uint64_t)});
+            const int trc = transfer_sync(comm, sends, recvs);
+            if (trc) return trc;
+        }
+        ++n_batches; records += m;
+        if (rank != 0) return KATGPU_OK;
+        if (world > 1) {
+            ScopedTimer tm(c, KATGPU_K_PROFILE, 0);
+            hipLaunchKernelGGL(k_hits_sum, dim3((unsigned)grid_for(c, m, 256, 8)), dim3(256), 0, c->stream, d_hits, stage.as<uint64_t>(), (uint64_t)m, (uint32_t)(world - 1));
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipMemcpyAsync(hits + r0, d_hits, m * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        return KATGPU_OK;
+    });
+    if (no_room) rc = fail(c, KATGPU_ERR_NOMEM, "seq hits gathered: no %zu bytes of device memory for a batch of bases", no_room);
+    rc = comm_agree_done(comm, rc, "seq hits gathered: rank %d failed");
+    if (rc) return rc;
+    if (rank == 0 && g_timing)
+        fprintf(stderr, "katgpu_timing {\"phase\": \"seq_hits_gathered\", \"batches\": %llu, \"ranks\": %d, \"records\": %llu, \"wire_bytes\": %llu}\n",
+                (unsigned long long)n_batches, world, (unsigned long long)records, (unsigned long long)(8 * records * (uint64_t)(world - 1)));
+    return KATGPU_OK;
 }
 
 // ------------------------------------------------------------------ per-record coverage statistics (kat sect -n, kat cold) ----
