@@ -27,13 +27,16 @@ extern "C" int katgpu_hist(katgpu_table* t, uint64_t base, uint64_t ceil_, uint6
     unsigned long long* d = buf.as<unsigned long long>();
     hipMemsetAsync(d, 0, nb * 8, c->stream);
     const uint32_t lds_bins = (uint32_t)std::min<uint64_t>(nb, 16384);          // 64 KB of u32 -> two blocks per CU
+    const int grid = grid_for(c, t->dev().cap / 4, SCAN_BLOCK, 2);
+    if (g_trace) fprintf(stderr, "[katgpu] reducer form: hist %s lds_bins=%u nb=%llu grid=%d n_ovf=%u\n", t->dev().keys_b ? "wide" : t->dev().cbits ? "pk" : "kv12", lds_bins,
+                         (unsigned long long)nb, grid, t->n_ovf);
     {
         ScopedTimer tm(c, KATGPU_K_HIST, t->dev().cap);
         if (t->dev().cbits)
-            hipLaunchKernelGGL(k_hist<true>, dim3(grid_for(c, t->dev().cap / 4, SCAN_BLOCK, 2)), dim3(SCAN_BLOCK), lds_bins * sizeof(uint32_t), c->stream,
+            hipLaunchKernelGGL(k_hist<true>, dim3(grid), dim3(SCAN_BLOCK), lds_bins * sizeof(uint32_t), c->stream,
                                t->dev(), t->n_ovf, base, ceil_, inc, (uint64_t)nb, d, lds_bins);
         else
-            hipLaunchKernelGGL(k_hist<false>, dim3(grid_for(c, t->dev().cap / 4, SCAN_BLOCK, 2)), dim3(SCAN_BLOCK), lds_bins * sizeof(uint32_t), c->stream,
+            hipLaunchKernelGGL(k_hist<false>, dim3(grid), dim3(SCAN_BLOCK), lds_bins * sizeof(uint32_t), c->stream,
                                t->dev(), t->n_ovf, base, ceil_, inc, (uint64_t)nb, d, lds_bins);
     }
     hipMemcpyAsync(out, d, nb * 8, hipMemcpyDeviceToHost, c->stream);
@@ -54,16 +57,21 @@ extern "C" int katgpu_gcp(katgpu_table* t, double cvg_scale, uint32_t cvg_bins, 
     const size_t lds = cells * sizeof(uint32_t);
     const uint32_t use_lds = lds <= 150 * 1024 ? (g_comp_plain_inc ? 2 : 1) : 0;   // 160 KB LDS per CU
     const int per_cu = use_lds && lds > 75 * 1024 ? 1 : 2;
+    const bool wide = t->dev().keys_b != nullptr, pk = !wide && t->dev().cbits != 0;
+    // packed: a wave per region (kg_kernels.hpp: k_gcp_pk); the flat scans: four slots per lane and round
+    const uint32_t grid = pk ? std::min<uint32_t>((t->dev().n_regions + SCAN_BLOCK / 64 - 1) / (SCAN_BLOCK / 64), (uint32_t)c->n_cu * per_cu)
+                             : (uint32_t)grid_for(c, t->dev().cap / 4, SCAN_BLOCK, per_cu);
+    if (g_trace) fprintf(stderr, "[katgpu] reducer form: gcp %s use_lds=%u per_cu=%d lds=%zu grid=%u n_ovf=%u cbits=%u\n", wide ? "wide" : pk ? "pk" : "flat", use_lds, per_cu, lds, grid,
+                         t->n_ovf, t->dev().cbits);
 #define KG_GCP(W, PK) do { \
         if (use_lds && lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_gcp<W, PK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
         ScopedTimer tm(c, KATGPU_K_GCP, t->dev().cap); \
-        hipLaunchKernelGGL((k_gcp<W, PK>), dim3(grid_for(c, t->dev().cap / 4, SCAN_BLOCK, per_cu)), dim3(SCAN_BLOCK), use_lds ? lds : 0, c->stream, t->dev(), t->n_ovf, cvg_scale, cvg_bins, d, use_lds); } while (0)
-    if (t->dev().keys_b) KG_GCP(true, false);
-    else if (t->dev().cbits) {                                  // packed: a wave per region (kg_kernels.hpp: k_gcp_pk)
+        hipLaunchKernelGGL((k_gcp<W, PK>), dim3(grid), dim3(SCAN_BLOCK), use_lds ? lds : 0, c->stream, t->dev(), t->n_ovf, cvg_scale, cvg_bins, d, use_lds); } while (0)
+    if (wide) KG_GCP(true, false);
+    else if (pk) {
         if (use_lds && lds > 64 * 1024) HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_gcp_pk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         ScopedTimer tm(c, KATGPU_K_GCP, t->dev().cap);
-        const uint32_t want = (t->dev().n_regions + SCAN_BLOCK / 64 - 1) / (SCAN_BLOCK / 64);
-        hipLaunchKernelGGL(k_gcp_pk, dim3(std::min<uint32_t>(want, (uint32_t)c->n_cu * per_cu)), dim3(SCAN_BLOCK), use_lds ? lds : 0, c->stream, t->dev(), t->n_ovf, cvg_scale, cvg_bins, d, use_lds);
+        hipLaunchKernelGGL(k_gcp_pk, dim3(grid), dim3(SCAN_BLOCK), use_lds ? lds : 0, c->stream, t->dev(), t->n_ovf, cvg_scale, cvg_bins, d, use_lds);
     }
     else KG_GCP(false, false);
 #undef KG_GCP
