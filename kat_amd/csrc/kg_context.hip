@@ -3,6 +3,7 @@
 // synthetic workload).
 #include "kg_host.hpp"
 #include "kg_kernels.hpp"
+#include "kg_synth_kernels.hpp"
 
 extern "C" const char* katgpu_version(void) { return "katgpu 0.1 (gfx950)"; }
 

@@ -38,6 +38,11 @@ constexpr int CTR_FULL = 66;       // != 0: an insert ran out of probes / carry 
 constexpr int CTR_SCRATCH = 67;    // cursors / scratch for export & partition (8 words)
 constexpr int CTR_WORDS = 80;
 
+// native vectors for the 16-byte accesses of more than one header (kg_partition.hpp has its own u32x4 / u32x2 family)
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));               // two slots' key words, or a wide k-mer {a, b}
+typedef uint32_t u32x4s __attribute__((ext_vector_type(4)));              // four KV12 counts, or two packed slots as dwords
+typedef uint64_t u64x2a8 __attribute__((ext_vector_type(2), aligned(8))); // two slots in LDS from an address that is only 8-byte aligned
+
 struct DevTable {
     uint64_t* keys;        // KV12: the k-mer (EMPTY = free).  P8: (remainder << cbits) | count (0 = free)
     uint64_t* keys_b;      // wide tables only (k > 32, see "wide keys" below): the second key word per slot; nullptr otherwise

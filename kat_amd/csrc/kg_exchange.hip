@@ -2,7 +2,8 @@
 // in-place merge of received runs region by region in LDS, and the direct paths beside them (kg_comm.hip drives these over RCCL;
 // kat_amd/dist.py drives them over torch.distributed).
 #include "kg_host.hpp"
-#include "kg_kernels.hpp"
+#include "kg_exchange_kernels.hpp"
+#include "kg_rows_scan.hpp"
 
 // ------------------------------------------------------------------ region-ordered exchange -----------
 

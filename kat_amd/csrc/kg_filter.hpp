@@ -3,7 +3,9 @@
 //  K9  k_filter<SEP, W>        one pass over every slot of a table: count x GC box -> keep / drop tables  (replaces FilterKmer::filterSlice)
 //  K10 k_seq_hits              per-record number of windows found in a table                              (replaces FilterSeq::getProfile + the
 //                                                                                                          nbFound loop of processSeq)
-//      k_seq_hits_owned        the same over the windows whose k-mer this rank owns; k_hits_sum adds the ranks' arrays on rank 0
+//      k_seq_hits_owned        the same over the windows whose k-mer this rank owns; k_hits_sum (kg_query_kernels.hpp) adds the ranks' arrays on rank 0
+// Both units that launch these include this header (kg_records.hip: K9; kg_query.hip: K10), so it holds templates only: a kernel that is
+// no template would be compiled into the unit that does not launch it.  From kg_kernels.hpp it takes Chunk and COUNT_BLOCK.
 // K9 rebuilds rather than clears: probing is linear inside a region (kg_device.hpp: Probe), so clearing a slot in place would cut the
 // probe chain of every k-mer placed after it.  The keep / drop tables are made with the source's region grid, so a k-mer lands in the
 // region of the same index it came from (a subset of a region's k-mers never probes further than the full set did) and the blocks that
@@ -188,17 +190,6 @@ k_seq_hits_owned(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __
                  const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len, uint64_t n_rec, unsigned long long* __restrict__ hits,
                  uint32_t rank, uint32_t n_ranks) {
     seq_hits_body<ALIGNED, W, true>(t, n_ovf, canonicalise, bases, n, n_chunks, rec_start, rec_len, n_rec, hits, rank, n_ranks);
-}
-
-// Rank 0 of the same: hits[r] += the n_parts arrays of m words that came from the other ranks, laid behind one another in `part`.
-static __global__ void __launch_bounds__(256)
-k_hits_sum(uint64_t* __restrict__ hits, const uint64_t* __restrict__ part, uint64_t m, uint32_t n_parts) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < m; r += stride) {
-        uint64_t s = hits[r];
-        for (uint32_t p = 0; p < n_parts; ++p) s += part[(uint64_t)p * m + r];
-        hits[r] = s;
-    }
 }
 
 }  // namespace kg

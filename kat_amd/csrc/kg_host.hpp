@@ -11,6 +11,12 @@
 //   kg_comm.hip      the communicator: RCCL or /dev/shm transports, liveness, small collectives, all-or-none agreements (katgpu_comm_*; kg_comm.hpp)
 //   kg_comm_exchange.hip  the exchange itself, above the communicator (katgpu_exchange_*)
 //   kg_reduce.hip    hist / gcp / comp
+// A unit's kernels are in the headers only it includes, or in the unit itself: kg_context.hip kg_synth_kernels.hpp; kg_table.hip its own
+// (k_regrow, k_total); kg_query.hip kg_query_kernels.hpp, kg_filter.hpp (K10), kg_record_stats.hpp, kg_record_regions.hpp, kg_cvg_text.hpp;
+// kg_records.hip kg_record_kernels.hpp, kg_filter.hpp (K9); kg_jf_device.hip kg_jf_records.hpp, kg_jf_load.hpp; kg_count.hip its own
+// (k_sweep), kg_partition.hpp and what that includes, kg_partition_wide.hpp; kg_scan.hip kg_scan.hpp; kg_exchange.hip kg_exchange_kernels.hpp;
+// kg_reduce.hip kg_reduce_kernels.hpp.  Shared: kg_kernels.hpp (the chunk geometry and the direct counter k_count) and kg_rows_scan.hpp
+// (kg_scan.hip, kg_exchange.hip).  tests/test_kernel_units.py holds every unit to it.
 // gfx950 only; there is no CPU path in this library.
 #pragma once
 #include "../../include/katgpu.h"
@@ -211,7 +217,7 @@ static const bool g_testing = getenv("KATGPU_TESTING") != nullptr;
 inline const char* hook(const char* name) { return g_testing ? getenv(name) : nullptr; }
 inline uint64_t hook_u64(const char* name, uint64_t dflt) { const char* v = hook(name); return v ? strtoull(v, nullptr, 10) : dflt; }
 
-constexpr int MAX_EXCHANGE_PARTS_HOST = 256;        // ranks of an exchange (kg_kernels.hpp: MAX_EXCHANGE_PARTS)
+constexpr int MAX_EXCHANGE_PARTS_HOST = 256;        // ranks of an exchange (kg_exchange_kernels.hpp: MAX_EXCHANGE_PARTS)
 // table geometry limits
 constexpr uint32_t AP2_MAX_SLOTS = 10240;           // the apply kernels: a region of at most this many slots (120 KB of KV12 region + 36 KB of queues; 80 KB packed)
 constexpr int AP2_QCAP_BIG = 192;                   // KV12 apply: queue entries per wave for regions beyond 8192 slots

@@ -4,6 +4,7 @@
 #include "kg_host.hpp"
 #include "kg_comm.hpp"
 #include "kg_kernels.hpp"
+#include "kg_query_kernels.hpp"
 #include "kg_filter.hpp"
 #include "kg_record_stats.hpp"
 #include "kg_record_regions.hpp"

@@ -2,7 +2,7 @@
 // one body for one-word keys and for the two-word keys of the `_wide` entry points), and the k-mer filter of `kat filter kmer`, which
 // routes a table's records into one or two new tables.
 #include "kg_host.hpp"
-#include "kg_kernels.hpp"
+#include "kg_record_kernels.hpp"
 #include "kg_filter.hpp"
 
 // ------------------------------------------------------------------ partition / export / merge -------

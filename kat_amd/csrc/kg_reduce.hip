@@ -1,6 +1,6 @@
 // kg_reduce.hip -- the reducers: katgpu_hist / katgpu_gcp / katgpu_comp / katgpu_comp3 (Histogram::bin, Gcp::analyse, Comp::compare).
 #include "kg_host.hpp"
-#include "kg_kernels.hpp"
+#include "kg_reduce_kernels.hpp"
 
 // ------------------------------------------------------------------ reducers --------------------------
 
@@ -58,7 +58,7 @@ extern "C" int katgpu_gcp(katgpu_table* t, double cvg_scale, uint32_t cvg_bins, 
     const uint32_t use_lds = lds <= 150 * 1024 ? (g_comp_plain_inc ? 2 : 1) : 0;   // 160 KB LDS per CU
     const int per_cu = use_lds && lds > 75 * 1024 ? 1 : 2;
     const bool wide = t->dev().keys_b != nullptr, pk = !wide && t->dev().cbits != 0;
-    // packed: a wave per region (kg_kernels.hpp: k_gcp_pk); the flat scans: four slots per lane and round
+    // packed: a wave per region (kg_reduce_kernels.hpp: k_gcp_pk); the flat scans: four slots per lane and round
     const uint32_t grid = pk ? std::min<uint32_t>((t->dev().n_regions + SCAN_BLOCK / 64 - 1) / (SCAN_BLOCK / 64), (uint32_t)c->n_cu * per_cu)
                              : (uint32_t)grid_for(c, t->dev().cap / 4, SCAN_BLOCK, per_cu);
     if (g_trace) fprintf(stderr, "[katgpu] reducer form: gcp %s use_lds=%u per_cu=%d lds=%zu grid=%u n_ovf=%u cbits=%u\n", wide ? "wide" : pk ? "pk" : "flat", use_lds, per_cu, lds, grid,
@@ -152,7 +152,7 @@ extern "C" int katgpu_comp(katgpu_table* t1, katgpu_table* t2, int canon1, int c
         ScopedTimer tm(c, KATGPU_K_COMP_PASS1, t1->dev().cap + t2->dev().cap);
         const uint32_t grid = std::min<uint32_t>(t1->dev().n_regions, (uint32_t)c->n_cu);
         // the streamed region in registers, 16-byte pairs of slots per lane (4 or 5: regions of up to 8192 / 10240 slots); 64-bit counts only
-        // where a side table holds some (kg_kernels.hpp: k_comp_fused)
+        // where a side table holds some (kg_reduce_kernels.hpp: k_comp_fused)
         const bool five = s_str > 4 * FUSED_BLOCK * 2, ovf = t1->n_ovf != 0 || t2->n_ovf != 0;
 #define KG_FUSED(SWAP, JP, OVF) do { \
             HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(k_comp_fused<SWAP, JP, OVF>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256)); \

@@ -25,6 +25,7 @@
 #include "kg_host.hpp"
 #include "kg_ingest.hpp"
 #include "kg_scan.hpp"
+#include "kg_rows_scan.hpp"
 
 #include <atomic>
 #include <condition_variable>

@@ -16,8 +16,10 @@
 //   k_nl_write   NL[j] = position of the j-th newline
 //   k_line_len   per line: what it contributes to the output (and the structure checks)   -> scan -> out_off[j]
 //   k_emit       per byte: its place in the output, from its line
+// (the two scans between them are k_rows_scan, kg_rows_scan.hpp, which kg_scan.hip includes beside this header)
 #pragma once
-#include "kg_kernels.hpp"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace kg {
 

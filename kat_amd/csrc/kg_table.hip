@@ -1,7 +1,6 @@
 // kg_table.hip -- the HBM-resident count table behind katgpu_table and its life cycle: geometry and layout choice, allocation, regrow
 // (hash_counter::double_size), the counters and statistics, and the room made for records that are added in bulk (add_in_rooms).
 #include "kg_host.hpp"
-#include "kg_kernels.hpp"
 
 static const uint32_t g_region_slots = (uint32_t)hook_u64("KATGPU_TEST_REGION_SLOTS", REGION_SLOTS);
 static const bool g_no_packed = hook("KATGPU_NO_PACKED") != nullptr;   // tests / A-B: every table in the KV12 layout
@@ -154,6 +153,22 @@ int refresh_counters(katgpu_table* t) {
     return KATGPU_OK;
 }
 
+namespace kg {
+// K2: re-insert a table's (key,count) records into a larger one (hash_counter::double_size, hash_counter.hpp:204-244; k_merge,
+// kg_record_kernels.hpp, does the same with a record list).  One body for one-word and wide k-mers (W).
+template <bool W>
+__global__ void __launch_bounds__(256)
+k_regrow(DevTable dst, DevTable src, uint32_t src_n_ovf) {
+    uint32_t new_distinct = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < src.cap; i += stride) {
+        const SlotRec<W> s = slot_rec<W>(src, i, src_n_ovf);
+        if (s.occ) table_add(dst, s.key, s.total, new_distinct);
+    }
+    flush_distinct(dst, new_distinct);
+}
+}  // namespace kg
+
 // hash_counter::double_size (deps/jellyfish-2.2.0/include/jellyfish/hash_counter.hpp:204-244): allocate a larger array,
 // re-insert every (key,count), swap.  Here one grid-stride kernel instead of a barrier-synchronised thread team.
 int regrow(katgpu_table* t, uint64_t new_cap) {
@@ -224,6 +239,21 @@ int add_in_rooms(katgpu_table* t, size_t n, uint64_t* unseen, const std::functio
     }
     return KATGPU_OK;
 }
+
+namespace kg {
+// Σ counts (table_stats "total")
+static __global__ void __launch_bounds__(256)
+k_total(DevTable t, uint32_t n_ovf, uint64_t* out) {
+    uint64_t s = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < t.cap; i += stride) {
+        const uint64_t w = t.keys[i];
+        if (t.cbits ? w != 0 : w != EMPTY) s += slot_total(t, i, w, t.cbits ? pk_count(w, t.cbits) : (uint64_t)t.counts[i], n_ovf);
+    }
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    if ((threadIdx.x & 63) == 0 && s) atomicAdd((unsigned long long*)out, (unsigned long long)s);
+}
+}  // namespace kg
 
 extern "C" int katgpu_table_stats(katgpu_table* t, uint64_t* distinct, uint64_t* total, uint64_t* capacity) {
     if (!t) return KATGPU_ERR_INVALID_ARG;

@@ -1,7 +1,7 @@
 """Synthetic workload of BASELINE.json's configs, host (numpy) edition.
 
 Counter-based SplitMix64 so any shard can be produced independently; bit-identical to the device generator
-(kat_amd/csrc/kg_kernels.hpp: k_synth_genome / k_synth_reads), which bench.py uses at full size.  This module is used
+(kat_amd/csrc/kg_synth_kernels.hpp: k_synth_genome / k_synth_reads), which bench.py uses at full size.  This module is used
 at parity scale: it writes the FASTA/FASTQ files the file-level tests feed to both the HIP engine and the oracle.
 
   genome : n i.i.d. uniform bases

@@ -1,4 +1,4 @@
-"""k > 32 on the device ("wide" tables: a k-mer in two 63-bit words, kat_amd/csrc/kg_device.hpp; the kernels are kg_kernels.hpp's, W = true) against the wide
+"""k > 32 on the device ("wide" tables: a k-mer in two 63-bit words, kat_amd/csrc/kg_device.hpp; the kernels are those of kg_kernels.hpp, kg_table.hip, kg_record_kernels.hpp, kg_query_kernels.hpp and kg_reduce_kernels.hpp, W = true) against the wide
 oracle (oracle/koracle_wide.c, itself checked against the reference's parser + multi-word mer_dna), bit-exact, through the C ABI."""
 import os
 

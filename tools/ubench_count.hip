@@ -1,6 +1,7 @@
 // ubench_count.hip -- where does k_count's time go?  Variants of the insert step over the same extraction front end.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I kat_amd/csrc tools/ubench_count.hip -o /tmp/ubench_count
 #include "kg_kernels.hpp"
+#include "kg_synth_kernels.hpp"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
