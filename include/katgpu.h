@@ -260,6 +260,31 @@ int katgpu_table_record_cvg_text_host(katgpu_table* t, const char* bases, size_t
 int katgpu_table_record_cvg_text_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
                                         const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, uint8_t* dev_text, size_t cap,
                                         uint64_t* dev_text_off /* n_rec + 1 */, uint64_t* total);
+/* `kat sect -g`: the text Sect::printGCCounts (src/sect.cc:348-370, gcCountToPercentage; the counts of :525-541) writes to -counts.gc
+ * for a record, without its ">name" line, rendered on the device.  It follows from the bases alone: the calls take a context and k
+ * (1 <= k <= KATGPU_MAX_K, else KATGPU_ERR_K with a message), not a table.  Records are given as for katgpu_table_seq_hits_*; nb =
+ * rec_len - k + 1 when rec_len >= k, else 0.  Window j of a record is invalid when one of its k bytes is not one of ACGTacgt (validKmer,
+ * lib/include/kat/str_utils.hpp:183-201: N and n are no bases either) and its string is "-0.1"; otherwise g is the number of G g C c
+ * among them (gcCount, :151-165) and its string "%.1f" of ((double)g / (double)k) * 100.0 -- the k + 1 strings are formatted by the
+ * library on the host, the device copies their 3 to 5 characters.  A record's text is its nb strings with one space between them and
+ * '\n' behind the last, or "0.0\n" when nb == 0.  The call's text is the records' texts one after another; text_off[r], r = 0 ..
+ * n_rec, is the byte record r's text starts at, text_off[n_rec] the total.  Nothing per position is kept on the device or crosses
+ * the bus in either form: the text and 8 bytes per record come back.
+ * Host form: validates the records (KATGPU_ERR_INVALID_ARG, the messages of katgpu_table_seq_hits_host) and returns one malloc'ed
+ * array of text_off[n_rec] bytes in *text (katgpu_free_host; never NULL on success), brought back through the context's two pinned
+ * buffers (64 MiB each, made on first use).  Device memory, from the context's pool: the records go through in batches of at most B =
+ * 2^25 bases and 2^20 records, a record longer than B being a batch of its own: max(B, L) + 64 bytes of bases, with L the longest
+ * record, and 32 bytes per record of a batch; 8 bytes per 4096 bases for the tile sums, and the batch's text: at most 6 bytes per
+ * window start ("100.0 ") -- 192 MiB for a full batch.  KATGPU_ERR_NOMEM, with a message, when that cannot be had.
+ * Device form: takes device pointers, does not validate the records, and takes the tile sums and 8 bytes per record above, for all n
+ * bases, from the pool.  It writes the first min(*total, cap) bytes of the text to dev_text and always writes all of dev_text_off and
+ * reports the true total: a caller that sees *total > cap calls again with more room.  cap == 0 with dev_text == NULL only sizes;
+ * n_rec == 0 writes dev_text_off[0] = 0.  It returns when the work is done. */
+int katgpu_record_gc_text_host(katgpu_ctx* ctx, uint32_t k, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                               size_t n_rec, char** text, uint64_t* text_off /* n_rec + 1 */);
+int katgpu_record_gc_text_device(katgpu_ctx* ctx, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                 const uint64_t* dev_rec_len, size_t n_rec, uint8_t* dev_text, size_t cap,
+                                 uint64_t* dev_text_off /* n_rec + 1 */, uint64_t* total);
 /* All (key,count) pairs in unspecified order (the eager_iterator walk, JF/.../large_hash_iterator.hpp:28-65).
  * Pass cap = 0 to query *n_out only. */
 int katgpu_table_export(katgpu_table* t, uint64_t* keys, uint64_t* counts, size_t cap, size_t* n_out);

@@ -44,7 +44,7 @@ EXPORTS = (
     "katgpu_table_add_jf_records_device", "katgpu_jf_load_part",
     "katgpu_table_record_regions_host", "katgpu_table_record_regions_device", "katgpu_jf_dump_gathered",
     "katgpu_table_profile_gathered_host", "katgpu_table_record_cvg_text_host", "katgpu_table_record_cvg_text_device",
-    "katgpu_table_seq_hits_gathered_host",
+    "katgpu_table_seq_hits_gathered_host", "katgpu_record_gc_text_host", "katgpu_record_gc_text_device",
 )
 
 # katgpu_record_stats: one record of Table.record_stats
@@ -127,6 +127,8 @@ def load_library():
     L.katgpu_table_record_regions_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp, C.c_uint32, vp, sz, vp]
     L.katgpu_table_record_cvg_text_host.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp, vp]
     L.katgpu_table_record_cvg_text_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp, sz, vp, vp]
+    L.katgpu_record_gc_text_host.argtypes = [vp, u32, vp, sz, vp, vp, sz, vp, vp]
+    L.katgpu_record_gc_text_device.argtypes = [vp, u32, vp, sz, vp, vp, sz, vp, sz, vp, vp]
     L.katgpu_hist.argtypes = [vp, u64, u64, u64, vp, sz]
     L.katgpu_gcp.argtypes = [vp, C.c_double, u32, vp]
     L.katgpu_comp.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, u32, u32, vp, vp, vp]
@@ -440,6 +442,33 @@ class Engine:
         return Table(self, self.L.katgpu_table_k(h), bool(self.L.katgpu_table_canonical(h)), _handle=h.value)
 
     # ---- profiling ----
+    def record_gc_text(self, k, bases, rec_start, rec_len):
+        """The -counts.gc text of records (katgpu_record_gc_text_host): (text, offsets).  A record's text is "%.1f" of the G+C percentage
+        of each of its windows of k bases, "-0.1" for a window with a byte outside ACGTacgt, a space between them and a newline behind
+        the last, "0.0\\n" for a record without a window; record r's text is text[offsets[r]:offsets[r + 1]], offsets a u64 array of
+        n_rec + 1 entries.  No table: the text follows from the bases."""
+        if isinstance(bases, str):
+            bases = bases.encode()
+        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
+        st, ln = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_len, np.uint64)
+        assert st.size == ln.size
+        p = C.c_void_p()
+        off = np.zeros(st.size + 1, np.uint64)
+        self._chk(self.L.katgpu_record_gc_text_host(self.h, k, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size, C.byref(p), off.ctypes.data))
+        try:
+            text = C.string_at(p, int(off[-1]))
+        finally:
+            self.L.katgpu_free_host(p)
+        return text, off
+
+    def record_gc_text_device(self, k, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, dev_text, cap, dev_text_off):
+        """Device-resident form: DeviceBuffers or raw device addresses; `dev_text` takes `cap` bytes (None with cap 0: size only),
+        `dev_text_off` n_rec + 1 offsets of 8 bytes.  Returns the true number of bytes of the text, whatever `cap`."""
+        p = [getattr(x, "ptr", x) for x in (dev_bases, dev_rec_start, dev_rec_len, dev_text, dev_text_off)]
+        total = C.c_uint64()
+        self._chk(self.L.katgpu_record_gc_text_device(self.h, k, p[0], n, p[1], p[2], n_rec, p[3], cap, p[4], C.byref(total)))
+        return int(total.value)
+
     def profile_reset(self):
         self._chk(self.L.katgpu_profile_reset(self.h))
 

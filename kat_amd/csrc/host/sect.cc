@@ -6,7 +6,8 @@
 // per-record statistics and the text.  When no per-position output is asked for (-n) the device keeps the counts to itself: the
 // per-record statistics (katgpu_table_record_stats_host) and the regions of -E / -F (katgpu_table_record_regions_host) come back.
 // With KATGPU_SECT_DEVICE_TEXT=1 that holds without -n as well: the lines of -counts.cvg are rendered on the device
-// (katgpu_table_record_cvg_text_host) and no count comes back in any one-GPU mode.  Records are read with the semantics of the vendored SeqAn 2.0.0 reader
+// (katgpu_table_record_cvg_text_host) and no count comes back in any one-GPU mode.  In both of these modes the lines of -g's -counts.gc
+// come from the device as well (katgpu_record_gc_text_host), so nothing walks a record's bases on the host.  Records are read with the semantics of the vendored SeqAn 2.0.0 reader
 // (deps/seqan-library-2.0.0/include/seqan/seq_io/fasta_fastq.h:306-380, CharString target).
 #include "kat_host.hpp"
 #include "record_stats_host.hpp"
@@ -219,8 +220,8 @@ void Sect::gcText(Record& r, const vector<int16_t>& gc) {
     } else o += "0.0\n";
 }
 
-// A record from the device's statistics (katgpu_table_record_stats_host): no per-position output was asked for.  The GC line of -g
-// needs the bases only.
+// A record from the device's statistics (katgpu_table_record_stats_host): nothing here is per position.  (The GC line of -g is
+// rendered on the device: katgpu_record_gc_text_host in processSeqFile.)
 void Sect::processSeqStats(Record& r, const katgpu_record_stats& st) {
     const uint16_t k = input.merLen;
     const string& seq = *r.seq;
@@ -232,16 +233,6 @@ void Sect::processSeqStats(Record& r, const katgpu_record_stats& st) {
         r.mean = (double)st.sum / (double)nbCounts;
     }
     recordScalars(r, st.non_zero, st.invalid, st.gc_bases, st.n_bases);
-    if (outputGCStats) {
-        vector<int16_t> gc(nbCounts > 0 ? (size_t)nbCounts : 0);
-        uint32_t bad = 0, g = 0;
-        if (!gc.empty()) for (size_t i = 0; i < seqLength; i++) {
-            bad += !isBase(seq[i]); g += isGC(seq[i]);
-            if (i >= k) { bad -= !isBase(seq[i - k]); g -= isGC(seq[i - k]); }
-            if (i + 1 >= k) gc[i + 1 - k] = bad ? (int16_t)-1 : (int16_t)g;
-        }
-        gcText(r, gc);
-    }
 }
 
 // Everything the reference's processSeq + print* produce for one record, from the device's per-position counts.
@@ -369,6 +360,7 @@ void Sect::processSeqFile() {                                                   
     // default: a one-GPU run without -n is pinned to the per-position profile by the suite (tests/test_gpu_record_stats.py).
     const char* dt = getenv("KATGPU_SECT_DEVICE_TEXT");
     const bool cvg_text = !dist && !noCountStats && dt && atoi(dt) != 0, stats_only = !dist && (noCountStats || cvg_text);
+    const bool gc_text = stats_only && outputGCStats;        // -g there: the lines of -counts.gc from the device too, from the bases alone
     vector<katgpu_count_range> ranges;
     if (stats_only && extractNR) ranges.push_back({1, minRepeat});
     if (stats_only && extractR) ranges.push_back({minRepeat, maxRepeat});
@@ -377,6 +369,9 @@ void Sect::processSeqFile() {                                                   
     vector<size_t> first_nr, first_r;                         // a record's regions: [first[i], first[i + 1]) of its range's
     char* cvg = nullptr;                                      // the batch's -counts.cvg lines: record i's is [cvg_off[i], cvg_off[i + 1])
     vector<uint64_t> cvg_off;
+    char* gct = nullptr;                                      // the same of -counts.gc
+    vector<uint64_t> gct_off;
+    uint64_t gc_text_bytes = 0;
     // KATGPU_TIMING: where the phase's wall time goes (reader | joined buffer | device call | per-record host work | text), one line on stderr
     double t_part[5] = {0, 0, 0, 0, 0};
     auto lap = [&, t = std::chrono::steady_clock::now()](int part) mutable {
@@ -422,6 +417,11 @@ void Sect::processSeqFile() {                                                   
                 Engine::check(katgpu_table_record_cvg_text_host(input.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, input.canonical ? 1 : 0,
                                                                 &cvg, cvg_off.data()));
             }
+            if (gc_text) {
+                gct_off.resize(n + 1);
+                Engine::check(katgpu_record_gc_text_host(Engine::ctx(), input.merLen, joined.data(), joined.size(), offs.data(), lens.data(), n, &gct, gct_off.data()));
+                gc_text_bytes += gct_off[n];
+            }
         } else if (dist) {
             if (speak && counts.size() < joined.size()) counts.resize(joined.size());
             Engine::profileGathered(input.hash, joined.data(), joined.size(), input.canonical, speak ? counts.data() : nullptr);
@@ -459,7 +459,8 @@ void Sect::processSeqFile() {                                                   
             const Record& r = recs[i];
             if (cvg_text) { count_path_stream << '>' << *r.name << '\n'; count_path_stream.write(cvg + cvg_off[i], (std::streamsize)(cvg_off[i + 1] - cvg_off[i])); }
             else if (!noCountStats) count_path_stream << r.cvg_txt;
-            if (outputGCStats) gc_count_path_stream << r.gc_txt;
+            if (gc_text) { gc_count_path_stream << '>' << *r.name << '\n'; gc_count_path_stream.write(gct + gct_off[i], (std::streamsize)(gct_off[i + 1] - gct_off[i])); }
+            else if (outputGCStats) gc_count_path_stream << r.gc_txt;
             if (extractNR) nr_path_stream << r.nr_txt;
             if (extractR) r_path_stream << r.r_txt;
             // printStatTable, :427-445: std::fixed << setprecision(5); kmers_in_seq is uint32 arithmetic and wraps for short records
@@ -470,12 +471,14 @@ void Sect::processSeqFile() {                                                   
         }
         katgpu_free_host(cvg);
         cvg = nullptr;
+        katgpu_free_host(gct);
+        gct = nullptr;
         lap(4);
         if (verbose) std::cerr << "done" << endl;
     }
     if (getenv("KATGPU_TIMING") && speak)
-        fprintf(stderr, "katgpu_timing {\"phase\": \"sect_coverage\", \"read_s\": %.3f, \"join_s\": %.3f, \"device_call_s\": %.3f, \"records_s\": %.3f, \"text_s\": %.3f}\n",
-                t_part[0], t_part[1], t_part[2], t_part[3], t_part[4]);
+        fprintf(stderr, "katgpu_timing {\"phase\": \"sect_coverage\", \"read_s\": %.3f, \"join_s\": %.3f, \"device_call_s\": %.3f, \"records_s\": %.3f, \"text_s\": %.3f, \"gc_text_bytes\": %llu}\n",
+                t_part[0], t_part[1], t_part[2], t_part[3], t_part[4], (unsigned long long)gc_text_bytes);
     cout << " done.";
     cout.flush();
 }

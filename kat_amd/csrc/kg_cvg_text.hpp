@@ -129,10 +129,11 @@ k_cvg_tiles(const uint64_t* __restrict__ counts, uint64_t n, uint32_t k, const u
 }
 
 // K19.  Block 0: the tile sums become, in place, the offset of each tile's first byte among the windows' bytes.  Block 1: extra[r] =
-// 2 x the records before r that have no window.  totals[b] = the sum of block b's array.
+// empty_bytes x the records before r that have no window (2 for the "0\n" of the .cvg text, 4 for the "0.0\n" of kg_gc_text.hpp's).
+// totals[b] = the sum of block b's array.
 static __global__ void __launch_bounds__(CT_SCAN_BLOCK)
 k_cvg_scan(unsigned long long* __restrict__ tile_sum, uint64_t n_tiles, const uint64_t* __restrict__ rec_len, uint64_t n_rec, uint32_t k,
-           uint64_t* __restrict__ extra, unsigned long long* __restrict__ totals) {
+           uint32_t empty_bytes, uint64_t* __restrict__ extra, unsigned long long* __restrict__ totals) {
     __shared__ uint64_t s_w[CT_SCAN_BLOCK / 64];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool recs = blockIdx.x == 1;
@@ -143,7 +144,7 @@ k_cvg_scan(unsigned long long* __restrict__ tile_sum, uint64_t n_tiles, const ui
         uint64_t v[CT_SCAN_ITEMS], sum = 0;
 #pragma unroll
         for (int j = 0; j < CT_SCAN_ITEMS; ++j) {
-            v[j] = i + j >= cnt ? 0 : recs ? (rec_len[i + j] < k ? 2 : 0) : tile_sum[i + j];
+            v[j] = i + j >= cnt ? 0 : recs ? (rec_len[i + j] < k ? empty_bytes : 0) : tile_sum[i + j];
             sum += v[j];
         }
         uint64_t inc = sum;                                        // inclusive sums along the wave

@@ -2,7 +2,7 @@
 // handles of include/katgpu.h, error plumbing, the allocation pool, launch timing.  The library is split by concern:
 //   kg_context.hip   context, pool, profile counters, device buffers, the synthetic workload
 //   kg_table.hip     table life cycle: geometry, create / regrow / free, counters and statistics, room for records to come
-//   kg_query.hip     a sequence or keys against a table: lookups, profiles and per-record hits (one table, or the ranks' tables gathered), coverage statistics, count-range regions and -counts.cvg text
+//   kg_query.hip     a sequence or keys against a table: lookups, profiles and per-record hits (one table, or the ranks' tables gathered), coverage statistics, count-range regions, -counts.cvg and -counts.gc text
 //   kg_records.hip   records out of a table and into one: partition / export / merge, the k-mer filter
 //   kg_jf_device.hip .jf records in file order out of a table, and streamed from a file into one
 //   kg_count.hip     counting: the direct kernel, the partitioned counter's host loop, the host feeder, katgpu_count*
@@ -12,7 +12,7 @@
 //   kg_comm_exchange.hip  the exchange itself, above the communicator (katgpu_exchange_*)
 //   kg_reduce.hip    hist / gcp / comp
 // A unit's kernels are in the headers only it includes, or in the unit itself: kg_context.hip kg_synth_kernels.hpp; kg_table.hip its own
-// (k_regrow, k_total); kg_query.hip kg_query_kernels.hpp, kg_filter.hpp (K10), kg_record_stats.hpp, kg_record_regions.hpp, kg_cvg_text.hpp;
+// (k_regrow, k_total); kg_query.hip kg_query_kernels.hpp, kg_filter.hpp (K10), kg_record_stats.hpp, kg_record_regions.hpp, kg_cvg_text.hpp, kg_gc_text.hpp;
 // kg_records.hip kg_record_kernels.hpp, kg_filter.hpp (K9); kg_jf_device.hip kg_jf_records.hpp, kg_jf_load.hpp; kg_count.hip its own
 // (k_sweep), kg_partition.hpp and what that includes, kg_partition_wide.hpp; kg_scan.hip kg_scan.hpp; kg_exchange.hip kg_exchange_kernels.hpp;
 // kg_reduce.hip kg_reduce_kernels.hpp.  Shared: kg_kernels.hpp (the chunk geometry and the direct counter k_count) and kg_rows_scan.hpp

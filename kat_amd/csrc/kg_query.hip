@@ -1,6 +1,6 @@
 // kg_query.hip -- a sequence or keys against a table, which is left as it is: batch lookups (katgpu_table_get*), per-position profiles
 // (katgpu_table_profile_*; _gathered_host: of a table that lies on several ranks, gathered on rank 0), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*; _gathered_host: summed over the ranks' tables on rank 0), the per-record coverage statistics
-// of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*) the count-range regions of `kat sect -E / -F` (katgpu_table_record_regions_*) and the -counts.cvg text of `kat sect` (katgpu_table_record_cvg_text_*).  The host forms send their input through the device in batches.
+// of `kat sect -n` and `kat cold` (katgpu_table_record_stats_*) the count-range regions of `kat sect -E / -F` (katgpu_table_record_regions_*) the -counts.cvg text of `kat sect` (katgpu_table_record_cvg_text_*) and the -counts.gc text of `kat sect -g` (katgpu_record_gc_text_*: bases only, no table).  The host forms send their input through the device in batches.
 #include "kg_host.hpp"
 #include "kg_comm.hpp"
 #include "kg_kernels.hpp"
@@ -9,6 +9,7 @@
 #include "kg_record_stats.hpp"
 #include "kg_record_regions.hpp"
 #include "kg_cvg_text.hpp"
+#include "kg_gc_text.hpp"
 
 static const bool g_forbid_profile_host = hook_u64("KATGPU_TEST_FORBID_PROFILE_HOST", 0) != 0;   // tests: a driver that should not need per-position counts asks for none
 static const size_t g_profile_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_PROFILE_BATCH", (uint64_t)32 << 20), 1);   // tests: window starts per batch of profile_host
@@ -688,7 +689,7 @@ static int launch_cvg_size(katgpu_table* t, const uint8_t* dev_bases, size_t n, 
     const dim3 grid((unsigned)std::min<uint64_t>(w.n_tiles, (uint64_t)c->n_cu * 8));
     hipLaunchKernelGGL(k_cvg_tiles<false>, grid, dim3(CT_BLOCK), 0, c->stream, w.counts, (uint64_t)n, k, dev_start, dev_len, (uint64_t)n_rec, w.n_tiles, w.tile_sum,
                        w.extra, w.totals, (uint64_t)0, (uint8_t*)nullptr, (uint64_t)0, (uint64_t*)nullptr);
-    hipLaunchKernelGGL(k_cvg_scan, dim3(2), dim3(CT_SCAN_BLOCK), 0, c->stream, w.tile_sum, w.n_tiles, dev_len, (uint64_t)n_rec, k, w.extra, w.totals);
+    hipLaunchKernelGGL(k_cvg_scan, dim3(2), dim3(CT_SCAN_BLOCK), 0, c->stream, w.tile_sum, w.n_tiles, dev_len, (uint64_t)n_rec, k, 2u, w.extra, w.totals);
     HIPCHK(c, hipGetLastError());
     return KATGPU_OK;
 }
@@ -729,6 +730,33 @@ extern "C" int katgpu_table_record_cvg_text_device(katgpu_table* t, const uint8_
     if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "cvg text: %s", hipGetErrorString(e));
     *total = totals[0] + totals[1];
     return KATGPU_OK;
+}
+
+// What the host forms of the text calls share.  text_room: the result holds `need` bytes, grown by half at least.  text_fetch: `total`
+// bytes of a batch's text from the device to dst through the context's two pinned buffers (ensure_pinned), piece i on its way into one
+// while piece i - 1 is copied out of the other.
+static int text_room(katgpu_ctx* c, const char* what, char*& res, size_t& res_cap, size_t need) {
+    if (need <= res_cap) return KATGPU_OK;
+    const size_t want = std::max(need, res_cap + res_cap / 2);
+    char* grown = (char*)realloc(res, want);
+    if (!grown) return fail(c, KATGPU_ERR_NOMEM, "%s: no host memory for %zu bytes of text", what, want);
+    res = grown; res_cap = want;
+    return KATGPU_OK;
+}
+static hipError_t text_fetch(katgpu_ctx* c, const uint8_t* dev, size_t total, char* dst) {
+    hipError_t e = hipSuccess;
+    const size_t piece = c->stage_bytes, n_pieces = (total + piece - 1) / piece;
+    for (size_t i = 0; i <= n_pieces && e == hipSuccess; ++i) {
+        if (i < n_pieces) {
+            e = hipMemcpyAsync(c->pinned[i & 1], dev + i * piece, std::min(piece, total - i * piece), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipEventRecord(c->pin_free[i & 1], c->stream);
+        }
+        if (i && e == hipSuccess) {
+            e = hipEventSynchronize(c->pin_free[(i - 1) & 1]);
+            if (e == hipSuccess) memcpy(dst + (i - 1) * piece, c->pinned[(i - 1) & 1], std::min(piece, total - (i - 1) * piece));
+        }
+    }
+    return e;
 }
 
 // Host form: the records go through the device in batches of at most g_cvg_batch bases and 2^20 records (for_record_batches), so any input
@@ -774,25 +802,10 @@ extern "C" int katgpu_table_record_cvg_text_host(katgpu_table* t, const char* ba
                 }
                 out_cap = total;
             }
-            if (have + total > res_cap) {
-                const size_t want = std::max(have + total, res_cap + res_cap / 2);
-                char* grown = (char*)realloc(res, want);
-                if (!grown) return fail(c, KATGPU_ERR_NOMEM, "cvg text: no host memory for %zu bytes of text", want);
-                res = grown; res_cap = want;
-            }
+            rc = text_room(c, "cvg text", res, res_cap, have + total); if (rc) return rc;
             rc = launch_cvg_write(t, nb, ds, dl, m, w, have, out.as<uint8_t>(), total, w.text_off); if (rc) return rc;
             e = hipMemcpyAsync(text_off + r0, w.text_off, m * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
-            const size_t piece = c->stage_bytes, n_pieces = (total + piece - 1) / piece;
-            for (size_t i = 0; i <= n_pieces && e == hipSuccess; ++i) {   // piece i on its way into one pinned buffer, piece i - 1 out of the other
-                if (i < n_pieces) {
-                    e = hipMemcpyAsync(c->pinned[i & 1], out.as<uint8_t>() + i * piece, std::min(piece, total - i * piece), hipMemcpyDeviceToHost, c->stream);
-                    if (e == hipSuccess) e = hipEventRecord(c->pin_free[i & 1], c->stream);
-                }
-                if (i && e == hipSuccess) {
-                    e = hipEventSynchronize(c->pin_free[(i - 1) & 1]);
-                    if (e == hipSuccess) memcpy(res + have + (i - 1) * piece, c->pinned[(i - 1) & 1], std::min(piece, total - (i - 1) * piece));
-                }
-            }
+            if (e == hipSuccess) e = text_fetch(c, out.as<uint8_t>(), total, res + have);
             have += total;
             return e == hipSuccess ? (int)KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "cvg text: %s", hipGetErrorString(e));
         });
@@ -801,6 +814,171 @@ extern "C" int katgpu_table_record_cvg_text_host(katgpu_table* t, const char* ba
     }
     if (!res) res = (char*)malloc(1);
     if (!res) return fail(c, KATGPU_ERR_NOMEM, "cvg text: no host memory for the text");
+    text_off[n_rec] = have;
+    *text = res;
+    return KATGPU_OK;
+}
+
+// ------------------------------------------------------------------ the -counts.gc text of records (kat sect -g) ----
+
+static const size_t g_gc_batch = (size_t)std::max<uint64_t>(hook_u64("KATGPU_TEST_GC_BATCH", (uint64_t)32 << 20), 1);   // tests: bases per batch of the host form
+
+// the k + 2 strings of a window (kg_gc_text.hpp): glibc's "%.1f" of every percentage, and "-0.1"
+static GcStrings gc_strings(uint32_t k) {
+    GcStrings s{};
+    auto entry = [](const char* str) {
+        const size_t len = strlen(str);
+        uint64_t e = (uint64_t)len << 56;
+        for (size_t i = 0; i < len; ++i) e |= (uint64_t)(uint8_t)str[i] << (8 * i);
+        return e;
+    };
+    char tmp[32];
+    for (uint32_t g = 0; g <= k; ++g) { snprintf(tmp, sizeof tmp, "%.1f", ((double)g / (double)k) * 100.0); s.e[g] = entry(tmp); }
+    s.e[k + 1] = entry("-0.1");
+    return s;
+}
+
+// the workspace of one call or batch of n bases and n_rec records: a sum per tile | the window-less records' bytes before every record |
+// the two totals | (with_off: the host form's) a text offset per record and one more
+struct GcWork {
+    DevBuf buf;
+    size_t bytes = 0;
+    uint64_t n_tiles = 0;
+    GcStrings strs;
+    uint64_t *extra = nullptr, *text_off = nullptr;
+    unsigned long long *tile_sum = nullptr, *totals = nullptr;
+    int fit(katgpu_ctx* c, size_t n, size_t n_rec, bool with_off) {
+        n_tiles = n / CT_TILE + 1;                                 // positions 0 .. n
+        const size_t extra_off = n_tiles * 8, tot_off = extra_off + n_rec * 8, off_off = tot_off + 16;
+        const size_t need = off_off + (with_off ? (n_rec + 1) * 8 : 0);
+        if (need > bytes) {
+            bytes = 0;
+            if (buf.pooled(c, need) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(c, KATGPU_ERR_NOMEM, "gc text: no %zu bytes of device memory for the tile sums of %zu bases and %zu records", need, n, n_rec);
+            }
+            bytes = need;
+        }
+        uint8_t* w = buf.as<uint8_t>();
+        tile_sum = (unsigned long long*)w; extra = (uint64_t*)(w + extra_off);
+        totals = (unsigned long long*)(w + tot_off); text_off = (uint64_t*)(w + off_off);
+        return KATGPU_OK;
+    }
+};
+
+template <bool WRITE>
+static void launch_gc_tiles(katgpu_ctx* c, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec,
+                            const GcWork& w, uint64_t text_base, uint8_t* dev_text, size_t cap, uint64_t* dev_text_off) {
+    const dim3 grid((unsigned)std::min<uint64_t>(w.n_tiles, (uint64_t)c->n_cu * 8));
+    auto go = [&](auto A) {
+        hipLaunchKernelGGL((k_gc_tiles<WRITE, decltype(A)::value>), grid, dim3(CT_BLOCK), 0, c->stream, dev_bases, (uint64_t)n, k, w.strs, dev_start, dev_len,
+                           (uint64_t)n_rec, w.n_tiles, w.tile_sum, w.extra, w.totals, text_base, dev_text, (uint64_t)cap, dev_text_off);
+    };
+    if (aligned16(dev_bases)) go(std::true_type{});
+    else go(std::false_type{});
+}
+
+// On the stream: K20 without writing, K19; w.totals then holds the bytes of the windows and of the window-less records.
+static int launch_gc_size(katgpu_ctx* c, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec, const GcWork& w) {
+    ScopedTimer tm(c, KATGPU_K_PROFILE, n >= k ? n - k + 1 : 0);
+    launch_gc_tiles<false>(c, k, dev_bases, n, dev_start, dev_len, n_rec, w, 0, nullptr, 0, nullptr);
+    hipLaunchKernelGGL(k_cvg_scan, dim3(2), dim3(CT_SCAN_BLOCK), 0, c->stream, w.tile_sum, w.n_tiles, dev_len, (uint64_t)n_rec, k, 4u, w.extra, w.totals);
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+// K20 again behind it: the first `cap` bytes of the text to dev_text, the records' offsets (n_rec + 1, counted from text_base) to dev_text_off
+static int launch_gc_write(katgpu_ctx* c, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec,
+                           const GcWork& w, uint64_t text_base, uint8_t* dev_text, size_t cap, uint64_t* dev_text_off) {
+    ScopedTimer tm(c, KATGPU_K_PROFILE, 0);
+    launch_gc_tiles<true>(c, k, dev_bases, n, dev_start, dev_len, n_rec, w, text_base, dev_text, cap, dev_text_off);
+    HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+static int gc_check_k(katgpu_ctx* c, uint32_t k) {
+    if (k < 1 || k > KATGPU_MAX_K) return fail(c, KATGPU_ERR_K, "gc text: k = %u unsupported (1 <= k <= %d)", k, KATGPU_MAX_K);
+    return KATGPU_OK;
+}
+
+extern "C" int katgpu_record_gc_text_device(katgpu_ctx* c, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                            const uint64_t* dev_rec_len, size_t n_rec, uint8_t* dev_text, size_t cap, uint64_t* dev_text_off, uint64_t* total) {
+    if (!c || !total || !dev_text_off || (n_rec && (!dev_rec_start || !dev_rec_len)) || (n && !dev_bases) || (cap && !dev_text)) return KATGPU_ERR_INVALID_ARG;
+    *total = 0;
+    int rc = gc_check_k(c, k); if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!n_rec) {
+        HIPCHK(c, hipMemsetAsync(dev_text_off, 0, sizeof(uint64_t), c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return KATGPU_OK;
+    }
+    GcWork w;
+    w.strs = gc_strings(k);
+    rc = w.fit(c, n, n_rec, false); if (rc) return rc;
+    rc = launch_gc_size(c, k, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, w);
+    if (!rc) rc = launch_gc_write(c, k, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, w, 0, dev_text, cap, dev_text_off);
+    unsigned long long totals[2] = {0, 0};
+    hipError_t e = hipMemcpyAsync(totals, w.totals, sizeof totals, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "gc text: %s", hipGetErrorString(e));
+    *total = totals[0] + totals[1];
+    return KATGPU_OK;
+}
+
+// Host form: the records go through the device in batches of at most g_gc_batch bases and 2^20 records (for_record_batches).  Per batch
+// the totals come back first, then room for the batch's text is found on the device and in the result, K20 fills it, and it comes back
+// through the context's two pinned buffers (text_fetch); the offsets of a batch count from the call's first byte.
+extern "C" int katgpu_record_gc_text_host(katgpu_ctx* c, uint32_t k, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
+                                          size_t n_rec, char** text, uint64_t* text_off) {
+    if (!c || !text || !text_off || (n_rec && (!rec_start || !rec_len)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    *text = nullptr;
+    int rc = gc_check_k(c, k); if (rc) return rc;
+    char* res = nullptr;
+    size_t have = 0, res_cap = 0;
+    if (n_rec) {
+        rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;
+        HIPCHK(c, hipSetDevice(c->device));
+        rc = ensure_pinned(c); if (rc) return rc;
+        const size_t max_recs = std::min(n_rec, (size_t)1 << 20);
+        DevBuf recs, out;                                          // start and length of every record of a batch; the text of a batch
+        size_t out_cap = 0;
+        if (recs.pooled(c, max_recs * 2 * sizeof(uint64_t)) != hipSuccess)
+            return fail(c, KATGPU_ERR_NOMEM, "gc text: no device memory for the records of a batch");
+        uint64_t* dr = recs.as<uint64_t>();
+        GcWork w;
+        w.strs = gc_strings(k);
+        size_t no_room = 0;
+        rc = for_record_batches(c, bases, n, rec_start, rec_len, n_rec, g_gc_batch, max_recs, dr, dr + max_recs, "gc text", &no_room,
+                                [](size_t, bool) { return true; },
+                                [&](const uint8_t* db, size_t nb, const uint64_t* ds, const uint64_t* dl, size_t m, size_t r0) {
+            int rc = w.fit(c, nb, m, true); if (rc) return rc;
+            rc = launch_gc_size(c, k, db, nb, ds, dl, m, w); if (rc) return rc;
+            unsigned long long totals[2] = {0, 0};
+            hipError_t e = hipMemcpyAsync(totals, w.totals, sizeof totals, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "gc text: %s", hipGetErrorString(e));
+            const size_t total = (size_t)(totals[0] + totals[1]);
+            if (total > out_cap) {
+                out_cap = 0;
+                if (out.pooled(c, total) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return fail(c, KATGPU_ERR_NOMEM, "gc text: no %zu bytes of device memory for the text of a batch", total);
+                }
+                out_cap = total;
+            }
+            rc = text_room(c, "gc text", res, res_cap, have + total); if (rc) return rc;
+            rc = launch_gc_write(c, k, db, nb, ds, dl, m, w, have, out.as<uint8_t>(), total, w.text_off); if (rc) return rc;
+            e = hipMemcpyAsync(text_off + r0, w.text_off, m * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess) e = text_fetch(c, out.as<uint8_t>(), total, res + have);
+            have += total;
+            return e == hipSuccess ? (int)KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "gc text: %s", hipGetErrorString(e));
+        });
+        if (no_room) rc = fail(c, KATGPU_ERR_NOMEM, "gc text: no %zu bytes of device memory for a batch of bases", no_room);
+        if (rc) { free(res); return rc; }
+    }
+    if (!res) res = (char*)malloc(1);
+    if (!res) return fail(c, KATGPU_ERR_NOMEM, "gc text: no host memory for the text");
     text_off[n_rec] = have;
     *text = res;
     return KATGPU_OK;

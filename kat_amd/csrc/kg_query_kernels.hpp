@@ -1,5 +1,5 @@
 // kg_query_kernels.hpp -- lookups that leave the table as it is, written for gfx950 (CDNA4, wave64): what kg_query.hip launches
-// beside the kernels of kg_filter.hpp, kg_record_stats.hpp, kg_record_regions.hpp and kg_cvg_text.hpp.
+// beside the kernels of kg_filter.hpp, kg_record_stats.hpp, kg_record_regions.hpp, kg_cvg_text.hpp and kg_gc_text.hpp.
 //
 //     k_get            batch lookup of keys                                      (replaces JellyfishHelper::getCount)
 //  K8 k_profile        per-position lookup of a sequence's windows               (replaces the lookups of Sect::processSeq)
