@@ -115,10 +115,11 @@ static const uint64_t g_test_p2_ovf_cap = hook("KATGPU_TEST_P2_OVF_CAP") ? strto
 static const uint32_t g_test_spill_mod = hook("KATGPU_TEST_SPILL_MOD") ? (uint32_t)strtoul(hook("KATGPU_TEST_SPILL_MOD"), nullptr, 10) : 0;
 static const uint64_t g_test_ap_seg = hook_u64("KATGPU_TEST_AP_SEG", 0) & ~3ULL;   // tests: k-mers per walk segment of the apply kernels (several segments per run)
 static const uint32_t g_apply_per_cu = (uint32_t)hook_u64("KATGPU_APPLY_PER_CU", 0);   // A/B: packed apply workgroups per CU (0: as many as the LDS holds)
+static const uint64_t g_fresh_max_pct = hook_u64("KATGPU_FRESH_MAX_PCT", 100);   // A/B: a packed table's first round claims inline below this many items per 100 slots (launch_apply)
 static const bool g_l1b_stamp = hook_u64("KATGPU_L1B_STAMP", 0) != 0;   // diagnostic: level 1's block edition with cycle stamps (printed per round)
 static const bool g_p2x_stamp = hook_u64("KATGPU_P2X_STAMP", 0) != 0;   // diagnostic: kg_l2_blocks.hpp's kernel with cycle stamps (printed per pass)
 static const bool g_p2_stamp = hook_u64("KATGPU_P2_STAMP", 0) != 0;   // diagnostic: the one-pass level 2 of 5-byte items from groups with cycle stamps (printed per pass)
-static const bool g_apply_stamp = hook_u64("KATGPU_APPLY_STAMP", 0) != 0;              // diagnostic: the bench-shape apply with cycle stamps (printed per pass)
+static const bool g_apply_stamp = hook_u64("KATGPU_APPLY_STAMP", 0) != 0;              // diagnostic: the bench-shape apply, and a first round's small-region shape, with cycle stamps (printed per pass)
 
 static bool part_geometry(const DevTable& d, PartGeom* g) {
     g->R = d.n_regions; g->S = d.region_slots; g->P1 = d.p1; g->P2 = d.p2; g->l2 = d.l2;
@@ -288,12 +289,16 @@ static int apply_pk(const ApplyLaunch& a) {
                       a.qcap, a.seg_len, g_test_spill_mod, a.zero_fill);
 }
 // probe rounds before the queue: 2 (measured at the bench size, same box: 163 ms per step against 177 with 3 and 198 with inline
-// claims in every round); a table's first round claims inline and keeps 3
+// claims in every round); a table's first round claims inline and keeps 3 -- where launch_apply calls it fresh
 template <int HB>
 static int apply_pk_shape(const ApplyLaunch& a, uint32_t blk, bool fresh, bool hooked) {
     if (hooked) return apply_pk<1024, 5, HB, false, true, true, 3>(a);
     if (blk == 1024) return fresh ? apply_pk<1024, 5, HB, true, false, true, 3>(a) : apply_pk<1024, 5, HB, false, false, true, 2>(a);
-    if (a.g.S <= 4096) return fresh ? apply_pk<512, 4, HB, true, false, true, 3>(a) : apply_pk<512, 4, HB, false, false, true, 2>(a);
+    if (a.g.S <= 4096) {
+        if (HB == 1 && g_apply_stamp && fresh)               // diagnostic: the small-region shape of a first round (the bench's second input) with cycle stamps
+            return with_stamps(a.t->ctx, a.spill_n + STAMP_AT_APPLY, 7, nullptr, [&](unsigned long long*) { return apply_pk<512, 4, 1, true, false, true, 3, true>(a); });
+        return fresh ? apply_pk<512, 4, HB, true, false, true, 3>(a) : apply_pk<512, 4, HB, false, false, true, 2>(a);
+    }
     if (HB == 1 && g_apply_stamp && !fresh)                  // diagnostic: the bench's shape with cycle stamps (the kernel adds them at spill_n + STAMP_AT_APPLY)
         return with_stamps(a.t->ctx, a.spill_n + STAMP_AT_APPLY, 7, nullptr, [&](unsigned long long*) { return apply_pk<512, 10, 1, false, false, false, 2, true>(a); });
     return fresh ? apply_pk<512, 10, HB, true, false, false, 3>(a) : apply_pk<512, 10, HB, false, false, false, 2>(a);
@@ -313,16 +318,18 @@ static int apply_kv12_shape(const ApplyLaunch& a, uint32_t blk, bool big, bool f
     return fresh ? apply_kv12<1024, 4, HB, true, AP2_QCAP, false>(a) : apply_kv12<1024, 4, HB, false, AP2_QCAP, false>(a);
 }
 static int launch_apply(katgpu_table* t, const PartGeom& g, const uint64_t* off2, const uint8_t* l2_buf, uint64_t* spill_buf, unsigned long long* spill_n,
-                        const uint32_t* run_len, const uint64_t* bucket_end, ApplyForm* form = nullptr) {
+                        const uint32_t* run_len, const uint64_t* bucket_end, uint64_t round_items, ApplyForm* form = nullptr) {
     katgpu_ctx* c = t->ctx;
     const uint32_t n_cu = (uint32_t)c->n_cu, regions = (g.b_hi - g.b_lo) * g.P2;
-    const bool fresh = t->distinct == 0;                     // (inline claims in a table's first round)
+    bool fresh = t->distinct == 0;                           // (inline claims in a table's first round; a packed table's: see below)
     const bool hooked = g_test_spill_mod != 0;
     ApplyLaunch a{t, g, off2, l2_buf, spill_buf, spill_n, run_len, bucket_end, dim3(1), 0, 0, 0, 0, form};
     int rc = KATGPU_OK;
     if (g.cbits) {
         // 512-thread workgroups, as many per CU as the LDS holds next to their queues (two at the bench's 9344-slot regions, four for
-        // small regions); one of 1024 threads when a region leaves no room for a second
+        // small regions); one of 1024 threads when a region leaves no room for a second.  (Four is what the LDS admits and what the grid is sized
+        // for; by registers -- 85-91 VGPRs for the small shapes, five waves per SIMD -- TWO are resident at a time and the other half of the grid follows.
+        // A grid of two per CU measured inside the spread, step 371.1 -> 370.5 ms: profiles/second_input_parent_vs_branch.txt; four stays.)
         const size_t region_b = (size_t)g.S * 8;
         auto room = [&](uint32_t wgs) -> long { return (long)(LDS_BYTES / wgs / LDS_GRANULE * LDS_GRANULE) - 64 - (long)region_b; };   // bytes left for the queues
         uint32_t per_cu = 4;
@@ -339,6 +346,16 @@ static int launch_apply(katgpu_table* t, const PartGeom& g, const uint64_t* off2
         a.qcap = (uint32_t)std::min<long>(256, room(per_cu) / (long)(nw * 8));
         if (a.qcap < 72) return fail(c, KATGPU_ERR_DEVICE, "a region of %u packed slots leaves no room for the apply kernel's queues", g.S);
         a.lds = region_b + (size_t)nw * a.qcap * 8;
+        // Inline claims in a table's first round -- where the round can be mostly new k-mers.  A round of more items than the table has slots is
+        // mostly repeats whatever it holds (a deep read set) and takes the steady-state shape, whose claims go through the waves' queues -- if those
+        // are of ordinary length: a wave leaves up to 64 entries behind a chunk, so the next chunk's survivors find qcap - 64 places.  Measured
+        // per step (profiles/second_input_parent_vs_branch.txt), steady-state against inline: hist and gcp (9 items per slot, 255 entries) apply
+        // 19.7 -> 15.3 and 44.0 -> 34.6 ms; the bench's reads (2.5, 111) 2 x 22.9 -> 2 x 21.5; config 5's shard (3.6, the 72 entries that min_q admits
+        // for a second workgroup) 79.5 -> 116.5: it keeps inline claims; the bench's assembly (0.62) + 9.7 ms: it does too.  That the queue's length
+        // is what sets config 5 apart is SUPPOSED, not measured: it also differs in k, item width and items per slot, and no shape was run with its
+        // queue alone shortened.  Between the measured points the limits are min_q's 96 entries and the pigeonhole's one item per slot (no point
+        // between 0.62 and 2.5 items per slot was measured).  g_fresh_max_pct is the A/B.  KV12 tables: not measured.
+        if (fresh && a.qcap >= 96 && (double)round_items * 100.0 >= (double)g_fresh_max_pct * (double)t->dv.cap) fresh = false;
         const uint64_t seg_cap = (pk_half(g.cbits) - 1) & ~3ULL;                              // a walk adds less than half the count range
         a.seg_len = g_test_ap_seg ? std::min<uint64_t>(g_test_ap_seg, seg_cap) : std::min<uint64_t>(AP2_SEGMENT, seg_cap);
         a.grid = dim3(std::min<uint32_t>(regions, n_cu * per_cu));
@@ -669,7 +686,7 @@ static int level2_and_apply(katgpu_table* t, PartGeom& g, const L1Plan& l1, cons
         ovf_total = overflowed;
         {   // (exact level 2: a bucket's runs stop short of the next bucket's -- bend)
             ScopedTimer tm(c, KATGPU_K_PART_APPLY, pass_items);
-            rc = launch_apply(t, g, A.off2, A.l2_buf, spill_buf, A.spill_n, runs ? A.cnt2 : nullptr, runs ? nullptr : A.bend, &ap);
+            rc = launch_apply(t, g, A.off2, A.l2_buf, spill_buf, A.spill_n, runs ? A.cnt2 : nullptr, runs ? nullptr : A.bend, items, &ap);
         }
         if (rc) return rc;
         HIPCHK(c, hipGetLastError());

@@ -616,6 +616,11 @@ k_comp_fused(DevTable t1, uint32_t n1_ovf, DevTable t2, uint32_t n2_ovf, CompArg
     hot_s.tile_cell = SWAP ? comp_tile_cell<1>(1, 0, a) : comp_tile_cell<2>(1, 0, a);
     hot_r.tile_cell = SWAP ? comp_tile_cell<2>(1, 0, a) : comp_tile_cell<1>(1, 0, a);
     hot_s.spec_bin = hot_r.spec_bin = spectrum_bin(1u, a.spec_size);
+    // The sweep's short cut for hot_r's k-mers (count 1, absent there): where that account is nothing but tallies -- its cell lies in the
+    // tile (else it is a global atomic) and the resident table has no side-table entry that could continue a slot's count of 1
+    const bool sweep_hot = hot_r.tile_cell != 0xFFFFFFFFu && !(OVF && nr_ovf);
+    const uint64_t cmask = pk_cmask(cb);
+    uint32_t n_hot = 0;                                        // this lane's (fewer than 2^32 slots per lane, as CompAcc's tallies)
     const Place pl = place_make(tr.k, tr.p1, tr.n1, tr.l2);
     const uint32_t R = tr.n_regions;
     u32x4s kq[FUSED_KP], wq[JP];
@@ -713,6 +718,8 @@ k_comp_fused(DevTable t1, uint32_t n1_ovf, DevTable t2, uint32_t n2_ovf, CompArg
         }
         __syncthreads();                                       // every mark is in
         // ---- the resident region: what of it the accounts want (hash 1 resident: the k-mers nobody found; hash 2: all), the same way ----
+        // Most of them are hot_r's case -- count 1, nobody found it (two of three occupied slots of a read set's region): such a slot is
+        // one more in the lane's n_hot and never sees the queue or the account (the account's sums get their share behind the region loop)
 #pragma unroll 1
         for (uint32_t i0 = 0; ; i0 += blockDim.x) {
             const bool more = i0 + wave0 < Sr;                 // (uniform in the wave)
@@ -720,7 +727,9 @@ k_comp_fused(DevTable t1, uint32_t n1_ovf, DevTable t2, uint32_t n2_ovf, CompArg
                 const uint32_t i = i0 + tid;
                 const unsigned long long cur = i < Sr ? rk[i] : 0ULL;
                 const bool marked = i < Sr && ((s_mark[i >> 5] >> (i & 31)) & 1u);
-                const bool want = cur != 0 && (SWAP || !marked);
+                const bool hot = sweep_hot && cur != 0 && !marked && (cur & cmask) == 1;
+                n_hot += hot ? 1u : 0u;
+                const bool want = cur != 0 && (SWAP || !marked) && !hot;
                 const unsigned long long m = __ballot(want);
                 if (m) {
                     const uint32_t at = q_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
@@ -742,6 +751,13 @@ k_comp_fused(DevTable t1, uint32_t n1_ovf, DevTable t2, uint32_t n2_ovf, CompArg
             }
             if (!more) break;
         }
+    }
+    {   // what comp_account<SWAP ? 2 : 1, true>(true, 1, 0, ..., &hot_r) does, n_hot times: the four sums, hot_r's cell, and the spectrum's bin of
+        // count 1 (pass 1 with CompArgs::fold takes a tile k-mer's spectrum from the tile's marginals: no bin then)
+        CompAcc& acc = SWAP ? acc2 : acc1;
+        acc.a_total += n_hot; acc.a_distinct += n_hot; acc.a_only_total += n_hot; acc.a_only_distinct += n_hot;
+        hot_r.n_tile += n_hot;
+        if (SWAP || !a.fold) hot_r.n_spec += n_hot;
     }
     comp_hot_flush(hot_s, s_tile, SWAP ? s_spec1 : s_spec2);
     comp_hot_flush(hot_r, s_tile, SWAP ? s_spec2 : s_spec1);
