@@ -1704,6 +1704,235 @@ k_p3_apply2(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const uin
 constexpr int APK_LANE_PROBES = 12;
 constexpr uint32_t APK_SLOT_SHIFT = 44;
 
+// The walk of one run segment by one wave of the packed apply (k_p3_apply_pk), a function of its own: chunks of 64 U k-mers
+// from the segment's LDS counter, NR unconditional probe rounds, survivors to the wave's queue, drain_pass with its wave-wide finish, the spill of a
+// k-mer whose region is full.  The queue is empty when walk() returns: a queue entry belongs to the region image it was made for.
+// One kernel uses it today.  It stands apart from k_p3_apply_pk for the next attempt at an apply whose waves are not tied to a region (DESIGN.md
+// section 8, item 1: the first was built on it, measured and taken out), which walks the same way from another frame -- and because the kernel measured
+// faster with its walk compiled as a function (same section): an effect of this compiler's code generation that no test pins.
+template <int HB, bool INLINE_CLAIM, bool TEST_SPILL, int NR, bool STAMP, int UG>
+struct ApkWalk {
+    static constexpr int U = 4 * UG;
+    static constexpr uint32_t CH = 64 * U;
+    static constexpr uint64_t rem_mask = (1ULL << APK_SLOT_SHIFT) - 1;
+    const PartGeom& g;
+    unsigned long long* rk;                                   // the region's image in LDS
+    unsigned long long* wq;                                   // this wave's queue
+    uint64_t* __restrict__ spill; unsigned long long* __restrict__ spill_n;
+    uint32_t S, cb, qcap, lane, rd1, rd2 /* the region's digits: they give a spilled k-mer back */, spill_mod;
+    uint32_t& new_distinct;
+    unsigned long long* st;                                   // the kernel's stamps: [2] drains, [6] chunks
+    __device__ __forceinline__ unsigned long long now() const { return STAMP ? (unsigned long long)clock64() : 0ULL; }
+    __device__ __forceinline__ uint32_t next_slot(uint32_t s) const { return s + 1 == S ? 0 : s + 1; }
+    // +1: the count lives in the low cbits <= 32 bits of the word and the write-back's sweep rules a carry out of it out, so the add is a
+    // 32-bit one on the word's low half (a 64-bit LDS atomic costs about twice as much)
+    __device__ __forceinline__ void add1(uint32_t slot) const { (void)__hip_atomic_fetch_add(&reinterpret_cast<uint32_t*>(rk)[2 * slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+    __device__ __forceinline__ void spill_rem(uint64_t rem) const { spill_put(spill, spill_n, g.spill_cap, place_key_d(rd1, rd2, rem, g.pl)); }
+
+    // k-mers [sbeg, sbeg + n_run) of the level-2 buffer; the wave's first chunk is c_first, further ones come from *next_chunk
+    __device__ __forceinline__ void walk(const uint8_t* __restrict__ l2_buf, uint64_t sbeg, uint64_t n_run, uint64_t c_first, unsigned long long* next_chunk) {
+        uint32_t* rk32 = reinterpret_cast<uint32_t*>(rk);
+        uint32_t q_n = 0;                                     // entries in this wave's queue (wave-uniform)
+        // (Lanes that refill from the queue as they finish, a pass ending when fewer than 16 are busy: measured 141-152 ms against 142 -- the
+        // drains' cost is their dependent round trips, not their idle lanes.)
+        // One pass over up to 64 queue entries (taken from the tail).  Phase 1, one entry per lane: dependent probes with the
+        // claim, while at least 8 lanes are busy and for at most APK_LANE_PROBES probes.  Phase 2: what is left is on a long
+        // chain: the WAVE finishes such a k-mer, 64 consecutive slots per read.
+        auto drain_pass = [&](bool fin /* nothing will follow: leave no entry behind */) {
+            const unsigned long long t_dr = now();
+            struct DrainStamp { unsigned long long& acc; unsigned long long t0; bool on; __device__ ~DrainStamp() { if (on) acc += (unsigned long long)clock64() - t0; } } drain_stamp{st[2], t_dr, STAMP};
+            const uint32_t take = q_n < 64 ? q_n : 64;
+            q_n -= take;
+            bool live = lane < take;
+            uint64_t rem = 0; uint32_t slot = 0, budget = 0;
+            if (live) {
+                const unsigned long long e = wq[q_n + lane];
+                rem = e & rem_mask; slot = (uint32_t)(e >> APK_SLOT_SHIFT);
+                const uint32_t home = place_offset(rem, g.pl, S);
+                budget = S - (slot >= home ? slot - home : slot + S - home);       // probes left before the region has been walked once
+            }
+#pragma unroll 1
+            for (int rr = 0; rr < APK_LANE_PROBES; ++rr) {
+                const int busy = __popcll(__ballot(live));
+                if (busy == 0 || (busy < 8 && (fin || rr >= 4))) break;
+                if (live) {
+                    unsigned long long w = rk[slot];
+                    if (w == 0) {
+                        w = atomicCAS(&rk[slot], 0ULL, (unsigned long long)((rem << cb) | 1ULL));
+                        if (w == 0) { ++new_distinct; live = false; }                  // claimed, counted
+                    }
+                    if (live) {
+                        if ((w >> cb) == rem) { add1(slot); live = false; }
+                        else {
+                            slot = next_slot(slot);
+                            if (--budget == 0) { spill_rem(rem); live = false; }       // region full: direct path later
+                        }
+                    }
+                }
+            }
+            // the wave takes over what has had its APK_LANE_PROBES (all that is left, when nothing follows); the rest goes back
+            const bool lng = live && (fin || S - budget >= (uint32_t)(APK_LANE_PROBES + NR));
+            {
+                const bool back = live && !lng;
+                const unsigned long long m = __ballot(back);
+                if (m) {
+                    const uint32_t at = q_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+                    if (back) wq[at] = rem | ((unsigned long long)slot << APK_SLOT_SHIFT);
+                    q_n += (uint32_t)__popcll(m);
+                }
+            }
+            unsigned long long todo = __ballot(lng);
+#pragma unroll 1
+            while (todo) {
+                const int src = __ffsll((long long)todo) - 1;
+                todo &= todo - 1;
+                const unsigned long long ck = lane_value((uint64_t)rem, src);            // wave-uniform from here on
+                uint32_t cs = lane_value(slot, src);
+                int cbud = (int)lane_value(budget, src);
+#pragma unroll 1
+                for (;;) {
+                    uint32_t idx = cs + lane; if (idx >= S) idx -= S;                      // S >= 64 on this path (host-checked)
+                    const unsigned long long w = rk[idx];
+                    const unsigned long long mk = __ballot(w != 0 && (w >> cb) == ck), me = __ballot(w == 0);
+                    if (!(mk | me)) {                                                      // 64 foreign k-mers
+                        cbud -= 64; cs = cs + 64 >= S ? cs + 64 - S : cs + 64;
+                        if (cbud <= 0) { if (lane == 0) spill_rem(ck); break; }
+                        continue;
+                    }
+                    const int first = __ffsll((long long)(mk | me)) - 1;
+                    if (first >= cbud) { if (lane == 0) spill_rem(ck); break; }            // beyond the region's last unprobed slot
+                    if ((mk >> first) & 1) { if ((int)lane == first) add1(idx); break; }
+                    unsigned long long old = 0;                                            // a free slot comes first: claim it
+                    if ((int)lane == first) old = atomicCAS(&rk[idx], 0ULL, (unsigned long long)((ck << cb) | 1ULL));
+                    old = lane_value((uint64_t)old, first);
+                    if (old == 0) { if ((int)lane == first) ++new_distinct; break; }
+                    if ((old >> cb) == ck) { if ((int)lane == first) add1(idx); break; }   // the same k-mer got there first
+                    cbud -= first; cs = cs + first >= S ? cs + first - S : cs + first;     // someone else's k-mer landed there: go on from that slot
+                }
+            }
+        };
+
+        const uint64_t n_chunks = (n_run + CH - 1) / CH;         // chunk c = groups [64 c, 64 c + 64) of the run
+        const uint64_t n_grp = (n_run + 3) >> 2, g0 = sbeg >> 2;      // (runs start on group boundaries and end on "no item" padding)
+        u32x4 c_lo[UG], n_lo[UG];
+        typename HiGroup<HB>::type c_hi[UG], n_hi[UG];
+        bool c_in[UG], n_in[UG];                              // the lane's group lies inside the run
+        const L2Run<HB> run(l2_buf, g0);
+#pragma unroll
+        for (int gq = 0; gq < UG; ++gq) {
+            const uint64_t gi = (c_first * UG + gq) * 64 + lane;
+            c_in[gq] = gi < n_grp; c_hi[gq] = typename HiGroup<HB>::type{}; n_hi[gq] = typename HiGroup<HB>::type{};
+            run.load(c_in[gq] ? (uint32_t)gi : 0u, c_lo[gq], c_hi[gq]);
+        }
+        auto grab = [&]() -> uint64_t {
+            unsigned long long v = 0;
+            if (lane == 0) v = atomicAdd(next_chunk, 1ULL);
+            return lane_value((uint64_t)v, 0);
+        };
+        for (uint64_t c = c_first; c < n_chunks;) {
+            const uint64_t c_next = grab();
+#pragma unroll
+            for (int gq = 0; gq < UG; ++gq) {             // next chunk: in flight behind this one (unconditional loads from a clamped index)
+                const uint64_t gi = (c_next * UG + gq) * 64 + lane;
+                n_in[gq] = gi < n_grp;
+                run.load(n_in[gq] ? (uint32_t)gi : 0u, n_lo[gq], n_hi[gq]);
+            }
+            uint64_t rem[U];
+            uint32_t slot[U];
+            bool pend[U];                                     // k-mer u still to be placed (lane masks in SGPRs)
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int gq = u >> 2, q = u & 3;
+                rem[u] = ((uint64_t)hi_of_group<HB>(c_hi[gq], q) << 32) | (q == 0 ? c_lo[gq].x : q == 1 ? c_lo[gq].y : q == 2 ? c_lo[gq].z : c_lo[gq].w);
+                pend[u] = c_in[gq] && rem[u] != L2Fmt<HB>::NONE;
+                slot[u] = place_offset(rem[u], g.pl, S);
+                if (TEST_SPILL && spill_mod && pend[u] && __umulhi((uint32_t)(mix64(place_key_d(rd1, rd2, rem[u], g.pl)) >> 32), spill_mod) == 0) { spill_rem(rem[u]); pend[u] = false; }
+            }
+            // Probe rounds: U reads in flight, one wait; a match adds 1 and is done, a foreign k-mer moves on, a free slot is
+            // claimed (inline, or through the queue).  Lanes that are done take no part in the LDS operations.
+#pragma unroll
+            for (int rr = 0; rr < NR; ++rr) {
+                // every lane reads and adds whether its k-mer is still looking or not (a settled one reads its last slot and adds
+                // 0): an exec mask and a branch around each of the eight LDS operations of a round cost more issue slots than the
+                // operations, and issue is what bounds this walk (cycle stamps, round 4)
+                // (Two slots per round -- a slot and its successor in one ds_read2_b64, so that fewer k-mers go through the queue -- measured
+                // 167 ms per step against 154.5: the second compare costs every k-mer more than the drains it saves.)
+                unsigned long long seen[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) seen[u] = rk[slot[u]];
+                bool claim[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const bool hit = pend[u] && seen[u] != 0 && (seen[u] >> cb) == rem[u];
+                    (void)__hip_atomic_fetch_add(&rk32[2 * slot[u]], hit ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    pend[u] = pend[u] && !hit;
+                    claim[u] = pend[u] && seen[u] == 0;
+                    slot[u] = (pend[u] && !claim[u]) ? next_slot(slot[u]) : slot[u];
+                }
+                // INLINE_CLAIM (a table's first round: nearly every k-mer is new): claims right here, U CAS in flight
+                bool any_claim = false;
+#pragma unroll
+                for (int u = 0; u < U; ++u) any_claim = any_claim || claim[u];
+                if (INLINE_CLAIM && __any(any_claim)) {
+                    unsigned long long got[U];
+#pragma unroll
+                    for (int u = 0; u < U; ++u) { got[u] = 0; if (claim[u]) got[u] = atomicCAS(&rk[slot[u]], 0ULL, (unsigned long long)((rem[u] << cb) | 1ULL)); }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        if (claim[u]) {
+                            if (got[u] == 0) { ++new_distinct; pend[u] = false; }
+                            else if ((got[u] >> cb) == rem[u]) { add1(slot[u]); pend[u] = false; }
+                            else slot[u] = next_slot(slot[u]);                             // someone else's k-mer landed there
+                        }
+                    }
+                }
+            }
+            // survivors -> queue.  Normal case: one wave-wide prefix sum; a chunk with more survivors than the queue has room for
+            // goes in one k-mer column at a time.
+            // (ballots, not a shuffle scan: six dependent ds_bpermute -- ~200 cycles each on gfx950, tools/ubench_valu.hip -- were a
+            // third of a chunk's time; a ballot and a bit count are a handful of cycles)
+            unsigned long long pm_u[U];
+            uint32_t total = 0;
+#pragma unroll
+            for (int u = 0; u < U; ++u) { pm_u[u] = __ballot(pend[u]); total += (uint32_t)__popcll(pm_u[u]); }
+            if (UG > 1) while (q_n && q_n + total > qcap) drain_pass(false);    // (twice the k-mers per chunk: make room first)
+            if (q_n + total <= qcap) {
+                uint32_t at = q_n;
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (pend[u]) wq[at + __builtin_amdgcn_mbcnt_hi((uint32_t)(pm_u[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm_u[u], 0))] = rem[u] | ((unsigned long long)slot[u] << APK_SLOT_SHIFT);
+                    at += (uint32_t)__popcll(pm_u[u]);
+                }
+                q_n += total;
+            } else {
+                uint32_t pm = 0;
+#pragma unroll
+                for (int u = 0; u < U; ++u) pm |= pend[u] ? 1u << u : 0u;
+#pragma unroll 1
+                for (int it = 0; it < U; ++it) {
+                    const bool p = pm & 1;
+                    const unsigned long long m = __ballot(p);
+                    if (m) {
+                        while (q_n > qcap - 64) drain_pass(false);
+                        const uint32_t at = q_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+                        if (p) wq[at] = rem[0] | ((unsigned long long)slot[0] << APK_SLOT_SHIFT);
+                        q_n += (uint32_t)__popcll(m);
+                    }
+                    pm >>= 1;
+#pragma unroll
+                    for (int u = 0; u + 1 < U; ++u) { rem[u] = rem[u + 1]; slot[u] = slot[u + 1]; }
+                }
+            }
+            const bool last = c_next >= n_chunks;                     // the wave's last chunk empties the queue
+            while (q_n > (last ? 0u : 64u)) drain_pass(last);
+#pragma unroll
+            for (int gq = 0; gq < UG; ++gq) { c_lo[gq] = n_lo[gq]; c_hi[gq] = n_hi[gq]; c_in[gq] = n_in[gq]; }
+            c = c_next;
+            if (STAMP) st[6] += 1;
+        }
+    }
+};
+
 template <int BLOCK, int KP /* 16-byte loads per lane that cover a region: two slots each */, int HB, bool INLINE_CLAIM = false, bool TEST_SPILL = false,
           bool PF = true /* the next region travels from HBM into registers behind the walk of this one (2 KP VGPRs across the walk); false: loaded when its turn comes -- for shapes with a second workgroup on the CU to cover that */,
           int NR = 3 /* probe rounds before a k-mer goes to the queue */,
@@ -1719,10 +1948,9 @@ k_p3_apply_pk(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const u
               uint32_t zero_fill /* the table's first sweep (katgpu_table::zero_from): its slots hold whatever the memory held -- a region starts from zeros
                                     in LDS instead of being loaded, and EVERY region of the launch is visited and written, a run or not */) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    constexpr int NW = BLOCK / 64, U = 4 * UG;
-    constexpr uint32_t CH = 64 * U;
+    constexpr int NW = BLOCK / 64;
     const uint32_t S = g.S, cb = g.cbits;                     // S % 4 == 0 (host-checked)
-    const uint64_t cmask = pk_cmask(cb), half = pk_half(cb), rem_mask = (1ULL << APK_SLOT_SHIFT) - 1;
+    const uint64_t cmask = pk_cmask(cb), half = pk_half(cb);
     unsigned long long* rk = reinterpret_cast<unsigned long long*>(lds_raw);
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     unsigned long long* wq = rk + S + (size_t)wave * qcap;
@@ -1746,11 +1974,6 @@ k_p3_apply_pk(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const u
 #pragma unroll
         for (int u = 0; u < KP; ++u) { const uint32_t i = (u * BLOCK + tid) * 2; kq[u] = *reinterpret_cast<const u32x4*>(t.keys + base + (i < S ? i : 0)); }    // clamped, unconditional: stays in registers
     };
-    auto next_slot = [&](uint32_t s) -> uint32_t { return s + 1 == S ? 0 : s + 1; };
-    // +1: the count lives in the low cbits <= 32 bits of the word and the sweep below rules a carry out of it out, so the add is a
-    // 32-bit one on the word's low half (a 64-bit LDS atomic costs about twice as much)
-    uint32_t* rk32 = reinterpret_cast<uint32_t*>(rk);
-    auto add1 = [&](uint32_t slot) { (void)__hip_atomic_fetch_add(&rk32[2 * slot], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
 
     unsigned long long st[7] = {0, 0, 0, 0, 0, 0, 0};
     auto now = [&]() -> unsigned long long { return STAMP ? (unsigned long long)clock64() : 0ULL; };
@@ -1772,7 +1995,6 @@ k_p3_apply_pk(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const u
         const uint32_t rn = next_region(r + gridDim.x);
         // what spilling a k-mer (region full, test hook) needs: the region's digits give the k-mer back
         const uint32_t rd1 = r >> g.l2, rd2 = r & (g.P2 - 1);
-        auto spill_rem = [&](uint64_t rem) { spill_put(spill, spill_n, g.spill_cap, place_key_d(rd1, rd2, rem, g.pl)); };
 
         for (uint64_t sbeg = beg; sbeg < end; sbeg += seg_len) {            // one segment, normally
             const uint64_t n_run = (end - sbeg < seg_len ? end - sbeg : seg_len);
@@ -1781,205 +2003,10 @@ k_p3_apply_pk(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const u
             const unsigned long long t_walk = now();
             st[0] += t_walk - t_fill;
 
-            // ---- the walk ----
-            uint32_t q_n = 0;                                     // entries in this wave's queue (wave-uniform)
-            // (Lanes that refill from the queue as they finish, a pass ending when fewer than 16 are busy: measured 141-152 ms against 142 -- the
-            // drains' cost is their dependent round trips, not their idle lanes.)
-            // One pass over up to 64 queue entries (taken from the tail).  Phase 1, one entry per lane: dependent probes with the
-            // claim, while at least 8 lanes are busy and for at most APK_LANE_PROBES probes.  Phase 2: what is left is on a long
-            // chain: the WAVE finishes such a k-mer, 64 consecutive slots per read.
-            auto drain_pass = [&](bool fin /* nothing will follow: leave no entry behind */) {
-                const unsigned long long t_dr = now();
-                struct DrainStamp { unsigned long long& acc; unsigned long long t0; bool on; __device__ ~DrainStamp() { if (on) acc += (unsigned long long)clock64() - t0; } } drain_stamp{st[2], t_dr, STAMP};
-                const uint32_t take = q_n < 64 ? q_n : 64;
-                q_n -= take;
-                bool live = lane < take;
-                uint64_t rem = 0; uint32_t slot = 0, budget = 0;
-                if (live) {
-                    const unsigned long long e = wq[q_n + lane];
-                    rem = e & rem_mask; slot = (uint32_t)(e >> APK_SLOT_SHIFT);
-                    const uint32_t home = place_offset(rem, g.pl, S);
-                    budget = S - (slot >= home ? slot - home : slot + S - home);       // probes left before the region has been walked once
-                }
-#pragma unroll 1
-                for (int rr = 0; rr < APK_LANE_PROBES; ++rr) {
-                    const int busy = __popcll(__ballot(live));
-                    if (busy == 0 || (busy < 8 && (fin || rr >= 4))) break;
-                    if (live) {
-                        unsigned long long w = rk[slot];
-                        if (w == 0) {
-                            w = atomicCAS(&rk[slot], 0ULL, (unsigned long long)((rem << cb) | 1ULL));
-                            if (w == 0) { ++new_distinct; live = false; }                  // claimed, counted
-                        }
-                        if (live) {
-                            if ((w >> cb) == rem) { add1(slot); live = false; }
-                            else {
-                                slot = next_slot(slot);
-                                if (--budget == 0) { spill_rem(rem); live = false; }       // region full: direct path later
-                            }
-                        }
-                    }
-                }
-                // the wave takes over what has had its APK_LANE_PROBES (all that is left, when nothing follows); the rest goes back
-                const bool lng = live && (fin || S - budget >= (uint32_t)(APK_LANE_PROBES + NR));
-                {
-                    const bool back = live && !lng;
-                    const unsigned long long m = __ballot(back);
-                    if (m) {
-                        const uint32_t at = q_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-                        if (back) wq[at] = rem | ((unsigned long long)slot << APK_SLOT_SHIFT);
-                        q_n += (uint32_t)__popcll(m);
-                    }
-                }
-                unsigned long long todo = __ballot(lng);
-#pragma unroll 1
-                while (todo) {
-                    const int src = __ffsll((long long)todo) - 1;
-                    todo &= todo - 1;
-                    const unsigned long long ck = lane_value((uint64_t)rem, src);            // wave-uniform from here on
-                    uint32_t cs = lane_value(slot, src);
-                    int cbud = (int)lane_value(budget, src);
-#pragma unroll 1
-                    for (;;) {
-                        uint32_t idx = cs + lane; if (idx >= S) idx -= S;                      // S >= 64 on this path (host-checked)
-                        const unsigned long long w = rk[idx];
-                        const unsigned long long mk = __ballot(w != 0 && (w >> cb) == ck), me = __ballot(w == 0);
-                        if (!(mk | me)) {                                                      // 64 foreign k-mers
-                            cbud -= 64; cs = cs + 64 >= S ? cs + 64 - S : cs + 64;
-                            if (cbud <= 0) { if (lane == 0) spill_rem(ck); break; }
-                            continue;
-                        }
-                        const int first = __ffsll((long long)(mk | me)) - 1;
-                        if (first >= cbud) { if (lane == 0) spill_rem(ck); break; }            // beyond the region's last unprobed slot
-                        if ((mk >> first) & 1) { if ((int)lane == first) add1(idx); break; }
-                        unsigned long long old = 0;                                            // a free slot comes first: claim it
-                        if ((int)lane == first) old = atomicCAS(&rk[idx], 0ULL, (unsigned long long)((ck << cb) | 1ULL));
-                        old = lane_value((uint64_t)old, first);
-                        if (old == 0) { if ((int)lane == first) ++new_distinct; break; }
-                        if ((old >> cb) == ck) { if ((int)lane == first) add1(idx); break; }   // the same k-mer got there first
-                        cbud -= first; cs = cs + first >= S ? cs + first - S : cs + first;     // someone else's k-mer landed there: go on from that slot
-                    }
-                }
-            };
-
-            const uint64_t n_chunks = (n_run + CH - 1) / CH;         // chunk c = groups [64 c, 64 c + 64) of the run
-            const uint64_t n_grp = (n_run + 3) >> 2, g0 = sbeg >> 2;      // (runs start on group boundaries and end on "no item" padding)
-            u32x4 c_lo[UG], n_lo[UG];
-            typename HiGroup<HB>::type c_hi[UG], n_hi[UG];
-            bool c_in[UG], n_in[UG];                              // the lane's group lies inside the run
-            const L2Run<HB> run(l2_buf, g0);
-#pragma unroll
-            for (int gq = 0; gq < UG; ++gq) {
-                const uint64_t gi = ((uint64_t)wave * UG + gq) * 64 + lane;
-                c_in[gq] = gi < n_grp; c_hi[gq] = typename HiGroup<HB>::type{}; n_hi[gq] = typename HiGroup<HB>::type{};
-                run.load(c_in[gq] ? (uint32_t)gi : 0u, c_lo[gq], c_hi[gq]);
-            }
-            auto grab = [&]() -> uint64_t {
-                unsigned long long v = 0;
-                if (lane == 0) v = atomicAdd(&s_next_chunk, 1ULL);
-                return lane_value((uint64_t)v, 0);
-            };
-            for (uint64_t c = wave; c < n_chunks;) {
-                const uint64_t c_next = grab();
-#pragma unroll
-                for (int gq = 0; gq < UG; ++gq) {             // next chunk: in flight behind this one (unconditional loads from a clamped index)
-                    const uint64_t gi = (c_next * UG + gq) * 64 + lane;
-                    n_in[gq] = gi < n_grp;
-                    run.load(n_in[gq] ? (uint32_t)gi : 0u, n_lo[gq], n_hi[gq]);
-                }
-                uint64_t rem[U];
-                uint32_t slot[U];
-                bool pend[U];                                     // k-mer u still to be placed (lane masks in SGPRs)
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int gq = u >> 2, q = u & 3;
-                    rem[u] = ((uint64_t)hi_of_group<HB>(c_hi[gq], q) << 32) | (q == 0 ? c_lo[gq].x : q == 1 ? c_lo[gq].y : q == 2 ? c_lo[gq].z : c_lo[gq].w);
-                    pend[u] = c_in[gq] && rem[u] != L2Fmt<HB>::NONE;
-                    slot[u] = place_offset(rem[u], g.pl, S);
-                    if (TEST_SPILL && spill_mod && pend[u] && __umulhi((uint32_t)(mix64(place_key_d(rd1, rd2, rem[u], g.pl)) >> 32), spill_mod) == 0) { spill_rem(rem[u]); pend[u] = false; }
-                }
-                // Probe rounds: U reads in flight, one wait; a match adds 1 and is done, a foreign k-mer moves on, a free slot is
-                // claimed (inline, or through the queue).  Lanes that are done take no part in the LDS operations.
-#pragma unroll
-                for (int rr = 0; rr < NR; ++rr) {
-                    // every lane reads and adds whether its k-mer is still looking or not (a settled one reads its last slot and adds
-                    // 0): an exec mask and a branch around each of the eight LDS operations of a round cost more issue slots than the
-                    // operations, and issue is what bounds this walk (cycle stamps, round 4)
-                    // (Two slots per round -- a slot and its successor in one ds_read2_b64, so that fewer k-mers go through the queue -- measured
-                    // 167 ms per step against 154.5: the second compare costs every k-mer more than the drains it saves.)
-                    unsigned long long seen[U];
-#pragma unroll
-                    for (int u = 0; u < U; ++u) seen[u] = rk[slot[u]];
-                    bool claim[U];
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const bool hit = pend[u] && seen[u] != 0 && (seen[u] >> cb) == rem[u];
-                        (void)__hip_atomic_fetch_add(&rk32[2 * slot[u]], hit ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        pend[u] = pend[u] && !hit;
-                        claim[u] = pend[u] && seen[u] == 0;
-                        slot[u] = (pend[u] && !claim[u]) ? next_slot(slot[u]) : slot[u];
-                    }
-                    // INLINE_CLAIM (a table's first round: nearly every k-mer is new): claims right here, U CAS in flight
-                    bool any_claim = false;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) any_claim = any_claim || claim[u];
-                    if (INLINE_CLAIM && __any(any_claim)) {
-                        unsigned long long got[U];
-#pragma unroll
-                        for (int u = 0; u < U; ++u) { got[u] = 0; if (claim[u]) got[u] = atomicCAS(&rk[slot[u]], 0ULL, (unsigned long long)((rem[u] << cb) | 1ULL)); }
-#pragma unroll
-                        for (int u = 0; u < U; ++u) {
-                            if (claim[u]) {
-                                if (got[u] == 0) { ++new_distinct; pend[u] = false; }
-                                else if ((got[u] >> cb) == rem[u]) { add1(slot[u]); pend[u] = false; }
-                                else slot[u] = next_slot(slot[u]);                             // someone else's k-mer landed there
-                            }
-                        }
-                    }
-                }
-                // survivors -> queue.  Normal case: one wave-wide prefix sum; a chunk with more survivors than the queue has room for
-                // goes in one k-mer column at a time.
-                // (ballots, not a shuffle scan: six dependent ds_bpermute -- ~200 cycles each on gfx950, tools/ubench_valu.hip -- were a
-                // third of a chunk's time; a ballot and a bit count are a handful of cycles)
-                unsigned long long pm_u[U];
-                uint32_t total = 0;
-#pragma unroll
-                for (int u = 0; u < U; ++u) { pm_u[u] = __ballot(pend[u]); total += (uint32_t)__popcll(pm_u[u]); }
-                if (UG > 1) while (q_n && q_n + total > qcap) drain_pass(false);    // (twice the k-mers per chunk: make room first)
-                if (q_n + total <= qcap) {
-                    uint32_t at = q_n;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        if (pend[u]) wq[at + __builtin_amdgcn_mbcnt_hi((uint32_t)(pm_u[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)pm_u[u], 0))] = rem[u] | ((unsigned long long)slot[u] << APK_SLOT_SHIFT);
-                        at += (uint32_t)__popcll(pm_u[u]);
-                    }
-                    q_n += total;
-                } else {
-                    uint32_t pm = 0;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) pm |= pend[u] ? 1u << u : 0u;
-#pragma unroll 1
-                    for (int it = 0; it < U; ++it) {
-                        const bool p = pm & 1;
-                        const unsigned long long m = __ballot(p);
-                        if (m) {
-                            while (q_n > qcap - 64) drain_pass(false);
-                            const uint32_t at = q_n + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-                            if (p) wq[at] = rem[0] | ((unsigned long long)slot[0] << APK_SLOT_SHIFT);
-                            q_n += (uint32_t)__popcll(m);
-                        }
-                        pm >>= 1;
-#pragma unroll
-                        for (int u = 0; u + 1 < U; ++u) { rem[u] = rem[u + 1]; slot[u] = slot[u + 1]; }
-                    }
-                }
-                const bool last = c_next >= n_chunks;                     // the wave's last chunk empties the queue
-                while (q_n > (last ? 0u : 64u)) drain_pass(last);
-#pragma unroll
-                for (int gq = 0; gq < UG; ++gq) { c_lo[gq] = n_lo[gq]; c_hi[gq] = n_hi[gq]; c_in[gq] = n_in[gq]; }
-                c = c_next;
-                if (STAMP) st[6] += 1;
-            }
+            // ---- the walk (ApkWalk above) ----
+            ApkWalk<HB, INLINE_CLAIM, TEST_SPILL, NR, STAMP, UG> w{.g = g, .rk = rk, .wq = wq, .spill = spill, .spill_n = spill_n, .S = S, .cb = cb, .qcap = qcap, .lane = lane,
+                                                                   .rd1 = rd1, .rd2 = rd2, .spill_mod = spill_mod, .new_distinct = new_distinct, .st = st};      // (by name: most members are uint32_t)
+            w.walk(l2_buf, sbeg, n_run, wave, &s_next_chunk);
             const unsigned long long t_post = now();
             st[1] += t_post - t_walk;
             // ---- back to the invariant (kg_device.hpp: table_add_pk): a slot counts 1 .. half, the rest goes to the side table.  The walk
