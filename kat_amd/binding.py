@@ -315,6 +315,25 @@ def jf_write_records_wide(path, k, canonical, keys_hi, keys_lo, counts):
         raise KatGpuError(rc, L.katgpu_jf_last_error().decode(errors="replace"))
 
 
+def _record_args(bases, rec_start, rec_len):
+    """What the per-record host forms take: the bases as a u8 array, the records' starts and lengths as u64 arrays of one size."""
+    if isinstance(bases, str):
+        bases = bases.encode()
+    b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
+    st, ln = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_len, np.uint64)
+    assert st.size == ln.size
+    return b, st, ln
+
+
+def _take_text(L, p, off):
+    """(text, offsets) of a text host form: the off[-1] bytes behind p as bytes, the library's buffer given back."""
+    try:
+        text = C.string_at(p, int(off[-1]))
+    finally:
+        L.katgpu_free_host(p)
+    return text, off
+
+
 class ScratchView:
     """nbytes of device memory owned by the engine, exposed through the CUDA array interface (uint8)."""
 
@@ -447,19 +466,11 @@ class Engine:
         of each of its windows of k bases, "-0.1" for a window with a byte outside ACGTacgt, a space between them and a newline behind
         the last, "0.0\\n" for a record without a window; record r's text is text[offsets[r]:offsets[r + 1]], offsets a u64 array of
         n_rec + 1 entries.  No table: the text follows from the bases."""
-        if isinstance(bases, str):
-            bases = bases.encode()
-        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
-        st, ln = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_len, np.uint64)
-        assert st.size == ln.size
+        b, st, ln = _record_args(bases, rec_start, rec_len)
         p = C.c_void_p()
         off = np.zeros(st.size + 1, np.uint64)
         self._chk(self.L.katgpu_record_gc_text_host(self.h, k, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size, C.byref(p), off.ctypes.data))
-        try:
-            text = C.string_at(p, int(off[-1]))
-        finally:
-            self.L.katgpu_free_host(p)
-        return text, off
+        return _take_text(self.L, p, off)
 
     def record_gc_text_device(self, k, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, dev_text, cap, dev_text_off):
         """Device-resident form: DeviceBuffers or raw device addresses; `dev_text` takes `cap` bytes (None with cap 0: size only),
@@ -596,11 +607,7 @@ class Table:
 
     def seq_hits(self, bases, rec_start, rec_len, canonicalise=None):
         """Per-record hit counts (katgpu_table_seq_hits_host): u64[n_rec], the windows of each record that are valid and found."""
-        if isinstance(bases, str):
-            bases = bases.encode()
-        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
-        st, ln = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_len, np.uint64)
-        assert st.size == ln.size
+        b, st, ln = _record_args(bases, rec_start, rec_len)
         out = np.zeros(st.size, np.uint64)
         canon = self.canonical if canonicalise is None else canonicalise
         self.engine._chk(self.engine.L.katgpu_table_seq_hits_host(self.h, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size,
@@ -616,11 +623,7 @@ class Table:
     def record_stats(self, bases, rec_start, rec_len, canonicalise=None):
         """Per-record coverage statistics (katgpu_table_record_stats_host): a structured array (RECORD_STATS) of n_rec entries with the
         fields sum, median, non_zero, invalid, gc_bases, n_bases."""
-        if isinstance(bases, str):
-            bases = bases.encode()
-        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
-        st, ln = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_len, np.uint64)
-        assert st.size == ln.size
+        b, st, ln = _record_args(bases, rec_start, rec_len)
         out = np.zeros(st.size, RECORD_STATS)
         canon = self.canonical if canonicalise is None else canonicalise
         self.engine._chk(self.engine.L.katgpu_table_record_stats_host(self.h, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size,
@@ -637,11 +640,7 @@ class Table:
         """Count-range regions of records (katgpu_table_record_regions_host).  `ranges`: one or two (min, max) pairs, max == 0 for no
         upper bound.  One (m, 3) u64 array per range: (record, start, stop) of every maximal run of windows whose count lies in the
         range, start and stop counted from the record's first window, sorted by (record, start)."""
-        if isinstance(bases, str):
-            bases = bases.encode()
-        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
-        st, ln = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_len, np.uint64)
-        assert st.size == ln.size
+        b, st, ln = _record_args(bases, rec_start, rec_len)
         rg = np.ascontiguousarray(ranges, np.uint64).reshape(-1, 2)
         canon = self.canonical if canonicalise is None else canonicalise
         p = C.c_void_p()
@@ -671,21 +670,13 @@ class Table:
         """The -counts.cvg text of records (katgpu_table_record_cvg_text_host): (text, offsets).  A record's text is its windows' counts
         in decimal, a space between them and a newline behind the last, "0\\n" for a record without a window; record r's text is
         text[offsets[r]:offsets[r + 1]], offsets a u64 array of n_rec + 1 entries."""
-        if isinstance(bases, str):
-            bases = bases.encode()
-        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
-        st, ln = np.ascontiguousarray(rec_start, np.uint64), np.ascontiguousarray(rec_len, np.uint64)
-        assert st.size == ln.size
+        b, st, ln = _record_args(bases, rec_start, rec_len)
         canon = self.canonical if canonicalise is None else canonicalise
         p = C.c_void_p()
         off = np.zeros(st.size + 1, np.uint64)
         self.engine._chk(self.engine.L.katgpu_table_record_cvg_text_host(self.h, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size,
                                                                          int(bool(canon)), C.byref(p), off.ctypes.data))
-        try:
-            text = C.string_at(p, int(off[-1]))
-        finally:
-            self.engine.L.katgpu_free_host(p)
-        return text, off
+        return _take_text(self.engine.L, p, off)
 
     def record_cvg_text_device(self, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, dev_text, cap, dev_text_off, canonicalise=None):
         """Device-resident form: DeviceBuffers or raw device addresses; `dev_text` takes `cap` bytes (None with cap 0: size only),
@@ -990,11 +981,7 @@ class Comm:
     def seq_hits_gathered(self, table, bases, starts, lens, canonicalise=None):
         """Collective, after exchange_merge: Table.seq_hits of the records (the same bases, starts and lengths on every rank) against
         the union of the ranks' tables.  Rank 0 gets the u64[n_rec] array, the other ranks None."""
-        if isinstance(bases, str):
-            bases = bases.encode()
-        b = np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else np.ascontiguousarray(bases, np.uint8)
-        st, ln = np.ascontiguousarray(starts, np.uint64), np.ascontiguousarray(lens, np.uint64)
-        assert st.size == ln.size
+        b, st, ln = _record_args(bases, starts, lens)
         out = np.zeros(st.size, np.uint64) if self.rank == 0 else None
         canon = table.canonical if canonicalise is None else canonicalise
         self.engine._chk(self.engine.L.katgpu_table_seq_hits_gathered_host(self.h, table.h, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size,

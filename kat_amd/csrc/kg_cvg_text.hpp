@@ -68,17 +68,21 @@ __device__ __forceinline__ void cvg_walk(const uint64_t* __restrict__ rec_start,
     }
 }
 
-// K18.  A tile is CT_TILE positions, a lane's share CT_LANE consecutive ones; n_tiles covers positions 0 .. n.
+// The frame of the text kernels (K18, and K20 of kg_gc_text.hpp).  A tile is CT_TILE positions, a lane's share CT_LANE consecutive ones;
+// n_tiles covers positions 0 .. n.  s_w, s_r: CT_BLOCK / 64 and 2 words of the kernel's LDS.
 // WRITE == false: tile_sum[tile] = bytes of the windows that start in the tile.
 // WRITE == true:  tile_sum holds K19's offsets.  Byte o of the text goes to text[o] when o < cap; text_off[r] = text_base + the byte
 //                 record r's text starts at, text_off[n_rec] = text_base + the total.
-template <bool WRITE>
-__global__ void __launch_bounds__(CT_BLOCK)
-k_cvg_tiles(const uint64_t* __restrict__ counts, uint64_t n, uint32_t k, const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len,
-            uint64_t n_rec, uint64_t n_tiles, unsigned long long* __restrict__ tile_sum, const uint64_t* __restrict__ extra,
-            const unsigned long long* __restrict__ totals, uint64_t text_base, uint8_t* __restrict__ text, uint64_t cap, uint64_t* __restrict__ text_off) {
-    __shared__ uint32_t s_w[CT_BLOCK / 64];
-    __shared__ uint64_t s_r[2];
+// Src says what a window's string is: stage(c0, tid) before the tile's first barrier and lane(off) behind it make ready what the lane's
+// windows are read from; width(pos) is the length of the string of the window at pos; emit(pos, o, put) writes it from byte o on and
+// returns that length (the frame puts the separator behind it); Src::EMPTY is the text of a record without a window.
+template <typename Src> constexpr uint32_t text_empty_bytes() { return sizeof(Src::EMPTY) - 1; }     // K19's empty_bytes
+
+template <bool WRITE, typename Src>
+__device__ __forceinline__ void text_tiles(Src& src, uint32_t* s_w, uint64_t* s_r, uint64_t n, uint32_t k, const uint64_t* __restrict__ rec_start,
+                                           const uint64_t* __restrict__ rec_len, uint64_t n_rec, uint64_t n_tiles, unsigned long long* __restrict__ tile_sum,
+                                           const uint64_t* __restrict__ extra, const unsigned long long* __restrict__ totals, uint64_t text_base,
+                                           uint8_t* __restrict__ text, uint64_t cap, uint64_t* __restrict__ text_off) {
     const uint32_t tid = threadIdx.x;
     if (WRITE && blockIdx.x == 0 && tid == 0) text_off[n_rec] = text_base + totals[0] + totals[1];
 
@@ -89,15 +93,17 @@ k_cvg_tiles(const uint64_t* __restrict__ counts, uint64_t n, uint32_t k, const u
             s_r[0] = lo;
             s_r[1] = hits_lower_bound(rec_start, rec_len, lo, n_rec, c0 + CT_TILE, false);
         }
+        const uint64_t off = c0 + (uint64_t)tid * CT_LANE;
+        src.stage(c0, tid);
         __syncthreads();
         const uint64_t r_lo = s_r[0], r_hi = s_r[1];
-        const uint64_t off = c0 + (uint64_t)tid * CT_LANE;
+        src.lane(off);
 
         uint32_t sum = 0;
         cvg_walk(rec_start, rec_len, n_rec, r_lo, r_hi, off, n, k, [](uint64_t, uint64_t) {},
-                 [&](uint64_t, uint64_t pos, bool) { sum += cvg_digits(counts[pos]) + 1; });
+                 [&](uint64_t, uint64_t pos, bool) { sum += src.width(pos) + 1; });
         uint32_t total;
-        const uint32_t before = rg_block_before(sum, s_w, total);    // (its barriers also keep s_r for the slowest thread)
+        const uint32_t before = rg_block_before(sum, s_w, total);    // (its barriers also keep s_r and what Src staged for the slowest thread)
         if constexpr (!WRITE) {
             if (tid == 0) tile_sum[tile] = total;
         } else {
@@ -107,25 +113,54 @@ k_cvg_tiles(const uint64_t* __restrict__ counts, uint64_t n, uint32_t k, const u
                      [&](uint64_t r, uint64_t len) {
                          const uint64_t o = at + extra[r];
                          text_off[r] = text_base + o;
-                         if (len < k) { put(o, '0'); put(o + 1, '\n'); }
+                         if (len < k) {
+#pragma unroll
+                             for (uint32_t i = 0; i < text_empty_bytes<Src>(); ++i) put(o + i, Src::EMPTY[i]);
+                         }
                      },
                      [&](uint64_t r, uint64_t pos, bool last) {
-                         const uint64_t c = counts[pos];
-                         const uint32_t d = cvg_digits(c);
                          const uint64_t o = at + extra[r];
-                         uint64_t p = o + d;                         // the separator's place; the digits from the last one down
-                         put(p, last ? '\n' : ' ');
-                         if (c >> 32 == 0) {
-                             uint32_t v = (uint32_t)c;
-                             do { put(--p, (char)('0' + v % 10)); v /= 10; } while (v);
-                         } else {
-                             uint64_t v = c;
-                             do { put(--p, (char)('0' + v % 10)); v /= 10; } while (v);
-                         }
+                         const uint32_t d = src.emit(pos, o, put);
+                         put(o + d, last ? '\n' : ' ');
                          at += d + 1;
                      });
         }
     }
+}
+
+// the windows of the .cvg text: a count in decimal, read from k_profile's array
+struct CvgWindows {
+    static constexpr char EMPTY[] = "0\n";
+    const uint64_t* __restrict__ counts;
+    __device__ __forceinline__ void stage(uint64_t, uint32_t) const {}
+    __device__ __forceinline__ void lane(uint64_t) const {}
+    __device__ __forceinline__ uint32_t width(uint64_t pos) const { return cvg_digits(counts[pos]); }
+    template <typename Put>
+    __device__ __forceinline__ uint32_t emit(uint64_t pos, uint64_t o, Put&& put) const {
+        const uint64_t c = counts[pos];
+        const uint32_t d = cvg_digits(c);
+        uint64_t p = o + d;                                          // the separator's place; the digits from the last one down
+        if (c >> 32 == 0) {
+            uint32_t v = (uint32_t)c;
+            do { put(--p, (char)('0' + v % 10)); v /= 10; } while (v);
+        } else {
+            uint64_t v = c;
+            do { put(--p, (char)('0' + v % 10)); v /= 10; } while (v);
+        }
+        return d;
+    }
+};
+
+// K18
+template <bool WRITE>
+__global__ void __launch_bounds__(CT_BLOCK)
+k_cvg_tiles(const uint64_t* __restrict__ counts, uint64_t n, uint32_t k, const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len,
+            uint64_t n_rec, uint64_t n_tiles, unsigned long long* __restrict__ tile_sum, const uint64_t* __restrict__ extra,
+            const unsigned long long* __restrict__ totals, uint64_t text_base, uint8_t* __restrict__ text, uint64_t cap, uint64_t* __restrict__ text_off) {
+    __shared__ uint32_t s_w[CT_BLOCK / 64];
+    __shared__ uint64_t s_r[2];
+    CvgWindows src{counts};
+    text_tiles<WRITE>(src, s_w, s_r, n, k, rec_start, rec_len, n_rec, n_tiles, tile_sum, extra, totals, text_base, text, cap, text_off);
 }
 
 // K19.  Block 0: the tile sums become, in place, the offset of each tile's first byte among the windows' bytes.  Block 1: extra[r] =

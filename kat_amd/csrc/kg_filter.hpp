@@ -4,8 +4,9 @@
 //  K10 k_seq_hits              per-record number of windows found in a table                              (replaces FilterSeq::getProfile + the
 //                                                                                                          nbFound loop of processSeq)
 //      k_seq_hits_owned        the same over the windows whose k-mer this rank owns; k_hits_sum (kg_query_kernels.hpp) adds the ranks' arrays on rank 0
-// Both units that launch these include this header (kg_records.hip: K9; kg_query.hip: K10), so it holds templates only: a kernel that is
-// no template would be compiled into the unit that does not launch it.  From kg_kernels.hpp it takes Chunk and COUNT_BLOCK.
+// Both units that launch these include this header (kg_records.hip: K9; kg_query.hip: K10), and kg_per_record.hip's record headers take
+// the record search from it (hits_lower_bound), so it holds templates only: a kernel that is no template would be compiled into the
+// units that do not launch it.  From kg_kernels.hpp it takes Chunk and COUNT_BLOCK.
 // K9 rebuilds rather than clears: probing is linear inside a region (kg_device.hpp: Probe), so clearing a slot in place would cut the
 // probe chain of every k-mer placed after it.  The keep / drop tables are made with the source's region grid, so a k-mer lands in the
 // region of the same index it came from (a subset of a region's k-mers never probes further than the full set did) and the blocks that

@@ -15,7 +15,8 @@
 // of each that its CT_LANE positions and their k - 1 followers need, and window j is a shift, a mask of k bits, a popcount and a test.
 // So, unlike the .cvg text, nothing per position is written to device memory between the sizing pass and the writing pass: each pass
 // reads the bases again, 2 bytes per position between them, against the 4.5-5 bytes per position of text that are written.
-// The walk along the records, the sums along the block, the offsets and the tile geometry are those of kg_cvg_text.hpp.
+// The walk along the records, the sums along the block, the offsets and the tile geometry are those of kg_cvg_text.hpp: its text_tiles
+// is the whole frame of K20, and what is written here is the window's string (GcWindows).
 #pragma once
 #include "kg_cvg_text.hpp"
 
@@ -40,10 +41,55 @@ __device__ __forceinline__ uint32_t gc_bits16(const uint32_t w[4]) {
     return m;
 }
 
-// K20.  A tile is CT_TILE positions, a lane's share CT_LANE consecutive ones; n_tiles covers positions 0 .. n.
-// WRITE == false: tile_sum[tile] = bytes of the windows that start in the tile.
-// WRITE == true:  tile_sum holds K19's offsets.  Byte o of the text goes to text[o] when o < cap; text_off[r] = text_base + the byte
-//                 record r's text starts at, text_off[n_rec] = text_base + the total.
+// the windows of the .gc text (text_tiles' Src, kg_cvg_text.hpp): one of k + 2 strings, told from the two masks of the tile in LDS
+template <bool ALIGNED>
+struct GcWindows {
+    static constexpr char EMPTY[] = "0.0\n";
+    const uint8_t* __restrict__ bases;
+    uint64_t n;
+    uint32_t k;
+    uint64_t k_mask;                                                 // k ones
+    const uint64_t* s_str;                                          // GC_MAX_STRINGS entries
+    uint16_t *s_gc, *s_bad;                                          // CT_BLOCK + GC_HALO halfwords each
+    uint64_t off, gc_lo, bad_lo, gc_hi, bad_hi;                      // lane(): its first position and its 80 bits of each mask
+
+    __device__ __forceinline__ void stage16(uint32_t h, uint64_t at) const {     // 16 bytes from `at` to halfword h of both masks
+        uint32_t w[4], code, bad;
+        load16<ALIGNED>(bases, n, at, w);                            // (past n: 'N')
+        encode16(w, code, bad);
+        s_gc[h] = (uint16_t)gc_bits16(w);
+        s_bad[h] = (uint16_t)(__brev(bad) >> 16);                    // encode16 has the first byte on top
+    }
+    __device__ __forceinline__ void stage(uint64_t c0, uint32_t tid) const {
+        for (uint32_t h = tid; h < CT_BLOCK + GC_HALO; h += CT_BLOCK) stage16(h, c0 + (uint64_t)h * CT_LANE);   // (the first GC_HALO lanes: the halo too)
+    }
+    // positions off .. off + 15 and the k - 1 <= 62 behind them: 78 bits of 80
+    __device__ __forceinline__ void lane(uint64_t off_) {
+        const uint32_t tid = threadIdx.x;
+        off = off_;
+        gc_lo = (uint64_t)s_gc[tid] | (uint64_t)s_gc[tid + 1] << 16 | (uint64_t)s_gc[tid + 2] << 32 | (uint64_t)s_gc[tid + 3] << 48;
+        bad_lo = (uint64_t)s_bad[tid] | (uint64_t)s_bad[tid + 1] << 16 | (uint64_t)s_bad[tid + 2] << 32 | (uint64_t)s_bad[tid + 3] << 48;
+        gc_hi = s_gc[tid + 4]; bad_hi = s_bad[tid + 4];
+    }
+    __device__ __forceinline__ uint64_t string_of(uint64_t pos) const {          // the table entry of the window that starts at pos
+        const uint32_t j = (uint32_t)(pos - off);
+        const uint64_t b = ((bad_lo >> j) | (j ? bad_hi << (64 - j) : 0)) & k_mask;
+        const uint64_t g = ((gc_lo >> j) | (j ? gc_hi << (64 - j) : 0)) & k_mask;
+        return s_str[b ? k + 1 : (uint32_t)__popcll(g)];
+    }
+    __device__ __forceinline__ uint32_t width(uint64_t pos) const { return (uint32_t)(string_of(pos) >> 56); }
+    template <typename Put>
+    __device__ __forceinline__ uint32_t emit(uint64_t pos, uint64_t o, Put&& put) const {
+        const uint64_t s = string_of(pos);
+        const uint32_t d = (uint32_t)(s >> 56);
+        put(o, (char)s); put(o + 1, (char)(s >> 8)); put(o + 2, (char)(s >> 16));
+        if (d > 3) put(o + 3, (char)(s >> 24));
+        if (d > 4) put(o + 4, (char)(s >> 32));
+        return d;
+    }
+};
+
+// K20
 template <bool WRITE, bool ALIGNED>
 __global__ void __launch_bounds__(CT_BLOCK)
 k_gc_tiles(const uint8_t* __restrict__ bases, uint64_t n, uint32_t k, const GcStrings strs, const uint64_t* __restrict__ rec_start,
@@ -54,70 +100,9 @@ k_gc_tiles(const uint8_t* __restrict__ bases, uint64_t n, uint32_t k, const GcSt
     __shared__ uint64_t s_r[2];
     __shared__ uint64_t s_str[GC_MAX_STRINGS];
     __shared__ uint16_t s_gc[CT_BLOCK + GC_HALO], s_bad[CT_BLOCK + GC_HALO];
-    const uint32_t tid = threadIdx.x;
-    if (WRITE && blockIdx.x == 0 && tid == 0) text_off[n_rec] = text_base + totals[0] + totals[1];
-    if (tid < k + 2) s_str[tid] = strs.e[tid];                       // (k + 2 <= GC_MAX_STRINGS; the tile loop's first barrier is behind it)
-    const uint64_t k_mask = (1ULL << k) - 1;
-
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t c0 = tile * CT_TILE;
-        if (tid == 0) {                                            // the records that start in the tile
-            const uint64_t lo = hits_lower_bound(rec_start, rec_len, 0, n_rec, c0, false);
-            s_r[0] = lo;
-            s_r[1] = hits_lower_bound(rec_start, rec_len, lo, n_rec, c0 + CT_TILE, false);
-        }
-        const uint64_t off = c0 + (uint64_t)tid * CT_LANE;
-        auto stage = [&](uint32_t h, uint64_t at) {                 // 16 bytes from `at` to halfword h of both masks
-            uint32_t w[4], code, bad;
-            load16<ALIGNED>(bases, n, at, w);                        // (past n: 'N')
-            encode16(w, code, bad);
-            s_gc[h] = (uint16_t)gc_bits16(w);
-            s_bad[h] = (uint16_t)(__brev(bad) >> 16);                // encode16 has the first byte on top
-        };
-        stage(tid, off);
-        if (tid < GC_HALO) stage(CT_BLOCK + tid, c0 + CT_TILE + (uint64_t)tid * CT_LANE);
-        __syncthreads();
-        const uint64_t r_lo = s_r[0], r_hi = s_r[1];
-
-        // positions off .. off + 15 and the k - 1 <= 62 behind them: 78 bits of 80
-        const uint64_t gc_lo = (uint64_t)s_gc[tid] | (uint64_t)s_gc[tid + 1] << 16 | (uint64_t)s_gc[tid + 2] << 32 | (uint64_t)s_gc[tid + 3] << 48;
-        const uint64_t bad_lo = (uint64_t)s_bad[tid] | (uint64_t)s_bad[tid + 1] << 16 | (uint64_t)s_bad[tid + 2] << 32 | (uint64_t)s_bad[tid + 3] << 48;
-        const uint64_t gc_hi = s_gc[tid + 4], bad_hi = s_bad[tid + 4];
-        auto string_of = [&](uint64_t pos) {                         // the table entry of the window that starts at pos
-            const uint32_t j = (uint32_t)(pos - off);
-            const uint64_t b = ((bad_lo >> j) | (j ? bad_hi << (64 - j) : 0)) & k_mask;
-            const uint64_t g = ((gc_lo >> j) | (j ? gc_hi << (64 - j) : 0)) & k_mask;
-            return s_str[b ? k + 1 : (uint32_t)__popcll(g)];
-        };
-
-        uint32_t sum = 0;
-        cvg_walk(rec_start, rec_len, n_rec, r_lo, r_hi, off, n, k, [](uint64_t, uint64_t) {},
-                 [&](uint64_t, uint64_t pos, bool) { sum += (uint32_t)(string_of(pos) >> 56) + 1; });
-        uint32_t total;
-        const uint32_t before = rg_block_before(sum, s_w, total);    // (its barriers also keep s_r and the masks for the slowest thread)
-        if constexpr (!WRITE) {
-            if (tid == 0) tile_sum[tile] = total;
-        } else {
-            uint64_t at = tile_sum[tile] + before;                   // P(pos) along the lane
-            auto put = [&](uint64_t o, char ch) { if (o < cap) text[o] = (uint8_t)ch; };
-            cvg_walk(rec_start, rec_len, n_rec, r_lo, r_hi, off, n, k,
-                     [&](uint64_t r, uint64_t len) {
-                         const uint64_t o = at + extra[r];
-                         text_off[r] = text_base + o;
-                         if (len < k) { put(o, '0'); put(o + 1, '.'); put(o + 2, '0'); put(o + 3, '\n'); }
-                     },
-                     [&](uint64_t r, uint64_t pos, bool last) {
-                         const uint64_t s = string_of(pos);
-                         const uint32_t d = (uint32_t)(s >> 56);
-                         const uint64_t o = at + extra[r];
-                         put(o, (char)s); put(o + 1, (char)(s >> 8)); put(o + 2, (char)(s >> 16));
-                         if (d > 3) put(o + 3, (char)(s >> 24));
-                         if (d > 4) put(o + 4, (char)(s >> 32));
-                         put(o + d, last ? '\n' : ' ');
-                         at += d + 1;
-                     });
-        }
-    }
+    if (threadIdx.x < k + 2) s_str[threadIdx.x] = strs.e[threadIdx.x];   // (k + 2 <= GC_MAX_STRINGS; the tile loop's first barrier is behind it)
+    GcWindows<ALIGNED> src{bases, n, k, (1ULL << k) - 1, s_str, s_gc, s_bad};
+    text_tiles<WRITE>(src, s_w, s_r, n, k, rec_start, rec_len, n_rec, n_tiles, tile_sum, extra, totals, text_base, text, cap, text_off);
 }
 
 }  // namespace kg

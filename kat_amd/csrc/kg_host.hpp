@@ -2,8 +2,9 @@
 // handles of include/katgpu.h, error plumbing, the allocation pool, launch timing.  The library is split by concern:
 //   kg_context.hip   context, pool, profile counters, device buffers, the synthetic workload
 //   kg_table.hip     table life cycle: geometry, create / regrow / free, counters and statistics, room for records to come
-//   kg_query.hip     a sequence or keys against a table: lookups, profiles and per-record hits (one table, or the ranks' tables gathered), coverage statistics, count-range regions, -counts.cvg and -counts.gc text
-//   kg_records.hip   records out of a table and into one: partition / export / merge, the k-mer filter
+//   kg_query.hip     a sequence or keys against a table: lookups, profiles and per-record hits (one table, or the ranks' tables gathered)
+//   kg_per_record.hip  the per-record calls of sect and cold: coverage statistics, count-range regions, -counts.cvg and -counts.gc text
+//   kg_records.hip  records out of a table and into one: partition / export / merge, the k-mer filter
 //   kg_jf_device.hip .jf records in file order out of a table, and streamed from a file into one
 //   kg_count.hip     counting: the direct kernel, the partitioned counter's host loop, the host feeder, katgpu_count*
 //   kg_scan.hip      device-side record scan of raw FASTQ / FASTA bytes (katgpu_count_files' fast path)
@@ -12,7 +13,8 @@
 //   kg_comm_exchange.hip  the exchange itself, above the communicator (katgpu_exchange_*)
 //   kg_reduce.hip    hist / gcp / comp
 // A unit's kernels are in the headers only it includes, or in the unit itself: kg_context.hip kg_synth_kernels.hpp; kg_table.hip its own
-// (k_regrow, k_total); kg_query.hip kg_query_kernels.hpp, kg_filter.hpp (K10), kg_record_stats.hpp, kg_record_regions.hpp, kg_cvg_text.hpp, kg_gc_text.hpp;
+// (k_regrow, k_total); kg_query.hip kg_query_kernels.hpp, kg_filter.hpp (K10); kg_per_record.hip kg_record_stats.hpp, kg_record_regions.hpp,
+// kg_cvg_text.hpp, kg_gc_text.hpp (and through them kg_filter.hpp's record search; k_profile it reaches through kg_query.hip's launch_profile);
 // kg_records.hip kg_record_kernels.hpp, kg_filter.hpp (K9); kg_jf_device.hip kg_jf_records.hpp, kg_jf_load.hpp; kg_count.hip its own
 // (k_sweep), kg_partition.hpp and what that includes, kg_partition_wide.hpp; kg_scan.hip kg_scan.hpp; kg_exchange.hip kg_exchange_kernels.hpp;
 // kg_reduce.hip kg_reduce_kernels.hpp.  Shared: kg_kernels.hpp (the chunk geometry and the direct counter k_count) and kg_rows_scan.hpp
@@ -269,14 +271,30 @@ struct ScopedTimer {
 struct DevBuf {
     void* p = nullptr;
     katgpu_ctx* pool = nullptr;          // non-null: a pool allocation of this context
+    size_t cap = 0;                      // fit's: the bytes behind p
     DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p(o.p), pool(o.pool) { o.p = nullptr; }
+    DevBuf(DevBuf&& o) noexcept : p(o.p), pool(o.pool), cap(o.cap) { o.p = nullptr; o.cap = 0; }
     ~DevBuf() { reset(); }
     hipError_t plain(size_t bytes) { reset(); pool = nullptr; return hipMalloc(&p, bytes); }                 // (both leave p null when they fail)
     hipError_t pooled(katgpu_ctx* c, size_t bytes) { reset(); pool = c; return pool_alloc(c, &p, bytes); }
-    void reset() { if (p && pool) { hipStreamSynchronize(pool->stream); pool_release(pool, p); } else if (p) hipFree(p); p = nullptr; }
+    // grow-only, for a buffer that serves one batch after another: the block stays while it holds `need` bytes, else another comes from
+    // c's pool (what the old one held is gone).  No memory: p null, cap 0, and HIP's sticky error cleared.
+    hipError_t fit(katgpu_ctx* c, size_t need) {
+        if (cap >= need) return hipSuccess;
+        const hipError_t e = pooled(c, need);
+        if (e == hipSuccess) cap = need;
+        else (void)hipGetLastError();
+        return e;
+    }
+    void reset() { if (p && pool) { hipStreamSynchronize(pool->stream); pool_release(pool, p); } else if (p) hipFree(p); p = nullptr; cap = 0; }
     template <typename T> T* as() const { return static_cast<T*>(p); }
 };
+
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// window starts per chunk of the window kernels.  The geometry is kg_kernels.hpp's (Chunk<W>), which the units that launch such a
+// kernel include and this header does not: hence a template, looked up where it is called.
+namespace kg { template <bool W> struct Chunk; }
+template <bool W = true> uint64_t chunk_starts(bool wide) { return wide ? Chunk<W>::STARTS : Chunk<!W>::STARTS; }
 
 // The four (aligned, wide) instantiations of a window kernel behind one call: launch(A, W, grid, n_chunks) with A and W a
 // std::true_type / std::false_type each, n_chunks = the chunks of per_chunk items in n, and a grid of at most eight workgroups per CU.
@@ -308,33 +326,36 @@ inline int check_records(katgpu_ctx* c, const uint64_t* rec_start, const uint64_
 
 // The records of a host form through the device in batches [r0, r1) of at most max_bases bases and max_recs records (a record longer than that is a
 // batch of its own); joins(r, first) may end a batch earlier: it is asked once per record, in order, after the two limits (a batch's first record joins
-// whatever it says).  Per batch the bases from its first record's start to its last one's end, the starts (counted from there) and the lengths go up
-// (dev_start, dev_len: max_recs words each), body(dev_bases, nb, dev_start, dev_len, m, r0) queues its work, and the stream is waited for.
-// no_room != null: a batch of bases that finds no device memory ends the loop with KATGPU_ERR_NOMEM and its bytes there, for the caller to word.
+// whatever it says).  The records of a batch have a pooled buffer of max_recs x (2 + extra_words) words: start | length | the body's own.  Per batch
+// the bases from its first record's start to its last one's end, the starts (counted from there) and the lengths go up,
+// body(dev_bases, nb, dev_start, dev_len, m, r0, dev_extra) queues its work -- dev_extra: the words behind start and length -- and the stream is waited for.
+// what_nomem != null: no device memory for the records or for a batch of bases is KATGPU_ERR_NOMEM, worded in its name; null: whatever HIP said, in `what`'s.
 template <typename Joins, typename Body>
 int for_record_batches(katgpu_ctx* c, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec, size_t max_bases,
-                       size_t max_recs, uint64_t* dev_start, uint64_t* dev_len, const char* what, size_t* no_room, Joins&& joins, Body&& body) {
-    DevBuf db;
-    size_t db_bytes = 0;
+                       size_t max_recs, size_t extra_words, const char* what, const char* what_nomem, Joins&& joins, Body&& body) {
+    DevBuf recs, db;
+    hipError_t e = recs.pooled(c, max_recs * (2 + extra_words) * sizeof(uint64_t));
+    if (e != hipSuccess && what_nomem) return fail(c, KATGPU_ERR_NOMEM, "%s: no device memory for the records of a batch", what_nomem);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? KATGPU_ERR_NOMEM : KATGPU_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+    uint64_t *dev_start = recs.as<uint64_t>(), *dev_len = dev_start + max_recs;
     std::vector<uint64_t> st(max_recs), ln(max_recs);
-    int rc = KATGPU_OK; hipError_t e = hipSuccess;
+    int rc = KATGPU_OK;
     for (size_t r0 = 0; r0 < n_rec && !rc && e == hipSuccess;) {
         const uint64_t base = rec_start[r0];
         size_t r1 = r0;
         joins(r1++, true);
         while (r1 < n_rec && r1 - r0 < max_recs && rec_start[r1] + rec_len[r1] - base <= max_bases && joins(r1, false)) ++r1;
         const size_t nb = rec_start[r1 - 1] + rec_len[r1 - 1] - base, m = r1 - r0;
-        if (nb + 64 > db_bytes) {
-            db_bytes = std::max(nb + 64, std::min(max_bases, n) + 64);
-            e = db.pooled(c, db_bytes);
-            if (e != hipSuccess) { db_bytes = 0; if (no_room) { *no_room = nb + 64; rc = KATGPU_ERR_NOMEM; } break; }
+        if (nb + 64 > db.cap) {
+            e = db.fit(c, std::max(nb + 64, std::min(max_bases, n) + 64));
+            if (e != hipSuccess) { if (what_nomem) rc = fail(c, KATGPU_ERR_NOMEM, "%s: no %zu bytes of device memory for a batch of bases", what_nomem, nb + 64); break; }
         }
         for (size_t r = r0; r < r1; ++r) { st[r - r0] = rec_start[r] - base; ln[r - r0] = rec_len[r]; }
         if (nb) e = hipMemcpyAsync(db.p, bases + base, nb, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dev_start, st.data(), m * 8, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dev_len, ln.data(), m * 8, hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) break;
-        rc = body(db.as<uint8_t>(), nb, dev_start, dev_len, m, r0);
+        rc = body(db.as<uint8_t>(), nb, dev_start, dev_len, m, r0, dev_len + max_recs);
         e = hipStreamSynchronize(c->stream);
         r0 = r1;
     }
@@ -342,6 +363,16 @@ int for_record_batches(katgpu_ctx* c, const char* bases, size_t n, const uint64_
     if (e != hipSuccess) return fail(c, KATGPU_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
     return KATGPU_OK;
 }
+
+// n words of totals from the device, the stream waited for: how a form that sizes its output first learns the size
+inline int read_totals(katgpu_ctx* c, const unsigned long long* dev, uint32_t n, const char* what, unsigned long long* out) {
+    hipError_t e = hipMemcpyAsync(out, dev, n * sizeof *out, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    return e == hipSuccess ? KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
+}
+
+// k_profile over n >= k bases on the stream, one timed section (kg_query.hip, the one unit that compiles the kernel)
+int launch_profile(katgpu_table* t, const uint8_t* dev_bases, size_t n, int canonicalise, uint64_t* dev_counts);
 
 // What a stream of .jf records between a file and the device runs on: a copy stream beside the context's and up to two slots of a device buffer, a
 // pinned buffer of that size and four events.  alloc(void**, bytes) makes a device buffer; pooled: pool_release gives it back, else hipFree.

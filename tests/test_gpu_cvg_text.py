@@ -14,6 +14,7 @@ from tests import cvg_text_case as cvg_case
 from tests import cvg_text_model as cm
 from tests import record_regions_case as case
 from tests import record_stats_case as stats_case
+from tests.record_text_checks import assert_equal as _assert_equal, device_call as _device_call
 
 pytestmark = pytest.mark.gpu
 
@@ -24,17 +25,6 @@ _WANT = {}
 
 def _oracle(ko, k, canonical, bases):
     return (ko.WideTable(k, canonical) if k > 32 else ko.Table(k, canonical)).count_bases(bases)
-
-
-def _assert_equal(got, want, what=""):
-    (text, off), (wtext, woff) = got, want
-    assert isinstance(text, bytes) and off.dtype == np.uint64 and off.shape == woff.shape, (what, off.dtype, off.shape, woff.shape)
-    bad = np.nonzero(off != woff)[0]
-    assert bad.size == 0, (what, bad[:5], off[bad[:5]], woff[bad[:5]])
-    if text != wtext:
-        a, b = np.frombuffer(text, np.uint8), np.frombuffer(wtext, np.uint8)
-        at = int(np.nonzero(a != b)[0][0]) if a.size == b.size else min(a.size, b.size)
-        raise AssertionError((what, len(text), len(wtext), at, text[max(at - 30, 0):at + 30], wtext[max(at - 30, 0):at + 30]))
 
 
 def _seam_case(ko, k):
@@ -139,27 +129,6 @@ def test_batches(ko, tmp_path):
     _assert_equal((z["text"].tobytes(), z["off"]), want)
 
 
-def _device_call(engine, t, b, st, ln, cap, shift=0, guard=64):
-    m = st.size
-    db = engine.alloc(b.size + 64)
-    db.upload(b, offset=shift)
-    dr = engine.alloc(16 * m)
-    dr.upload(st)
-    dr.upload(ln, offset=8 * m)
-    fill = np.full(cap + guard, 0xAB, np.uint8)
-    do = engine.alloc(fill.nbytes)
-    do.upload(fill)
-    off_fill = np.full(m + 2, 0xCDCDCDCDCDCDCDCD, np.uint64)
-    df = engine.alloc(off_fill.nbytes)
-    df.upload(off_fill)
-    total = t.record_cvg_text_device(db.ptr + shift, b.size, dr.ptr, dr.ptr + 8 * m, m, do.ptr if cap else None, cap, df.ptr)
-    engine.sync()
-    out, off = do.download(np.uint8, fill.size), df.download(np.uint64, off_fill.size)
-    db.free(); dr.free(); do.free(); df.free()
-    assert off[-1] == 0xCDCDCDCDCDCDCDCD                            # n_rec + 1 offsets, not one more
-    return total, out, off[:-1]
-
-
 def test_device_form(engine, ko):
     k = 21
     b, st, ln, (wtext, woff) = _seam_case(ko, k)
@@ -167,14 +136,14 @@ def test_device_form(engine, ko):
     t = engine.table(k, True).count_bases(case.counted(k))
     _assert_equal(t.record_cvg_text(b, st, ln), (wtext, woff))
     for shift in (0, 1, 16):                                        # (the aligned and the byte-wise loader of the lookups)
-        total, out, off = _device_call(engine, t, b, st, ln, w.size, shift)
+        total, out, off = _device_call(engine, t.record_cvg_text_device, b, st, ln, w.size, shift)
         assert total == w.size and np.array_equal(off, woff), shift
         assert np.array_equal(out[:w.size], w) and (out[w.size:] == 0xAB).all(), shift
     for cap in (1, 7, 100_001, w.size - 1):                         # too little room: the first `cap` bytes, nothing behind them, the true total
-        total, out, off = _device_call(engine, t, b, st, ln, cap)
+        total, out, off = _device_call(engine, t.record_cvg_text_device, b, st, ln, cap)
         assert total == w.size and np.array_equal(off, woff), cap
         assert np.array_equal(out[:cap], w[:cap]) and (out[cap:] == 0xAB).all(), cap
-    total, out, off = _device_call(engine, t, b, st, ln, 0)         # size only: the offsets all the same
+    total, out, off = _device_call(engine, t.record_cvg_text_device, b, st, ln, 0)         # size only: the offsets all the same
     assert total == w.size and np.array_equal(off, woff) and (out == 0xAB).all()
     t.free()
 

@@ -3,6 +3,7 @@ with the oracle's per-position G+C counts, exactly -- key widths from one bit to
 side by side, every byte class, records across tile seams and a tile's halo, thousands of records without a window, touching records,
 batch boundaries, the device form with too little room, argument errors."""
 import ctypes as C
+import functools
 import os
 import subprocess
 import sys
@@ -14,23 +15,13 @@ import kat_amd
 from tests import gc_text_case as gc_case
 from tests import gc_text_model as gm
 from tests import record_stats_case as stats_case
+from tests.record_text_checks import assert_equal as _assert_equal, device_call as _device_call
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TILE = gc_case.TILE
 _WANT = {}
-
-
-def _assert_equal(got, want, what=""):
-    (text, off), (wtext, woff) = got, want
-    assert isinstance(text, bytes) and off.dtype == np.uint64 and off.shape == woff.shape, (what, off.dtype, off.shape, woff.shape)
-    bad = np.nonzero(off != woff)[0]
-    assert bad.size == 0, (what, bad[:5], off[bad[:5]], woff[bad[:5]])
-    if text != wtext:
-        a, b = np.frombuffer(text, np.uint8), np.frombuffer(wtext, np.uint8)
-        at = int(np.nonzero(a != b)[0][0]) if a.size == b.size else min(a.size, b.size)
-        raise AssertionError((what, len(text), len(wtext), at, text[max(at - 30, 0):at + 30], wtext[max(at - 30, 0):at + 30]))
 
 
 def _seam_case(ko, k):
@@ -125,40 +116,20 @@ def test_batches(ko, tmp_path):
     _assert_equal((z["text"].tobytes(), z["off"]), want)
 
 
-def _device_call(engine, k, b, st, ln, cap, shift=0, guard=64):
-    m = st.size
-    db = engine.alloc(b.size + 64)
-    db.upload(b, offset=shift)
-    dr = engine.alloc(16 * m)
-    dr.upload(st)
-    dr.upload(ln, offset=8 * m)
-    fill = np.full(cap + guard, 0xAB, np.uint8)
-    do = engine.alloc(fill.nbytes)
-    do.upload(fill)
-    off_fill = np.full(m + 2, 0xCDCDCDCDCDCDCDCD, np.uint64)
-    df = engine.alloc(off_fill.nbytes)
-    df.upload(off_fill)
-    total = engine.record_gc_text_device(k, db.ptr + shift, b.size, dr.ptr, dr.ptr + 8 * m, m, do.ptr if cap else None, cap, df.ptr)
-    engine.sync()
-    out, off = do.download(np.uint8, fill.size), df.download(np.uint64, off_fill.size)
-    db.free(); dr.free(); do.free(); df.free()
-    assert off[-1] == 0xCDCDCDCDCDCDCDCD                            # n_rec + 1 offsets, not one more
-    return total, out, off[:-1]
-
-
 def test_device_form(engine, ko):
     k = 21
     b, st, ln, (wtext, woff) = _seam_case(ko, k)
     w = np.frombuffer(wtext, np.uint8)
+    gc_text_device = functools.partial(engine.record_gc_text_device, k)
     for shift in (0, 1, 16):                                        # (the aligned and the byte-wise loader)
-        total, out, off = _device_call(engine, k, b, st, ln, w.size, shift)
+        total, out, off = _device_call(engine, gc_text_device, b, st, ln, w.size, shift)
         assert total == w.size and np.array_equal(off, woff), shift
         assert np.array_equal(out[:w.size], w) and (out[w.size:] == 0xAB).all(), shift
     for cap in (1, 7, 100_001, w.size - 1):                         # too little room: the first `cap` bytes, nothing behind them, the true total
-        total, out, off = _device_call(engine, k, b, st, ln, cap)
+        total, out, off = _device_call(engine, gc_text_device, b, st, ln, cap)
         assert total == w.size and np.array_equal(off, woff), cap
         assert np.array_equal(out[:cap], w[:cap]) and (out[cap:] == 0xAB).all(), cap
-    total, out, off = _device_call(engine, k, b, st, ln, 0)         # size only: the offsets all the same
+    total, out, off = _device_call(engine, gc_text_device, b, st, ln, 0)         # size only: the offsets all the same
     assert total == w.size and np.array_equal(off, woff) and (out == 0xAB).all()
 
 

@@ -89,3 +89,7 @@ def test_no_scratch_and_the_stage_kernels_keep_their_budgets(tmp_path):
     every("k_hist<", vgpr=64)
     every("k_gcp_pk", vgpr=64)
     every("k_gcp<", vgpr=64)
+    # the text kernels of sect (one frame, kg_cvg_text.hpp: text_tiles): eight waves per SIMD, LDS no more than the two words of the
+    # frame and the sums of a block (K18), and the strings and the two masks of a tile beside them (K20)
+    every("k_cvg_tiles<", vgpr=64, lds=32)
+    every("k_gc_tiles<", vgpr=64, lds=1616)
