@@ -21,6 +21,7 @@
 #pragma once
 #include "kg_kernels.hpp"
 #include "kg_l1_lean.hpp"
+#include "kg_apply_lean.hpp"
 
 #include <cstddef>
 #include <type_traits>
@@ -1757,9 +1758,9 @@ struct ApkWalk {
                 if (busy == 0 || (busy < 8 && (fin || rr >= 4))) break;
                 if (live) {
                     unsigned long long w = rk[slot];
-                    if (w == 0) {
+                    if (!ap_taken((uint32_t)w)) {
                         w = atomicCAS(&rk[slot], 0ULL, (unsigned long long)((rem << cb) | 1ULL));
-                        if (w == 0) { ++new_distinct; live = false; }                  // claimed, counted
+                        if (!ap_taken((uint32_t)w)) { ++new_distinct; live = false; }  // claimed, counted
                     }
                     if (live) {
                         if ((w >> cb) == rem) { add1(slot); live = false; }
@@ -1793,7 +1794,7 @@ struct ApkWalk {
                 for (;;) {
                     uint32_t idx = cs + lane; if (idx >= S) idx -= S;                      // S >= 64 on this path (host-checked)
                     const unsigned long long w = rk[idx];
-                    const unsigned long long mk = __ballot(w != 0 && (w >> cb) == ck), me = __ballot(w == 0);
+                    const unsigned long long mk = __ballot(ap_holds(w, ck, cb)), me = __ballot(!ap_taken((uint32_t)w));
                     if (!(mk | me)) {                                                      // 64 foreign k-mers
                         cbud -= 64; cs = cs + 64 >= S ? cs + 64 - S : cs + 64;
                         if (cbud <= 0) { if (lane == 0) spill_rem(ck); break; }
@@ -1805,7 +1806,7 @@ struct ApkWalk {
                     unsigned long long old = 0;                                            // a free slot comes first: claim it
                     if ((int)lane == first) old = atomicCAS(&rk[idx], 0ULL, (unsigned long long)((ck << cb) | 1ULL));
                     old = lane_value((uint64_t)old, first);
-                    if (old == 0) { if ((int)lane == first) ++new_distinct; break; }
+                    if (!ap_taken((uint32_t)old)) { if ((int)lane == first) ++new_distinct; break; }
                     if ((old >> cb) == ck) { if ((int)lane == first) add1(idx); break; }   // the same k-mer got there first
                     cbud -= first; cs = cs + first >= S ? cs + first - S : cs + first;     // someone else's k-mer landed there: go on from that slot
                 }
@@ -1863,11 +1864,12 @@ struct ApkWalk {
                 bool claim[U];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
-                    const bool hit = pend[u] && seen[u] != 0 && (seen[u] >> cb) == rem[u];
+                    const bool taken = ap_taken((uint32_t)seen[u]);                  // (the low word says it: kg_apply_lean.hpp)
+                    const bool hit = pend[u] && taken && (seen[u] >> cb) == rem[u];
                     (void)__hip_atomic_fetch_add(&rk32[2 * slot[u]], hit ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     pend[u] = pend[u] && !hit;
-                    claim[u] = pend[u] && seen[u] == 0;
-                    slot[u] = (pend[u] && !claim[u]) ? next_slot(slot[u]) : slot[u];
+                    claim[u] = pend[u] && !taken;
+                    slot[u] = ap_advance(slot[u], pend[u] && taken, S);
                 }
                 // INLINE_CLAIM (a table's first round: nearly every k-mer is new): claims right here, U CAS in flight
                 bool any_claim = false;
@@ -1880,7 +1882,7 @@ struct ApkWalk {
 #pragma unroll
                     for (int u = 0; u < U; ++u) {
                         if (claim[u]) {
-                            if (got[u] == 0) { ++new_distinct; pend[u] = false; }
+                            if (!ap_taken((uint32_t)got[u])) { ++new_distinct; pend[u] = false; }
                             else if ((got[u] >> cb) == rem[u]) { add1(slot[u]); pend[u] = false; }
                             else slot[u] = next_slot(slot[u]);                             // someone else's k-mer landed there
                         }

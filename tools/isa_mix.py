@@ -3,7 +3,8 @@
 
   tools/isa_mix.py <file.s> <substring of the mangled kernel name> [--loops]
 
-Prints the kernel's VGPR / SGPR / LDS / scratch use and its instructions by class (VALU, 64-bit VALU, `valu_quarter` = 32-bit
+Prints the kernel's VGPR / SGPR / LDS / scratch use and its instructions by class (VALU, 64-bit VALU -- counted on their own, weighted 1 --,
+`valu_quarter` = 32-bit
 multiplies and 64-bit mads -- counted on their own, but full rate on gfx950: tools/ubench_valu.hip --, LDS, global/flat, SALU,
 branches, waits), for the whole body and per basic block with --loops.  A VALU-bound
 kernel's time goes with the weighted VALU count of its hot loop, which is what this is for: iterating on instruction count
@@ -78,7 +79,8 @@ def main():
             break
     print(name)
     print("  ", meta)
-    w = lambda d: d.get("valu", 0) + 2 * d.get("valu_64", 0) + d.get("valu_quarter", 0)
+    # (64-bit shifts and compares weigh 1: the packed apply ran SLOWER with them replaced by more 32-bit instructions -- profiles/apply_lean_parent_vs_branch.txt)
+    w = lambda d: d.get("valu", 0) + d.get("valu_64", 0) + d.get("valu_quarter", 0)
     print("   total:", dict(sorted(tot.items())), "weighted VALU:", w(tot))
     if per_block:
         for nm, d in blocks:
