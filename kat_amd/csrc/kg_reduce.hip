@@ -148,6 +148,12 @@ extern "C" int katgpu_comp(katgpu_table* t1, katgpu_table* t2, int canon1, int c
         const size_t per_cu = std::max<size_t>(1, std::min<size_t>((160 * 1024) / (align_up(lds + 64, 1280)), 2048 / jblk));
         return std::min<uint32_t>(regions, (uint32_t)c->n_cu * (uint32_t)per_cu);
     };
+    // which form takes each pass (the launches below follow these)
+    const bool p1_join = !fused && join_1 && join1 <= 150 * 1024;
+    const bool p2_seen = !fused && a.seen && join1 <= 150 * 1024;
+    const bool p2_join = !fused && !p2_seen && same_grid && ident2 && join2 <= 150 * 1024 && (g_force_join || join_pays(t2, t1));
+    if (g_trace) fprintf(stderr, "[katgpu] reducer form: comp pass1=%s pass2=%s pk=%d wide=%d n_ovf1=%u n_ovf2=%u ones1=%llu ones2=%llu fold=%u\n", fused ? "fused" : p1_join ? "join" : "probe",
+                         fused ? "fused" : p2_seen ? "seen" : p2_join ? "join" : "probe", (int)pk, (int)wide, t1->n_ovf, t2->n_ovf, (unsigned long long)t1->ones, (unsigned long long)t2->ones, a.fold);
     if (fused) {
         ScopedTimer tm(c, KATGPU_K_COMP_PASS1, t1->dev().cap + t2->dev().cap);
         const uint32_t grid = std::min<uint32_t>(t1->dev().n_regions, (uint32_t)c->n_cu);
@@ -169,7 +175,7 @@ extern "C" int katgpu_comp(katgpu_table* t1, katgpu_table* t2, int canon1, int c
                hipLaunchKernelGGL((k_comp_join<PASS, false>), dim3(join_grid(LDS, TA->dev().n_regions)), dim3(jblk), LDS, c->stream, TA->dev(), TA->n_ovf, TB->dev(), TB->n_ovf, a); } } while (0)
     if (!fused) {
         ScopedTimer tm(c, KATGPU_K_COMP_PASS1, t1->dev().cap);
-        if (join_1 && join1 <= 150 * 1024) {
+        if (p1_join) {
             const size_t j1 = join1 + (a.seen ? (size_t)wpr * 4 : 0);
             KG_JOIN(1, t1, t2, j1);
         } else if (wide)
@@ -179,11 +185,11 @@ extern "C" int katgpu_comp(katgpu_table* t1, katgpu_table* t2, int canon1, int c
     }
     if (!fused) {
         ScopedTimer tm(c, KATGPU_K_COMP_PASS2, t2->dev().cap);
-        if (a.seen && join1 <= 150 * 1024) {
+        if (p2_seen) {
             const uint32_t grid = std::min<uint32_t>(t2->dev().n_regions, (uint32_t)c->n_cu * 4);
             if (pk) hipLaunchKernelGGL(k_comp_seen<true>, dim3(grid), dim3(512), lds2, c->stream, t2->dev(), t2->n_ovf, a);
             else hipLaunchKernelGGL(k_comp_seen<false>, dim3(grid), dim3(512), lds2, c->stream, t2->dev(), t2->n_ovf, a);
-        } else if (same_grid && ident2 && join2 <= 150 * 1024 && (g_force_join || join_pays(t2, t1))) {
+        } else if (p2_join) {
             KG_JOIN(2, t2, t1, join2);
         } else if (wide)
             hipLaunchKernelGGL((k_comp<2, true>), dim3(reducer_grid(c, t2->dev().cap + 1, 4)), dim3(256), lds2, c->stream, t2->dev(), t2->n_ovf, t1->dev(), t1->n_ovf, a);
@@ -219,15 +225,18 @@ extern "C" int katgpu_comp3(katgpu_table* t1, katgpu_table* t2, katgpu_table* t3
     a.d1_scale = d1_scale; a.d2_scale = d2_scale; a.d1_bins = d1_bins; a.d2_bins = d2_bins;
     a.canon2 = canon2 ? 1 : 0; a.canon3 = canon3 ? 1 : 0;
     a.mx[0] = d; a.mx[1] = d + cells; a.mx[2] = d + 2 * cells;
+    const int grid1 = reducer_grid(c, t1->dev().cap + 1, 3), grid3 = reducer_grid(c, t3->dev().cap + 1, 8);
+    if (g_trace) fprintf(stderr, "[katgpu] reducer form: comp3 wide=%d n_ovf1=%u n_ovf2=%u n_ovf3=%u ones1=%llu ones3=%llu grid1=%d grid3=%d\n", t1->dev().keys_b ? 1 : 0, t1->n_ovf, t2->n_ovf,
+                         t3->n_ovf, (unsigned long long)t1->ones, (unsigned long long)t3->ones, grid1, grid3);
     {
         ScopedTimer tm(c, KATGPU_K_COMP_PASS1, t1->dev().cap);
         if (t1->dev().keys_b)
-            hipLaunchKernelGGL(k_comp3_pass1<true>, dim3(reducer_grid(c, t1->dev().cap + 1, 3)), dim3(256), 3 * COMP_TILE * COMP_TILE * sizeof(uint32_t), c->stream,
+            hipLaunchKernelGGL(k_comp3_pass1<true>, dim3(grid1), dim3(256), 3 * COMP_TILE * COMP_TILE * sizeof(uint32_t), c->stream,
                                t1->dev(), t1->n_ovf, t2->dev(), t2->n_ovf, t3->dev(), t3->n_ovf, a);
         else
-            hipLaunchKernelGGL(k_comp3_pass1<false>, dim3(reducer_grid(c, t1->dev().cap + 1, 3)), dim3(256), 3 * COMP_TILE * COMP_TILE * sizeof(uint32_t), c->stream,
+            hipLaunchKernelGGL(k_comp3_pass1<false>, dim3(grid1), dim3(256), 3 * COMP_TILE * COMP_TILE * sizeof(uint32_t), c->stream,
                                t1->dev(), t1->n_ovf, t2->dev(), t2->n_ovf, t3->dev(), t3->n_ovf, a);
-        hipLaunchKernelGGL(k_comp3_pass3, dim3(reducer_grid(c, t3->dev().cap + 1, 8)), dim3(256), 0, c->stream, t3->dev(), t3->n_ovf, d + 3 * cells);
+        hipLaunchKernelGGL(k_comp3_pass3, dim3(grid3), dim3(256), 0, c->stream, t3->dev(), t3->n_ovf, d + 3 * cells);
     }
     HIPCHK(c, hipGetLastError());
     uint64_t c3[13];
