@@ -282,10 +282,10 @@ struct ApplyLaunch {                                         // what every insta
     katgpu_table* t; const PartGeom& g; const uint64_t* off2; const uint8_t* l2_buf; uint64_t* spill_buf; unsigned long long* spill_n; const uint32_t* run_len; const uint64_t* bucket_end;
     dim3 grid; size_t lds; uint32_t qcap; uint64_t seg_len; uint32_t zero_fill; ApplyForm* form;
 };
-template <int B, int KP, int HB, bool INL, bool HK, bool PF, int NR, bool STAMP = false>
+template <int B, int KP, int HB, bool INL, bool HK, bool LATE /* the next region's loads behind the end-of-walk barrier; false: with the wave */, int NR, bool STAMP = false>
 static int apply_pk(const ApplyLaunch& a) {
     if (a.form) *a.form = ApplyForm{true, B, KP, INL, HK};
-    return launch_lds(a.t->ctx, k_p3_apply_pk<B, KP, HB, INL, HK, PF, NR, STAMP>, a.grid, dim3(B), a.lds, LDS_BYTES - 256, a.t->dv, a.g, a.off2, a.l2_buf, a.spill_buf, a.spill_n, a.run_len, a.bucket_end,
+    return launch_lds(a.t->ctx, k_p3_apply_pk<B, KP, HB, INL, HK, LATE, NR, STAMP>, a.grid, dim3(B), a.lds, LDS_BYTES - 256, a.t->dv, a.g, a.off2, a.l2_buf, a.spill_buf, a.spill_n, a.run_len, a.bucket_end,
                       a.qcap, a.seg_len, g_test_spill_mod, a.zero_fill);
 }
 // probe rounds before the queue: 2 (measured at the bench size, same box: 163 ms per step against 177 with 3 and 198 with inline
@@ -328,8 +328,10 @@ static int launch_apply(katgpu_table* t, const PartGeom& g, const uint64_t* off2
     if (g.cbits) {
         // 512-thread workgroups, as many per CU as the LDS holds next to their queues (two at the bench's 9344-slot regions, four for
         // small regions); one of 1024 threads when a region leaves no room for a second.  (Four is what the LDS admits and what the grid is sized
-        // for; by registers -- 85-91 VGPRs for the small shapes, five waves per SIMD -- TWO are resident at a time and the other half of the grid follows.
-        // A grid of two per CU measured inside the spread, step 371.1 -> 370.5 ms: profiles/second_input_parent_vs_branch.txt; four stays.)
+        // for; by registers -- 61-72 VGPRs for the small shapes, seven waves per SIMD -- THREE are resident at a time and the rest of the grid follows:
+        // two until the region loop stopped holding its slot offsets across the walk, at 85-91 VGPRs; hist, gcp and comp-rr measured the same with
+        // three, profiles/apply_period_parent_vs_branch.txt.  A grid of two per CU measured inside the spread when two were resident, step
+        // 371.1 -> 370.5 ms: profiles/second_input_parent_vs_branch.txt; four stays.)
         const size_t region_b = (size_t)g.S * 8;
         auto room = [&](uint32_t wgs) -> long { return (long)(LDS_BYTES / wgs / LDS_GRANULE * LDS_GRANULE) - 64 - (long)region_b; };   // bytes left for the queues
         uint32_t per_cu = 4;

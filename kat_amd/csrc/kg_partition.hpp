@@ -1936,7 +1936,8 @@ struct ApkWalk {
 };
 
 template <int BLOCK, int KP /* 16-byte loads per lane that cover a region: two slots each */, int HB, bool INLINE_CLAIM = false, bool TEST_SPILL = false,
-          bool PF = true /* the next region travels from HBM into registers behind the walk of this one (2 KP VGPRs across the walk); false: loaded when its turn comes -- for shapes with a second workgroup on the CU to cover that */,
+          bool LATE_LOADS = true /* where the next region's loads are issued (they travel from HBM into 4 KP VGPRs that the next fill reads): true, behind the barrier that ends the walk;
+                            false, by each wave as it leaves the walk, ahead of that barrier (measured at the bench shape only: apply 125.9 -> 118.6 ms per step, profiles/apply_period_parent_vs_branch.txt) */,
           int NR = 3 /* probe rounds before a k-mer goes to the queue */,
           bool STAMP = false /* diagnostic (KATGPU_APPLY_STAMP): wave 0's cycles per phase, added into spill_n[8 ..]: [8] fill, [9] walk, [10] of it drains, [11] wait for the other waves + sweep, [12] write-back, [13] regions, [14] chunks */,
           int UG = 1 /* groups of the level-2 buffer a lane takes per chunk: 4 UG k-mers in flight per lane and probe round.  Two measured
@@ -1970,35 +1971,47 @@ k_p3_apply_pk(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const u
         while (r < r_hi && !zero_fill && (cnt2 ? cnt2[r] == 0 : off2[r] == run_end(r))) r += gridDim.x;
         return r;
     };
+    // A region is always loaded a region ahead, into kq.  The walk has no registers to spare at KP = 10 (100 VGPRs of 128), so nothing of this
+    // may live across it, and two things see to that.  kq is written on EVERY path of prefetch -- zeros where there is nothing to load (a first
+    // sweep, whose regions start from zeros; no region left): left alone there, its old value would count as live from the fill before.  And a
+    // lane's slot offsets are worked out afresh where they are used (fresh_tid: a handful of instructions): as loop invariants the compiler
+    // computes them once in front of the region loop, 2 KP registers and more.  Without either the bench shape keeps 40 to 190 bytes per lane
+    // in scratch (read from the compiler's resource remarks); with both, the small shapes need 61-72 VGPRs where they had 84-95.
+    auto fresh_tid = [&]() -> uint32_t { uint32_t v = tid; asm volatile("" : "+v"(v)); return v; };
     auto prefetch = [&](uint32_t r) {
-        if (zero_fill) return;                                 // (nothing to load)
-        const uint64_t base = (uint64_t)r * S;
+        if (zero_fill || r >= r_hi) {
 #pragma unroll
-        for (int u = 0; u < KP; ++u) { const uint32_t i = (u * BLOCK + tid) * 2; kq[u] = *reinterpret_cast<const u32x4*>(t.keys + base + (i < S ? i : 0)); }    // clamped, unconditional: stays in registers
+            for (int u = 0; u < KP; ++u) kq[u] = u32x4{0u, 0u, 0u, 0u};
+            return;
+        }
+        const uint64_t base = (uint64_t)r * S;
+        const uint32_t tt = fresh_tid();
+#pragma unroll
+        for (int u = 0; u < KP; ++u) { const uint32_t i = (u * BLOCK + tt) * 2; kq[u] = *reinterpret_cast<const u32x4*>(t.keys + base + (i < S ? i : 0)); }    // clamped, unconditional: stays in registers
     };
 
     unsigned long long st[7] = {0, 0, 0, 0, 0, 0, 0};
     auto now = [&]() -> unsigned long long { return STAMP ? (unsigned long long)clock64() : 0ULL; };
     uint32_t r = next_region(g.b_lo * g.P2 + blockIdx.x);
-    if (PF && r < r_hi) prefetch(r);
+    prefetch(r);
     while (r < r_hi) {
         const uint64_t beg = off2[r], end = cnt2 ? beg + cnt2[r] : run_end(r);
         const uint64_t base = (uint64_t)r * S;
         const unsigned long long t_fill = now();
-        // ---- fill: registers -> LDS ----
-        if (!PF) prefetch(r);
-        if (zero_fill) {
+        // ---- fill: registers -> LDS (zeros in a first sweep: prefetch put them there) ----
+        {
+            const uint32_t tt = fresh_tid();
 #pragma unroll
-            for (int u = 0; u < KP; ++u) { const uint32_t i = (u * BLOCK + tid) * 2; if (i < S) *reinterpret_cast<u32x4*>(rk + i) = u32x4{0u, 0u, 0u, 0u}; }
-        } else {
-#pragma unroll
-            for (int u = 0; u < KP; ++u) { const uint32_t i = (u * BLOCK + tid) * 2; if (i < S) *reinterpret_cast<u32x4*>(rk + i) = kq[u]; }
+            for (int u = 0; u < KP; ++u) { const uint32_t i = (u * BLOCK + tt) * 2; if (i < S) *reinterpret_cast<u32x4*>(rk + i) = kq[u]; }
         }
         const uint32_t rn = next_region(r + gridDim.x);
         // what spilling a k-mer (region full, test hook) needs: the region's digits give the k-mer back
         const uint32_t rd1 = r >> g.l2, rd2 = r & (g.P2 - 1);
 
-        for (uint64_t sbeg = beg; sbeg < end; sbeg += seg_len) {            // one segment, normally
+        // (The loop has ONE way out, behind the last segment's walk, and the early loads leave on it: issued on a path that could come round to
+        // another walk, or skipped on some way out, they would keep kq's registers alive across the walk.)
+        if (beg >= end) { if (!LATE_LOADS) prefetch(rn); }                          // (a region without a run -- a first sweep's -- has no walk to leave from)
+        else for (uint64_t sbeg = beg;; sbeg += seg_len) {                  // one segment, normally
             const uint64_t n_run = (end - sbeg < seg_len ? end - sbeg : seg_len);
             if (tid == 0) s_next_chunk = NW;                  // chunks 0 .. NW-1 are the waves' first ones
             lds_barrier();
@@ -2011,11 +2024,19 @@ k_p3_apply_pk(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const u
             w.walk(l2_buf, sbeg, n_run, wave, &s_next_chunk);
             const unsigned long long t_post = now();
             st[1] += t_post - t_walk;
+            if (sbeg + seg_len >= end) {
+                // !LATE_LOADS: the next region's loads leave with the wave -- its walk of the run's last segment is over and the walk's registers are dead --,
+                // so they travel behind the wait for the slowest wave and the write-back, and the next fill finds them in registers
+                if (!LATE_LOADS) prefetch(rn);
+                lds_barrier();                                    // every wave's adds are in; the write-back below brings the counters back to the invariant
+                if (STAMP) st[3] += now() - t_post;
+                break;
+            }
             // ---- back to the invariant (kg_device.hpp: table_add_pk): a slot counts 1 .. half, the rest goes to the side table.  The walk
             // found every counter there and added less than half, so none has carried; each lane looks at the slots it filled. ----
             lds_barrier();                                        // every wave's adds of this segment are in (and no wave grabs chunks any more)
             // (after the run's last segment -- the only one, normally -- the write-back below does this on its way: the same lane, the same slots)
-            if (sbeg + seg_len < end) {
+            {
 #pragma unroll 1
                 for (int u = 0; u < KP; ++u) {
                     const uint32_t i = (u * BLOCK + tid) * 2;
@@ -2035,13 +2056,14 @@ k_p3_apply_pk(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const u
             }
             if (STAMP) st[3] += now() - t_post;
         }
-        if (PF && rn < r_hi) prefetch(rn);                     // in flight behind the write-back
+        if (LATE_LOADS) prefetch(rn);                          // in flight behind the write-back
 
         // ---- write-back: LDS -> HBM, 16 bytes per lane and store; and back to the invariant on the way ----
         const unsigned long long t_wb = now();
+        const uint32_t tw = fresh_tid();
 #pragma unroll
         for (int u = 0; u < KP; ++u) {
-            const uint32_t i = (u * BLOCK + tid) * 2;
+            const uint32_t i = (u * BLOCK + tw) * 2;
             if (i < S) {
                 u64x2 ww = *reinterpret_cast<const u64x2*>(rk + i);
                 if ((ww.x & cmask) > half || (ww.y & cmask) > half) {        // (rare: a counter in the upper half of its range)
