@@ -30,4 +30,30 @@ KG_LEAN_FN uint32_t ap_advance(uint32_t s, bool go, uint32_t S) {
     return w < t ? w : t;
 }
 
+// The drain's window (ApkWalk::drain_pass): W consecutive slots read in one round trip, of which a k-mer with `budget` slots left to probe may
+// use the first min(W, budget).  Its first EVENT is the lowest of them that is free or holds the remainder; the slots in front of it hold other
+// k-mers.  `at` is the event's offset -- and with no event the number of slots the window has covered, min(W, budget): what the k-mer advances by.
+// A free slot is free whatever its high bits compare to (a remainder of 0 equals a free word's): the low half decides first, as in ap_holds.
+// Per slot: the shift and compare of ap_holds, the 32-bit compare of ap_taken, the scalar or / and with the constant `j < budget`, and two selects;
+// taken from the last slot to the first, so that the lowest event is the one that stays -- no chain of "found already" conditions.
+enum ApEventKind : uint32_t { AP_EV_NONE = 0, AP_EV_HOLDS = 1, AP_EV_FREE = 2 };
+struct ApEvent { uint32_t kind, at; };
+template <int W>
+KG_LEAN_FN ApEvent ap_first_event(const unsigned long long (&word)[W], uint64_t rem, uint32_t cbits, uint32_t budget) {
+    ApEvent e{AP_EV_NONE, budget < (uint32_t)W ? budget : (uint32_t)W};
+#pragma unroll
+    for (int j = W - 1; j >= 0; --j) {
+        const bool fr = !ap_taken((uint32_t)word[j]);
+        const bool ev = (fr || (word[j] >> cbits) == rem) && (uint32_t)j < budget;
+        e.kind = ev ? (fr ? AP_EV_FREE : AP_EV_HOLDS) : e.kind;
+        e.at = ev ? (uint32_t)j : e.at;
+    }
+    return e;
+}
+// slot s + d of a region of S slots, for d <= S (the window's indices: each from s, none from its neighbour)
+KG_LEAN_FN uint32_t ap_slot_at(uint32_t s, uint32_t d, uint32_t S) {
+    const uint32_t t = s + d, w = t - S;
+    return w < t ? w : t;
+}
+
 }  // namespace kg

@@ -244,7 +244,8 @@ static int launch_lds(katgpu_ctx* c, K kern, dim3 grid, dim3 block, size_t lds, 
 // The cycle-stamp diagnostics (KATGPU_L1B_STAMP, _P2X_STAMP, _P2_STAMP, _APPLY_STAMP): a kernel's STAMP instantiation adds its cycles per phase
 // into n counters of the arena's small area (`dev`, behind spill_n; the last of the n counts tiles).  They are zeroed in front of the launch,
 // fetched after it (a synchronisation: these are diagnostics) and every phase's share of phases [0, n_sum) is printed.  line == nullptr: the
-// apply's seven ([0] fill, [1] walk, [2] of it drains, [3] wait for the other waves + sweep, [4] write-back, [5] regions, [6] chunks).
+// apply's nine ([0] fill, [1] walk, [2] of it drains, [3] wait for the other waves + sweep, [4] write-back, [5] regions, [6] chunks, [7] drain
+// passes, [8] their phase-1 iterations).
 struct StampLine { const char* head; int n_shown, n_sum; const char* phase[9]; /* a phase's text around its "%.*f" */ int digits; };
 static const StampLine STAMPS_L1B = {"[katgpu] level-1 (blocks) stamps (wave 0 of every workgroup, cycles summed):", 9, 9,
     {" codes %.*f %%", "  blocks out %.*f %%", " (+ barrier %.*f %%)", "  sweep %.*f %%", " (+ %.*f %%)", "  per bucket %.*f %%", " (+ %.*f %%)", "  placing %.*f %%", " (+ %.*f %%)"}, 1};
@@ -252,7 +253,9 @@ static const StampLine STAMPS_P2X = {"[katgpu] level-2 (blocks in, blocks out) s
     {" wait for the tile %.*f %%", " (+ barrier %.*f %%)", "  ranking + blocks out %.*f %%", " (+ %.*f %%)", "  per sub-bucket %.*f %%", " (+ %.*f %%)", "  placing %.*f %%"}, 1};
 static const StampLine STAMPS_P2 = {"[katgpu] level-2 stamps (lane 0 of every workgroup, cycles summed):", 5, 5,
     {" wait for the tile %.*f %%", "  digit + rank %.*f %%", "  scan %.*f %%", "  staging %.*f %%", "  copy-out %.*f %%"}, 0};
-constexpr int STAMP_AT_APPLY = 8, STAMP_AT = 16;             // where they lie, in counters behind spill_n: the apply's seven, the others' (at most ten)
+constexpr int STAMP_AT_APPLY = 8, STAMP_AT = 18;             // where they lie, in counters behind spill_n: the apply's nine, the others' (at most ten)
+constexpr int STAMP_AREA = 256 / 8;                          // spill_n's carve is 256 bytes (PartArena::carve_from): 32 counters, the level-1 buffer lies behind them
+static_assert(2 <= STAMP_AT_APPLY && STAMP_AT_APPLY + 9 <= STAMP_AT && STAMP_AT + 10 <= STAMP_AREA, "the stamp counters lie behind spill_n and ovf_n, apart, inside spill_n's carve");
 template <typename Launch>
 static int with_stamps(katgpu_ctx* c, unsigned long long* dev, int n, const StampLine* line, Launch launch) {
     unsigned long long st[10];
@@ -263,8 +266,8 @@ static int with_stamps(katgpu_ctx* c, unsigned long long* dev, int n, const Stam
     HIPCHK(c, hipStreamSynchronize(c->stream));
     double tot = line ? 0 : (double)(st[0] + st[1] + st[3] + st[4]);
     if (!line && st[5])
-        fprintf(stderr, "[katgpu] apply stamps (wave 0 of every workgroup, cycles summed): fill %.3g (%.0f %%)  walk %.3g (%.0f %%; drains %.0f %% of the walk)  barrier + sweep %.3g (%.0f %%)  write-back %.3g (%.0f %%); %llu regions, %.1f chunks per wave and region, %.0f cycles per region\n",
-                (double)st[0], 100 * st[0] / tot, (double)st[1], 100 * st[1] / tot, 100.0 * st[2] / std::max(1.0, (double)st[1]), (double)st[3], 100 * st[3] / tot, (double)st[4], 100 * st[4] / tot, st[5], (double)st[6] / st[5], tot / st[5]);
+        fprintf(stderr, "[katgpu] apply stamps (wave 0 of every workgroup, cycles summed): fill %.3g (%.0f %%)  walk %.3g (%.0f %%; drains %.0f %% of the walk, %.2f iterations per pass)  barrier + sweep %.3g (%.0f %%)  write-back %.3g (%.0f %%); %llu regions, %.1f chunks per wave and region, %.0f cycles per region\n",
+                (double)st[0], 100 * st[0] / tot, (double)st[1], 100 * st[1] / tot, 100.0 * st[2] / std::max(1.0, (double)st[1]), (double)st[8] / std::max(1.0, (double)st[7]), (double)st[3], 100 * st[3] / tot, (double)st[4], 100 * st[4] / tot, st[5], (double)st[6] / st[5], tot / st[5]);
     if (!line || !st[n - 1]) return KATGPU_OK;
     for (int i = 0; i < line->n_sum; ++i) tot += (double)st[i];
     char buf[768];
@@ -289,18 +292,19 @@ static int apply_pk(const ApplyLaunch& a) {
                       a.qcap, a.seg_len, g_test_spill_mod, a.zero_fill);
 }
 // probe rounds before the queue: 2 (measured at the bench size, same box: 163 ms per step against 177 with 3 and 198 with inline
-// claims in every round); a table's first round claims inline and keeps 3 -- where launch_apply calls it fresh
+// claims in every round; 1 with the drains' window of four slots: apply 115.1 ms against 110.6 with 2, profiles/apply_drain_parent_vs_branch.txt);
+// a table's first round claims inline and keeps 3 -- where launch_apply calls it fresh
 template <int HB>
 static int apply_pk_shape(const ApplyLaunch& a, uint32_t blk, bool fresh, bool hooked) {
     if (hooked) return apply_pk<1024, 5, HB, false, true, true, 3>(a);
     if (blk == 1024) return fresh ? apply_pk<1024, 5, HB, true, false, true, 3>(a) : apply_pk<1024, 5, HB, false, false, true, 2>(a);
     if (a.g.S <= 4096) {
         if (HB == 1 && g_apply_stamp && fresh)               // diagnostic: the small-region shape of a first round (the bench's second input) with cycle stamps
-            return with_stamps(a.t->ctx, a.spill_n + STAMP_AT_APPLY, 7, nullptr, [&](unsigned long long*) { return apply_pk<512, 4, 1, true, false, true, 3, true>(a); });
+            return with_stamps(a.t->ctx, a.spill_n + STAMP_AT_APPLY, 9, nullptr, [&](unsigned long long*) { return apply_pk<512, 4, 1, true, false, true, 3, true>(a); });
         return fresh ? apply_pk<512, 4, HB, true, false, true, 3>(a) : apply_pk<512, 4, HB, false, false, true, 2>(a);
     }
     if (HB == 1 && g_apply_stamp && !fresh)                  // diagnostic: the bench's shape with cycle stamps (the kernel adds them at spill_n + STAMP_AT_APPLY)
-        return with_stamps(a.t->ctx, a.spill_n + STAMP_AT_APPLY, 7, nullptr, [&](unsigned long long*) { return apply_pk<512, 10, 1, false, false, false, 2, true>(a); });
+        return with_stamps(a.t->ctx, a.spill_n + STAMP_AT_APPLY, 9, nullptr, [&](unsigned long long*) { return apply_pk<512, 10, 1, false, false, false, 2, true>(a); });
     return fresh ? apply_pk<512, 10, HB, true, false, false, 3>(a) : apply_pk<512, 10, HB, false, false, false, 2>(a);
 }
 template <int B, int KP, int HB, bool INL, int QC, bool HK>
@@ -427,7 +431,7 @@ struct PartArena {
         cnt2 = carve<uint32_t>(a, (size_t)MAX_PARTS * MAX_PARTS * 4);
         bend = carve<uint64_t>(a, (size_t)MAX_PARTS * 8);
         carve<uint32_t>(a, (size_t)MAX_PARTS * 4);
-        spill_n = carve<unsigned long long>(a, 256);
+        spill_n = carve<unsigned long long>(a, STAMP_AREA * 8);      // (spill_n, ovf_n and the stamp diagnostics' counters: STAMP_AT_APPLY, STAMP_AT)
         ovf_n = spill_n + 1;
         round_items = std::min<size_t>(want_items, (size_t)((double)(arena_bytes - small_bytes) / per_item));
         l1_items = (round_items + round_items / 24 + fixed_l1 + 15) & ~(size_t)15;      // (a multiple of 16: the level-2 buffer starts on a 128-byte boundary)

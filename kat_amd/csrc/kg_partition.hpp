@@ -1702,7 +1702,8 @@ k_p3_apply2(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const uin
 // No-return adds cannot report a carry out of the count field, so none may happen: a walk finds every counter in 1 .. half (the
 // invariant of packed tables, kg_device.hpp: table_add_pk), covers fewer k-mers than half the range (longer runs are walked in
 // segments; the host passes seg_len) and hands what it left above half to the side table (keyed by the slot) before it ends.
-constexpr int APK_LANE_PROBES = 12;
+constexpr int APK_LANE_PROBES = 12;                         // slots a lane of a drain pass probes before the wave takes its k-mer over
+constexpr int APK_WINDOW = 4;                               // ... in windows of so many per LDS round trip (1, 2 and 4 compile)
 constexpr uint32_t APK_SLOT_SHIFT = 44;
 
 // The walk of one run segment by one wave of the packed apply (k_p3_apply_pk), a function of its own: chunks of 64 U k-mers
@@ -1716,13 +1717,15 @@ struct ApkWalk {
     static constexpr int U = 4 * UG;
     static constexpr uint32_t CH = 64 * U;
     static constexpr uint64_t rem_mask = (1ULL << APK_SLOT_SHIFT) - 1;
+    static constexpr int W = APK_WINDOW;                      // slots a lane of a drain pass probes per iteration
+    static constexpr int LANE_ITERS = (APK_LANE_PROBES + W - 1) / W, EXIT_ITERS = (4 + W - 1) / W;       // the pass's limits are counted in slots
     const PartGeom& g;
     unsigned long long* rk;                                   // the region's image in LDS
     unsigned long long* wq;                                   // this wave's queue
     uint64_t* __restrict__ spill; unsigned long long* __restrict__ spill_n;
     uint32_t S, cb, qcap, lane, rd1, rd2 /* the region's digits: they give a spilled k-mer back */, spill_mod;
     uint32_t& new_distinct;
-    unsigned long long* st;                                   // the kernel's stamps: [2] drains, [6] chunks
+    unsigned long long* st;                                   // the kernel's stamps: [2] drains, [6] chunks, [7] drain passes, [8] their phase-1 iterations
     __device__ __forceinline__ unsigned long long now() const { return STAMP ? (unsigned long long)clock64() : 0ULL; }
     __device__ __forceinline__ uint32_t next_slot(uint32_t s) const { return s + 1 == S ? 0 : s + 1; }
     // +1: the count lives in the low cbits <= 32 bits of the word and the write-back's sweep rules a carry out of it out, so the add is a
@@ -1736,8 +1739,8 @@ struct ApkWalk {
         uint32_t q_n = 0;                                     // entries in this wave's queue (wave-uniform)
         // (Lanes that refill from the queue as they finish, a pass ending when fewer than 16 are busy: measured 141-152 ms against 142 -- the
         // drains' cost is their dependent round trips, not their idle lanes.)
-        // One pass over up to 64 queue entries (taken from the tail).  Phase 1, one entry per lane: dependent probes with the
-        // claim, while at least 8 lanes are busy and for at most APK_LANE_PROBES probes.  Phase 2: what is left is on a long
+        // One pass over up to 64 queue entries (taken from the tail).  Phase 1, one entry per lane: dependent iterations of W slots each with the
+        // claim, while at least 8 lanes are busy and for at most APK_LANE_PROBES slots.  Phase 2: what is left is on a long
         // chain: the WAVE finishes such a k-mer, 64 consecutive slots per read.
         auto drain_pass = [&](bool fin /* nothing will follow: leave no entry behind */) {
             const unsigned long long t_dr = now();
@@ -1752,23 +1755,34 @@ struct ApkWalk {
                 const uint32_t home = place_offset(rem, g.pl, S);
                 budget = S - (slot >= home ? slot - home : slot + S - home);       // probes left before the region has been walked once
             }
+            if (STAMP) st[7] += 1;
 #pragma unroll 1
-            for (int rr = 0; rr < APK_LANE_PROBES; ++rr) {
+            for (int rr = 0; rr < LANE_ITERS; ++rr) {
                 const int busy = __popcll(__ballot(live));
-                if (busy == 0 || (busy < 8 && (fin || rr >= 4))) break;
+                if (busy == 0 || (busy < 8 && (fin || rr >= EXIT_ITERS))) break;
+                if (STAMP) st[8] += 1;
                 if (live) {
-                    unsigned long long w = rk[slot];
-                    if (!ap_taken((uint32_t)w)) {
-                        w = atomicCAS(&rk[slot], 0ULL, (unsigned long long)((rem << cb) | 1ULL));
-                        if (!ap_taken((uint32_t)w)) { ++new_distinct; live = false; }  // claimed, counted
-                    }
-                    if (live) {
-                        if ((w >> cb) == rem) { add1(slot); live = false; }
-                        else {
-                            slot = next_slot(slot);
-                            if (--budget == 0) { spill_rem(rem); live = false; }       // region full: direct path later
-                        }
-                    }
+                    // The window: W consecutive slots from `slot` on, read together -- one round trip where a slot per iteration took W.  It is
+                    // sound although other lanes and waves claim slots meanwhile: a taken slot never changes its remainder during a walk and
+                    // slots only go from free to taken, so the slots in front of the window's first event (a free slot, or one that holds this
+                    // remainder) hold other k-mers whatever happens after the read, and nothing behind the event is used.  A free slot is
+                    // settled by the compare-and-swap, as with one slot: two lanes with the same new remainder walk the same chain, meet at
+                    // the same first free slot, and the loser finds the winner's word there.
+                    unsigned long long win[W];
+#pragma unroll
+                    for (int j = 0; j < W; ++j) win[j] = rk[ap_slot_at(slot, (uint32_t)j, S)];
+                    const ApEvent ev = ap_first_event<W>(win, rem, cb, budget);
+                    const uint32_t at = ap_slot_at(slot, ev.at, S);        // the event's slot; without one, where the next window begins
+                    if (ev.kind == AP_EV_HOLDS) { add1(at); live = false; }
+                    else if (ev.kind == AP_EV_FREE) {
+                        const unsigned long long got = atomicCAS(&rk[at], 0ULL, (unsigned long long)((rem << cb) | 1ULL));
+                        if (!ap_taken((uint32_t)got)) { ++new_distinct; live = false; }                // claimed, counted
+                        else if ((got >> cb) == rem) { add1(at); live = false; }                    // the same k-mer got there first
+                        else { slot = next_slot(at); budget -= ev.at + 1; }                         // someone else's k-mer landed there: go on behind it
+                    } else { slot = at; budget -= ev.at; }
+                    // (With S >= 64 a lane leaves phase 1 after about APK_LANE_PROBES + NR slots, long before its budget comes near W: the cut of the
+                    // window at the budget and this spill are here for completeness.  A region that fills up is met by the wave-wide finish below.)
+                    if (live && budget == 0) { spill_rem(rem); live = false; }                       // the region has been walked once: direct path later
                 }
             }
             // the wave takes over what has had its APK_LANE_PROBES (all that is left, when nothing follows); the rest goes back
@@ -1939,7 +1953,7 @@ template <int BLOCK, int KP /* 16-byte loads per lane that cover a region: two s
           bool LATE_LOADS = true /* where the next region's loads are issued (they travel from HBM into 4 KP VGPRs that the next fill reads): true, behind the barrier that ends the walk;
                             false, by each wave as it leaves the walk, ahead of that barrier (measured at the bench shape only: apply 125.9 -> 118.6 ms per step, profiles/apply_period_parent_vs_branch.txt) */,
           int NR = 3 /* probe rounds before a k-mer goes to the queue */,
-          bool STAMP = false /* diagnostic (KATGPU_APPLY_STAMP): wave 0's cycles per phase, added into spill_n[8 ..]: [8] fill, [9] walk, [10] of it drains, [11] wait for the other waves + sweep, [12] write-back, [13] regions, [14] chunks */,
+          bool STAMP = false /* diagnostic (KATGPU_APPLY_STAMP): wave 0's cycles per phase, added into spill_n[8 ..]: [8] fill, [9] walk, [10] of it drains, [11] wait for the other waves + sweep, [12] write-back, [13] regions, [14] chunks, [15] drain passes, [16] their phase-1 iterations */,
           int UG = 1 /* groups of the level-2 buffer a lane takes per chunk: 4 UG k-mers in flight per lane and probe round.  Two measured
                         171.9 ms per step against 168.3 with one at the bench's shape (same box, round 4): the walk is bound by VALU issue at four waves per
                         SIMD (cycle stamps: 5.3 K cycles per chunk and wave = four waves x ~350 wave instructions x 4 cycles), not by LDS round trips */>
@@ -1990,7 +2004,7 @@ k_p3_apply_pk(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const u
         for (int u = 0; u < KP; ++u) { const uint32_t i = (u * BLOCK + tt) * 2; kq[u] = *reinterpret_cast<const u32x4*>(t.keys + base + (i < S ? i : 0)); }    // clamped, unconditional: stays in registers
     };
 
-    unsigned long long st[7] = {0, 0, 0, 0, 0, 0, 0};
+    unsigned long long st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     auto now = [&]() -> unsigned long long { return STAMP ? (unsigned long long)clock64() : 0ULL; };
     uint32_t r = next_region(g.b_lo * g.P2 + blockIdx.x);
     prefetch(r);
@@ -2078,7 +2092,7 @@ k_p3_apply_pk(DevTable t, PartGeom g, const uint64_t* __restrict__ off2, const u
         if (STAMP) { st[4] += now() - t_wb; st[5] += 1; }
         r = rn;
     }
-    if (STAMP && tid == 0) { for (int i = 0; i < 7; ++i) atomicAdd(&spill_n[8 + i], st[i]); }
+    if (STAMP && tid == 0) { for (int i = 0; i < 9; ++i) atomicAdd(&spill_n[8 + i], st[i]); }
     flush_distinct(t, new_distinct);
 }
 
