@@ -102,7 +102,6 @@ static const uint64_t g_test_round_items = hook("KATGPU_TEST_ROUND_ITEMS") ? str
 // share of the free HBM the partition arena may take (multi-GPU runs may lower it; bench.py sets 0.75 there)
 static const double g_arena_fraction = getenv("KATGPU_ARENA_FRACTION") ? std::min(0.95, std::max(0.05, atof(getenv("KATGPU_ARENA_FRACTION")))) : 0.85;
 static const uint32_t g_p1_wgs = hook("KATGPU_P1_WGS") ? std::max<uint32_t>(1, (uint32_t)strtoul(hook("KATGPU_P1_WGS"), nullptr, 10)) : 3;   // level-1 workgroups per CU
-static const bool g_l1_lean = hook_u64("KATGPU_L1_LEAN", 1) != 0;   // A/B: 0 = level 1's ranking sweep in its 64-bit form (kg_l1_lean.hpp is the 32-bit one)
 // level 1 without its counting pass (kg_partition.hpp: k_p1v2_scatter<true>, one fixed-capacity segment per workgroup and bucket):
 // 0 = never, 1 = for rounds of at least 64 M k-mers (the default), 2 = always (tests)
 static const uint32_t g_l1_fast = hook("KATGPU_L1_FAST") ? (uint32_t)strtoul(hook("KATGPU_L1_FAST"), nullptr, 10) : 1;
@@ -124,6 +123,7 @@ static const bool g_apply_stamp = hook_u64("KATGPU_APPLY_STAMP", 0) != 0;       
 static bool part_geometry(const DevTable& d, PartGeom* g) {
     g->R = d.n_regions; g->S = d.region_slots; g->P1 = d.p1; g->P2 = d.p2; g->l2 = d.l2;
     g->b_lo = 0; g->b_hi = d.p1;
+    g->l1_stride = 0; g->l1_real = 0; g->spill_cap = 0; g->l2_trim = 0;        // (a round's: count_partitioned)
     g->pl = place_make(d.k, d.p1, d.n1, d.l2);
     g->hb = l2_hi_bytes(g->pl.rb);
     g->hb1 = l2_hi_bytes(g->pl.n1);
@@ -132,17 +132,19 @@ static bool part_geometry(const DevTable& d, PartGeom* g) {
     // the apply kernels hold a region of whole 16-byte lines, at least a wave's worth of slots, in LDS
     return d.k <= 32 && g->pl.rb <= 63 /* all-ones is "no item" */ && g->P1 <= MAX_PARTS && g->P2 <= MAX_PARTS && g->S % 4 == 0 && g->S >= 64 && g->S <= AP2_MAX_SLOTS;
 }
-// bytes of partition arena per k-mer of a round: level-1 buffer (8 B + the segment slack 1/24), level-2 buffer (4 + hb B, that
-// slack again + the run slack 1/16 + the group padding's allowance 2 * 1024 / tile), overflow list (8 B / 32)
-static double l2_items_per_l1_item(uint32_t hb) { return 1 + 1.0 / 16 + 2.0 * MAX_PARTS / l2_tile_items(hb); }
+// (bytes of partition arena per k-mer of a round, by shape: kg_arena_plan.hpp)
+static_assert(PLAN_MAX_PARTS == MAX_PARTS && PLAN_L1_TILE_STARTS == P1_TILE_STARTS && PLAN_L1B_TILE_STARTS == L1B_TILE_STARTS && PLAN_L1B_ITEMS == L1B_ITEMS && PLAN_L1B_BYTES == L1B_BYTES,
+              "kg_arena_plan.hpp's copies of the kernels' constants");
 // buckets per pass of level 2 + apply: a CU-full when the buckets are a whole number of those (alloc_dev_table sees to it), else all
 static const uint32_t g_test_pass_buckets = hook("KATGPU_TEST_PASS_BUCKETS") ? (uint32_t)strtoul(hook("KATGPU_TEST_PASS_BUCKETS"), nullptr, 10) : 0;   // tests: passes of this many buckets
 static uint32_t pass_buckets(uint32_t p1, uint32_t n_cu) {
     if (g_test_pass_buckets) return std::max<uint32_t>(1, std::min(p1, g_test_pass_buckets));
     return n_cu && p1 > n_cu && p1 % n_cu == 0 ? n_cu : p1;
 }
-// ... of which the level-2 buffer holds one pass = 1 / passes of a round
-static double arena_bytes_per_item(uint32_t hb, uint32_t passes) { return 8.0 * (1 + 1.0 / 24) + l2_bytes_per_item(hb) * (1 + 1.0 / 24) * l2_items_per_l1_item(hb) / passes + 0.25 + 0.02; }
+// (the level-2 buffer holds one pass = 1 / passes of a round)
+// the table's shape selects level 1's block edition (kg_l1_blocks.hpp): plan_level1 runs it, PartArena carves the level-1 buffer for it
+static const bool g_l1_lean = hook_u64("KATGPU_L1_LEAN", 1) != 0;   // A/B: 0 = level 1's ranking sweep in its 64-bit form (kg_l1_lean.hpp is the 32-bit one)
+static bool l1_blocks_shape(const PartGeom& g, uint32_t k) { return g_l1_lean && lean_applies(k, g.pl.n1) && g.P1 <= 512 && g.hb1 == 2; }
 
 static const bool g_test_grow_nomem = hook("KATGPU_TEST_GROW_NOMEM") != nullptr;   // tests: table growth "fails" while the arena is busy
 
@@ -398,32 +400,33 @@ static int launch_apply(katgpu_table* t, const PartGeom& g, const uint64_t* off2
     return KATGPU_OK;
 }
 
-// ---- the arena of a call: [hist1 | offs | l1_off | off2 | cnt2 | bend | spill_n, ovf_n | L1 buffer | L2 buffer | overflow list] ----
-// L1 buffer: a round's k-mers + 1/24 + 64 per workgroup and bucket (segment slack of k_p1v2_scatter<true>);
-// L2 buffer: items of 4 + hb bytes in groups of four (kg_partition.hpp "the level-2 buffer"): the L1 count + 1/16 + 16 per region
-// (capacity slack of k_p2_fast) + two items per tile and region (group padding); overflow list: 1/32.
-// 14.8 bytes per k-mer of a round at hb = 1 (k = 27 at the bench size), 18.5 at hb = 4 -- with one pass; the level-2 buffer
-// holds one PASS of level 2 + apply (a CU-full of buckets, see level2_and_apply): 11.7 bytes with two passes.
-constexpr size_t SEG_PAD = 64;
+// ---- the arena of a call: [hist1 | offs | l1_off | off2 | cnt2 | bend | spill_n, ovf_n | L1 buffer | guard | L2 buffer | guard | overflow list | guard] ----
+// The three buffers' sizes are kg_arena_plan.hpp's (arena_carve): 9.70 bytes per k-mer of a round at hb = 1 (k = 27 at the bench size) with the
+// dense level-1 buffer, long runs and two passes -- the level-2 buffer holds one PASS of level 2 + apply (a CU-full of buckets, see
+// level2_and_apply) --; 11.9 with 8 bytes per level-1 item and the group editions' run allowance, 18.5 at hb = 4 with one pass.
+constexpr uint8_t GUARD_BYTE = 0xA5;
 struct PartArena {
     // sizes, from the table's geometry (the constructor): item width the level-2 buffer is carved for (a table that grows has more regions: never more
-    // remainder bits), passes of a round (rounded down: the buffer never too small), bytes per k-mer of a round, the fixed parts
-    uint32_t hb, passes; double per_item; size_t fixed_l1, small_bytes;
+    // remainder bits), passes of a round (rounded down: the buffer never too small), the table's regions, whether its shape selects level 1's
+    // block edition, the small arrays' bytes, the most a k-mer of a round can cost (what ensure_arena asks for)
+    uint32_t hb, passes, n_cu; uint64_t regions; bool blocks_shape; double per_item_max; size_t small_bytes;
     // the carve (carve_from) of an arena for rounds of at most want_items k-mers; the stamp diagnostics' counters lie behind spill_n, ovf_n
     uint32_t* hist1; uint64_t* offs; uint64_t* l1_off; uint64_t* off2; uint32_t* cnt2; uint64_t* bend; unsigned long long* spill_n; unsigned long long* ovf_n;
-    uint8_t* l1_buf;             // level-1 items, groups of 4, 8 bytes of room per item (kg_partition.hpp "the level-1 buffer")
+    uint8_t* l1_buf;             // level-1 items: groups of 4 with 8 bytes of room per item (kg_partition.hpp "the level-1 buffer"), or -- cv.dense -- blocks of ten
     uint8_t* l2_buf;             // level-2 items, groups of 4 (5-byte items: 64-byte blocks of 12)
     uint64_t* ovf_buf; uint64_t ovf_cap;
-    size_t round_items, l1_items, l2_items;
-    PartArena(const PartGeom& g0, uint32_t W, uint32_t n_cu) : hb(g0.hb), passes(std::max<uint32_t>(1, g0.P1 / pass_buckets(g0.P1, n_cu))), per_item(arena_bytes_per_item(hb, passes)) {
-        fixed_l1 = (size_t)W * MAX_PARTS * SEG_PAD;
-        const size_t fixed_l2 = (size_t)((double)fixed_l1 * l2_items_per_l1_item(hb) / passes) + (size_t)MAX_PARTS * MAX_PARTS * P2_RUN_SLACK + 8192;
+    ArenaCarve cv;
+    size_t round_items, l1_bytes, l2_items;
+    PartArena(const PartGeom& g0, uint32_t k, uint32_t W, uint32_t n_cu_) : hb(g0.hb), passes(std::max<uint32_t>(1, g0.P1 / pass_buckets(g0.P1, n_cu_))), n_cu(n_cu_), regions(g0.R), blocks_shape(l1_blocks_shape(g0, k)) {
+        per_item_max = arena_bytes_per_item(hb, passes, false, false);
         small_bytes = align_up((size_t)W * MAX_PARTS * 4, 256) + align_up((size_t)W * MAX_PARTS * 8, 256) +   /* W <= 4 * CUs */
                       align_up((MAX_PARTS + 1) * 8, 256) + align_up(((size_t)MAX_PARTS * MAX_PARTS + 1) * 8, 256) +
-                      align_up((size_t)MAX_PARTS * MAX_PARTS * 4, 256) + align_up((size_t)MAX_PARTS * 8, 256) + align_up((size_t)MAX_PARTS * 4, 256) + 256 +
-                      (fixed_l1 + fixed_l2 + 4096) * 8 + 4096;
+                      align_up((size_t)MAX_PARTS * MAX_PARTS * 4, 256) + align_up((size_t)MAX_PARTS * 8, 256) + align_up((size_t)MAX_PARTS * 4, 256) + 256;
     }
-    void carve_from(uint8_t* a, size_t arena_bytes, uint32_t W, size_t want_items) {
+    size_t fixed_bytes(uint32_t W) const { return small_bytes + (size_t)arena_fixed_bytes(hb, passes, W, n_cu, false, false); }      // what an arena needs before its first k-mer
+    // false: the buffers would end beyond the arena (cannot happen: arena_carve sizes them from arena_bytes; the caller fails the call)
+    bool carve_from(uint8_t* a, size_t arena_bytes, uint32_t W, size_t want_items) {
+        uint8_t* const a0 = a;
         hist1 = carve<uint32_t>(a, (size_t)W * MAX_PARTS * 4);
         offs = carve<uint64_t>(a, (size_t)W * MAX_PARTS * 8);
         l1_off = carve<uint64_t>(a, (MAX_PARTS + 1) * 8);
@@ -433,15 +436,34 @@ struct PartArena {
         carve<uint32_t>(a, (size_t)MAX_PARTS * 4);
         spill_n = carve<unsigned long long>(a, STAMP_AREA * 8);      // (spill_n, ovf_n and the stamp diagnostics' counters: STAMP_AT_APPLY, STAMP_AT)
         ovf_n = spill_n + 1;
-        round_items = std::min<size_t>(want_items, (size_t)((double)(arena_bytes - small_bytes) / per_item));
-        l1_items = (round_items + round_items / 24 + fixed_l1 + 15) & ~(size_t)15;      // (a multiple of 16: the level-2 buffer starts on a 128-byte boundary)
-        l2_items = ((size_t)((double)l1_items * l2_items_per_l1_item(hb) / passes) + (size_t)MAX_PARTS * MAX_PARTS * P2_RUN_SLACK + 4096 + 11) / 12 * 12;
+        if ((size_t)(a - a0) > small_bytes || arena_bytes <= small_bytes) return false;
+        cv = arena_carve(arena_bytes - small_bytes, want_items, hb, passes, W, n_cu, regions, blocks_shape, g_l1_fast, g_test_p2_ovf_cap);
+        round_items = cv.round_items; l1_bytes = cv.l1_bytes; l2_items = cv.l2_items; ovf_cap = cv.ovf_cap;
         l1_buf = a;
-        l2_buf = l1_buf + l1_items * 8;
-        ovf_buf = (uint64_t*)(l2_buf + align_up(l2_buffer_bytes(hb, l2_items), 16));
-        ovf_cap = g_test_p2_ovf_cap ? g_test_p2_ovf_cap : round_items / 32 + 1024;
+        l2_buf = l1_buf + cv.l1_bytes + ARENA_GUARD;
+        ovf_buf = (uint64_t*)(l2_buf + cv.l2_bytes + ARENA_GUARD);
+        return (size_t)((uint8_t*)(ovf_buf + ovf_cap) + ARENA_GUARD - a0) <= arena_bytes;
     }
+    uint8_t* guard(int i) const { return i == 0 ? l1_buf + cv.l1_bytes : i == 1 ? l2_buf + cv.l2_bytes : (uint8_t*)(ovf_buf + ovf_cap); }
 };
+static const char* const GUARD_NAME[3] = {"level-1 buffer", "level-2 buffer", "overflow list"};
+// KATGPU_TESTING: a fixed byte pattern behind each of the three buffers, checked after every round -- a kernel that wrote beyond its buffer fails the call
+static int guards_set(katgpu_ctx* c, const PartArena& A) {
+    if (!g_testing) return KATGPU_OK;
+    for (int i = 0; i < 3; ++i) HIPCHK(c, hipMemsetAsync(A.guard(i), GUARD_BYTE, ARENA_GUARD, c->stream));
+    return KATGPU_OK;
+}
+static int guards_check(katgpu_ctx* c, const PartArena& A) {
+    if (!g_testing) return KATGPU_OK;
+    std::vector<uint8_t> h(3 * ARENA_GUARD);
+    for (int i = 0; i < 3; ++i) HIPCHK(c, hipMemcpyAsync(h.data() + i * ARENA_GUARD, A.guard(i), ARENA_GUARD, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < 3; ++i)
+        for (size_t j = 0; j < ARENA_GUARD; ++j)
+            if (h[i * ARENA_GUARD + j] != GUARD_BYTE)
+                return fail(c, KATGPU_ERR_DEVICE, "partition arena: the guard behind the %s was written (byte %zu)", GUARD_NAME[i], j);
+    return KATGPU_OK;
+}
 // level 1 tallies the all-ones key of what it reads (k = 32, not canonical; the segmented editions always write the counter): a round that is
 // abandoned or repeated puts the table's own tally back
 static int restore_ones(katgpu_table* t) { katgpu_ctx* c = t->ctx; HIPCHK(c, hipMemcpyAsync(&t->dv.ctrs[CTR_ONES], &t->ones, sizeof(uint64_t), hipMemcpyHostToDevice, c->stream)); return KATGPU_OK; }
@@ -460,18 +482,7 @@ static int probe_items_per_start(katgpu_table* t, const PartGeom& g, const PartA
     // (the probe's all-ones tally must not count twice: the real count pass over the same prefix follows)
     return t->dv.k == 32 && !t->dv.canonical ? restore_ones(t) : KATGPU_OK;
 }
-// window starts of the next round, of `left`: what fills the buffers, the remaining rounds balanced
-static size_t round_starts(size_t left, size_t round_items, double items_per_start) {
-    size_t m = left;                                                           // items <= starts: this always fits
-    if (m > round_items) m = std::min(m, (size_t)((double)round_items / items_per_start * 0.98));
-    if (m < left) {
-        const size_t rounds_left = (left + m - 1) / m;
-        m = (left + rounds_left - 1) / rounds_left;
-        m += P1_TILE_STARTS - m % P1_TILE_STARTS;                              // whole tiles, keeps the next round 16-byte aligned
-        m = std::min(m, left);
-    }
-    return m;
-}
+// (window starts of the next round: kg_arena_plan.hpp's round_starts)
 
 // ---- level 1 ----
 // Segmented editions (one pass, fixed-capacity segments) when the round is big enough for their fixed costs; the exact editions
@@ -481,29 +492,20 @@ enum class L1Edition { Blocks, SegLean512, SegLean1024, SegPlain512, SegPlain102
 static const char* const L1_EDITION_NAME[] = {"Blocks", "SegLean512", "SegLean1024", "SegPlain512", "SegPlain1024", "ExactLean", "ExactPlain"};   // (KATGPU_TRACE)
 struct L1Plan {
     L1Edition edition; bool seg /* a segmented edition: level 2 reads segments (blocks of ten from Blocks, else groups) */; uint32_t wgs /* workgroups (<= W: the small arrays hold them) */; uint64_t n_tiles, tiles_per_wg;
-    uint64_t seg_cap, cap_plain, stride64;   // segmented: slots of a segment; k-mers it is expected to take at most (what the spill list must hold: 8 bytes each); bytes of a bucket (l1_bucket_base's + 32)
+    uint64_t seg_cap, cap_plain, stride64;   // segmented: slots of a segment; k-mers it is expected to take at most; bytes of a bucket (kg_arena_plan.hpp: l1_segments)
 };
-static L1Plan plan_level1(const PartGeom& g, uint32_t k, size_t m, uint64_t est_items, uint32_t W, uint32_t n_cu, size_t l1_items, bool seg_wanted) {
+static L1Plan plan_level1(const PartGeom& g, uint32_t k, size_t m, uint64_t est_items, uint32_t W, uint32_t n_cu, size_t l1_bytes, bool seg_wanted) {
     const bool lean = g_l1_lean && lean_applies(k, g.pl.n1);
     const bool pb512 = g.P1 <= 512;
-    const bool l1b = lean && pb512 && g.hb1 == 2;
+    const bool l1b = l1_blocks_shape(g, k);
     const uint64_t n_tiles = (m + P1_TILE_STARTS - 1) / P1_TILE_STARTS;
     L1Plan pl;
     pl.wgs = l1b ? n_cu : W;
     pl.n_tiles = l1b ? (m + L1B_TILE_STARTS - 1) / L1B_TILE_STARTS : n_tiles;
-    uint64_t seg_cap = est_items / ((uint64_t)pl.wgs * g.P1);
-    seg_cap += seg_cap / 24 + SEG_PAD;
-    if (g_test_l1_cpb) seg_cap = std::min<uint64_t>(seg_cap, g_test_l1_cpb);
-    if (l1b) seg_cap = (seg_cap + L1B_ITEMS - 1) / L1B_ITEMS * L1B_ITEMS;       // whole blocks: every slot may hold a k-mer
-    pl.cap_plain = seg_cap;
-    // groups (kg_partition.hpp: k_p1v2_scatter): a bucket's k-mers of a tile are padded to whole groups, 1.5 items per tile and bucket on average
-    if (!l1b && g.hb1 != 4 && !g_test_l1_cpb) seg_cap += std::min<uint64_t>(3 * seg_cap, 2 * ((pl.n_tiles + pl.wgs - 1) / pl.wgs));
-    if (!l1b) seg_cap = (seg_cap + 3) & ~3ULL;                                  // whole groups
-    pl.seg_cap = seg_cap;
-    pl.stride64 = l1b ? align_up(8 * (uint64_t)pl.wgs * pl.cap_plain + 32, 64)      // (blocks start on 64-byte boundaries; 6.4 bytes per item lie inside the 8)
-                      : std::max<uint64_t>(8 * (uint64_t)pl.wgs * pl.cap_plain, (uint64_t)(4 + g.hb1) * pl.wgs * seg_cap) + 32;
-    pl.seg = seg_wanted && pl.stride64 * g.P1 <= (uint64_t)l1_items * 8 &&
-             seg_cap < (1u << 24) && pl.stride64 <= 0xFFFFFFFFULL /* the kernel's segment arithmetic: 24 x 8 and 32 x 32 -> 64 bits */;
+    // the segments' capacity and the buckets' stride (kg_arena_plan.hpp): the block edition's stride is its segments' blocks, 6.4 bytes per item
+    const L1Segments sg = l1_segments(l1b, g.P1, g.hb1, pl.wgs, est_items, (pl.n_tiles + pl.wgs - 1) / pl.wgs, g_test_l1_cpb, l1_bytes);
+    pl.cap_plain = sg.cap_plain; pl.seg_cap = sg.seg_cap; pl.stride64 = sg.stride;
+    pl.seg = seg_wanted && sg.fits;
     if (pl.seg) pl.edition = l1b ? L1Edition::Blocks : lean ? (pb512 ? L1Edition::SegLean512 : L1Edition::SegLean1024) : (pb512 ? L1Edition::SegPlain512 : L1Edition::SegPlain1024);
     else { pl.edition = lean ? L1Edition::ExactLean : L1Edition::ExactPlain; pl.wgs = W; pl.n_tiles = n_tiles; }
     pl.tiles_per_wg = (pl.n_tiles + pl.wgs - 1) / pl.wgs;
@@ -541,14 +543,17 @@ static int launch_l1_scatter(katgpu_table* t, const PartGeom& g, const L1Plan& l
 // Level 1 of a round of m starts.  A segmented edition: one launch; how many k-mers it wrote is not needed (and not known: *items stays the
 // estimate).  An exact edition: count, scan, scatter; *items = the round's k-mers, and when they are more than the buffers hold (denser than
 // the prefix suggested) nothing is scattered: the caller repeats the round smaller.
-static int level1(katgpu_table* t, const PartGeom& g, const L1Plan& l1, const PartArena& A, const uint8_t* p, size_t m, double items_per_start, uint64_t* items) {
+static int level1(katgpu_table* t, const PartGeom& g, const L1Plan& l1, const PartArena& A, size_t cap_items, const uint8_t* p, size_t m, double items_per_start, uint64_t* items) {
     katgpu_ctx* c = t->ctx;
     const uint64_t nb = m + t->dv.k - 1;
     if (l1.seg) {
         int rc;
+        // (plan_level1 made the plan for this buffer: no launch on one whose last bucket ends beyond it)
+        if (l1.stride64 * g.P1 > A.l1_bytes || (uint64_t)l1.wgs * (l1.edition == L1Edition::Blocks ? l1.seg_cap / L1B_ITEMS * L1B_BYTES : (4 + g.hb1) * l1.seg_cap) > l1.stride64)
+            return fail(c, KATGPU_ERR_DEVICE, "partition round: %u buckets of %llu bytes end beyond the level-1 buffer of %zu bytes", g.P1, (unsigned long long)l1.stride64, A.l1_bytes);
         { ScopedTimer tm(c, KATGPU_K_PART_L1S, *items); rc = launch_l1_scatter(t, g, l1, A, p, nb); }
-        if (!rc && g_trace) fprintf(stderr, "[katgpu] partition round (segmented level 1%s): %zu starts, ~%llu items, %llu k-mers per segment (arena %.1f GB)\n", l1.edition == L1Edition::Blocks ? ", blocks of ten" : "", m,
-                                    (unsigned long long)*items, (unsigned long long)l1.seg_cap, c->arena_bytes / 1e9);
+        if (!rc && g_trace) fprintf(stderr, "[katgpu] partition round (segmented level 1%s): %zu starts, ~%llu items, %llu k-mers per segment (arena %.1f GB; capacity %zu items, %s, stride %llu)\n", l1.edition == L1Edition::Blocks ? ", blocks of ten" : "", m,
+                                    (unsigned long long)*items, (unsigned long long)l1.seg_cap, c->arena_bytes / 1e9, cap_items, L1_EDITION_NAME[(int)l1.edition], (unsigned long long)l1.stride64);
         return rc;
     }
     {
@@ -558,9 +563,13 @@ static int level1(katgpu_table* t, const PartGeom& g, const L1Plan& l1, const Pa
     }
     HIPCHK(c, hipMemcpyAsync(items, &A.l1_off[g.P1], sizeof *items, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (g_trace) fprintf(stderr, "[katgpu] partition round: %zu starts -> %llu items (buffer %zu items, arena %.1f GB, ratio %.3f)\n", m, (unsigned long long)*items, A.round_items, c->arena_bytes / 1e9, items_per_start);
-    if (*items > A.round_items) return t->dv.k == 32 && !t->dv.canonical ? restore_ones(t) : KATGPU_OK;
+    if (g_trace) fprintf(stderr, "[katgpu] partition round: %zu starts -> %llu items (buffer %zu items, arena %.1f GB, ratio %.3f; capacity %zu items, %s, stride 0)\n", m, (unsigned long long)*items, A.round_items, c->arena_bytes / 1e9, items_per_start,
+                         cap_items, L1_EDITION_NAME[(int)l1.edition]);
+    if (*items > cap_items) return t->dv.k == 32 && !t->dv.canonical ? restore_ones(t) : KATGPU_OK;
     if (!*items) return KATGPU_OK;
+    // (the exact layout: 8 bytes per item and 32 per bucket; cap_items is sized so that this holds -- and no scatter is launched where it does not)
+    if (l1_bucket_base(*items, g.P1) + 32 > A.l1_bytes)
+        return fail(c, KATGPU_ERR_DEVICE, "partition round: %llu items of an exact level 1 end beyond the level-1 buffer of %zu bytes", (unsigned long long)*items, A.l1_bytes);
     ScopedTimer tm(c, KATGPU_K_PART_L1S, *items);
     return launch_l1_scatter(t, g, l1, A, p, nb);
 }
@@ -648,12 +657,15 @@ static int level2_and_apply(katgpu_table* t, PartGeom& g, const L1Plan& l1, cons
     HIPCHK(c, hipStreamSynchronize(c->stream));
     auto lbeg = [&](uint32_t b) -> uint64_t { return seg ? (uint64_t)b * g.l1_real : h_l1_off[b]; };      // k-mers before bucket b (segmented: their bound)
     const uint32_t tile2 = l2_tile_items(g.hb);
-    auto pass_extent = [&](uint32_t b_lo, uint32_t b_hi) -> uint64_t {       // bound of what level 2 writes for these buckets, in items (either edition)
-        const uint64_t nn = lbeg(b_hi) - lbeg(b_lo);
-        return nn + nn / 16 + 2ULL * g.P2 * (nn / tile2 + 1) + (uint64_t)(b_hi - b_lo) * g.P2 * P2_RUN_SLACK + 64;
+    auto pass_extent = [&](uint32_t b_lo, uint32_t b_hi) -> uint64_t {       // bound of what level 2 writes for these buckets, in items (either edition: kg_arena_plan.hpp)
+        return p2_pass_extent(lbeg(b_hi) - lbeg(b_lo), b_hi - b_lo, g.P2, tile2, g.l2_trim != 0);
     };
     uint32_t step = pass_buckets(g.P1, (uint32_t)c->n_cu);
     auto fits = [&](uint32_t st) { for (uint32_t b = 0; b < g.P1; b += st) if (pass_extent(b, std::min(g.P1, b + st)) > A.l2_items) return false; return true; };
+    if (!seg && A.cv.big) {              // exact level 1: the caller chose the runs' form from an estimate of the buckets; now their counts are known
+        g.l2_trim = 0;
+        if (!fits(step) && l2_trims(g.hb, items, g.R)) g.l2_trim = 1;       // (the untrimmed passes do not fit: the trimmed form before any pass is halved)
+    }
     while (step > 1 && !fits(step)) step = (step + 1) / 2;
     if (!fits(step)) {
         *end = RoundEnd::DirectPath;
@@ -668,7 +680,8 @@ static int level2_and_apply(katgpu_table* t, PartGeom& g, const L1Plan& l1, cons
     for (uint32_t b_lo = 0; b_lo < g.P1; b_lo += step) {
         g.b_lo = b_lo; g.b_hi = std::min(g.P1, b_lo + step);
         const uint64_t pass_items = std::max<uint64_t>(1, (uint64_t)((double)items * (g.b_hi - g.b_lo) / g.P1));
-        // this pass's part of the level-1 buffer, dead once its level 2 is through: the pass's spill list (room for 8 bytes per k-mer)
+        // this pass's part of the level-1 buffer, dead once its level 2 is through: the pass's spill list (8-byte entries: room for one per k-mer, 0.8 per k-mer
+        // behind level 1's block edition -- a list that is too short is counted, not written, and fails the call below)
         auto l1_at = [&](uint32_t b) -> uint64_t { return seg ? (uint64_t)b * g.l1_stride : l1_bucket_base(lbeg(b), b); };
         uint64_t* spill_buf = (uint64_t*)(A.l1_buf + l1_at(b_lo));
         g.spill_cap = (l1_at(g.b_hi) - l1_at(b_lo)) / 8;
@@ -745,16 +758,19 @@ static int count_partitioned(katgpu_table* t, const uint8_t* dev_bases, size_t n
     const uint32_t W = n_cu * std::min<uint32_t>(g_p1_wgs, 4);                     // level-1 workgroups (rows of hist1 / offs)
     PartGeom g0;
     if (!part_geometry(t->dv, &g0)) return KATGPU_OK;                              // direct path
-    PartArena A(g0, W, n_cu);
+    PartArena A(g0, k, W, n_cu);
     size_t want_items = n_starts;
     if (g_test_round_items) want_items = std::min<size_t>(want_items, g_test_round_items);
     bool usable = false;
-    int rc = ensure_arena(c, A.small_bytes, 18, want_items, A.small_bytes + (size_t)((A.per_item + 0.5) * (double)want_items), "", &usable);
+    int rc = ensure_arena(c, A.fixed_bytes(W), 18, want_items, A.fixed_bytes(W) + (size_t)((A.per_item_max + 0.5) * (double)want_items), "", &usable);
     if (rc || !usable) return rc;                                                  // (no arena: direct path)
     ArenaBusy busy(c);
-    A.carve_from(c->arena, c->arena_bytes, W, want_items);
+    if (!A.carve_from(c->arena, c->arena_bytes, W, want_items)) return fail(c, KATGPU_ERR_DEVICE, "partition arena: the carve of %zu bytes ends beyond the arena", c->arena_bytes);
+    rc = guards_set(c, A);
+    if (rc) return rc;
     if (!g_test_round_items && A.round_items < ((size_t)1 << 20) && A.round_items < n_starts) return KATGPU_OK;
     bool p2_fast_ok = g_p2_fast != 0, l1_fast_ok = g_l1_fast != 0;
+    RoundCaps caps;                               // a round's capacity by the edition that runs it (kg_arena_plan.hpp): the exact one once a round ran, or has to run, the exact level 1
     double items_per_start = 1.0;
     size_t pos = 0;
     bool ratio_known = false;
@@ -773,24 +789,33 @@ static int count_partitioned(katgpu_table* t, const uint8_t* dev_bases, size_t n
         const size_t left = n_starts - pos;
         const uint8_t* p = dev_bases + pos;
         // (the segmented level 1 sizes its segments from this ratio, so it wants it even when one round takes everything)
-        if (!ratio_known && !g_test_round_items && (left > A.round_items || (l1_fast_ok && left >= ((size_t)64 << 20)))) {
+        // what a round holds depends on the edition that runs it: the exact level 1 places fewer k-mers in a dense buffer than the block edition
+        const size_t cap_items = caps.cap(A.cv, l1_fast_ok && l1_blocks_shape(g, k));
+        if (!ratio_known && !g_test_round_items && (left > cap_items || (l1_fast_ok && left >= ((size_t)64 << 20)))) {
             rc = probe_items_per_start(t, g, A, W, p, left, &items_per_start);
             if (rc) return rc;
             ratio_known = true;
         }
-        const size_t m = round_starts(left, A.round_items, items_per_start);
+        const size_t m = round_starts(left, cap_items, items_per_start);
         t->count_bound = 0xFFFFFFFFULL;          // the apply kernel chains its own carries; a later direct launch sweeps first
         const uint64_t est_items = (uint64_t)((double)m * items_per_start);
         const bool seg_wanted = l1_fast_ok && (g_l1_fast == 2 || (ratio_known && est_items >= ((uint64_t)64 << 20)));
-        const L1Plan l1 = plan_level1(g, k, m, est_items, W, n_cu, A.l1_items, seg_wanted);
+        const L1Plan l1 = plan_level1(g, k, m, est_items, W, n_cu, A.l1_bytes, seg_wanted);
+        if (l1.edition != L1Edition::Blocks && cap_items > caps.cap(A.cv, false)) { caps.exact_from_here(); continue; }      // sized for the block edition, which does not run: again with the exact capacity
         g.l1_stride = l1.seg ? l1.stride64 : 0;
         g.l1_real = l1.seg ? (uint64_t)l1.wgs * l1.cap_plain : 0;
+        {   // the runs' slack: trimmed only where a pass does not fit the level-2 buffer with the untrimmed form (kg_arena_plan.hpp: round_trims)
+            const uint32_t nb = std::min(g.P1, pass_buckets(g.P1, n_cu));
+            const uint64_t nn = l1.seg ? nb * g.l1_real : (uint64_t)((double)est_items * nb / g.P1 * (1 + 1.0 / 64)) + 1024;
+            g.l2_trim = round_trims(A.cv, g.hb, est_items, g.R, nn, nb, g.P2) ? 1u : 0u;
+        }
         HIPCHK(c, hipMemsetAsync(A.spill_n, 0, 2 * sizeof(unsigned long long), c->stream));          // spill_n, ovf_n
         uint64_t items = est_items;
-        rc = level1(t, g, l1, A, p, m, items_per_start, &items);
+        rc = level1(t, g, l1, A, cap_items, p, m, items_per_start, &items);
         if (rc) return rc;
-        if (!l1.seg && items > A.round_items) {   // (exact level 1) denser than the prefix suggested: redo this round smaller
+        if (!l1.seg && items > cap_items) {       // (exact level 1) denser than the prefix suggested: redo this round smaller, this and every later one with the exact capacity
             items_per_start = std::min(1.0, (double)items / (double)m * 1.02);
+            caps.exact_from_here();
             continue;
         }
         if (items) {
@@ -798,12 +823,14 @@ static int count_partitioned(katgpu_table* t, const uint8_t* dev_bases, size_t n
             RoundEnd end;
             rc = level2_and_apply(t, g, l1, A, items, &p2_fast_ok, &lists, &end);
             if (rc) return rc;
-            if (end == RoundEnd::RedoExactL1) { l1_fast_ok = false; continue; }
+            if (end == RoundEnd::RedoExactL1) { l1_fast_ok = false; caps.exact_from_here(); continue; }      // (the repeated round and every later one: the exact capacity)
             if (end == RoundEnd::DirectPath) break;
             bool lost = false;
             rc = insert_spilled(t, lists, &lost);
             if (rc) return rc;
             if (lost) { pos += m; break; }         // the caller re-enters for the rest
+            rc = guards_check(c, A);
+            if (rc) return rc;
         }
         pos += m;
     }

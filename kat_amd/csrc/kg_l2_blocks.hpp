@@ -48,8 +48,8 @@ k_p2x_fast(PartGeom g, const uint64_t* __restrict__ l1_off, const uint8_t* __res
     for (uint32_t b1 = g.b_lo + blockIdx.x; b1 < g.b_hi; b1 += gridDim.x) {
         uint64_t beg, n_items, n_real;
         const uint8_t* bucket = l1_buf + l1_bucket_range(g, l1_off, seg_slots, b1, beg, n_items, n_real);
-        const uint64_t cap = p2_region_cap(n_real, P, TILE_CAP, L2_BLOCK_ITEMS);
-        const uint64_t obase = p2_out_base(beg, b1, P, TILE_CAP, L2_BLOCK_ITEMS) - p2_out_base(beg0, g.b_lo, P, TILE_CAP, L2_BLOCK_ITEMS);   // the level-2 buffer holds this pass only
+        const uint64_t cap = p2_region_cap(n_real, P, TILE_CAP, L2_BLOCK_ITEMS, g.l2_trim != 0);
+        const uint64_t obase = p2_out_base(beg, b1, P, TILE_CAP, L2_BLOCK_ITEMS, g.l2_trim != 0) - p2_out_base(beg0, g.b_lo, P, TILE_CAP, L2_BLOCK_ITEMS, g.l2_trim != 0);   // the level-2 buffer holds this pass only
         uint8_t* const runs = l2_buf + l2_lo_at<1>(obase >> 2);                 // run of sub-bucket b: blocks [b * capb, (b + 1) * capb) from here
         const uint32_t capb = (uint32_t)(cap / L2_BLOCK_ITEMS);                 // (< 2^32: host-checked through the buffer's size)
         lds_barrier();                                                          // the bucket before is through with the carve

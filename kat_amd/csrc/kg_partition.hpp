@@ -22,6 +22,7 @@
 #include "kg_kernels.hpp"
 #include "kg_l1_lean.hpp"
 #include "kg_apply_lean.hpp"
+#include "kg_arena_plan.hpp"   // the level-2 formats, the exact layouts, a run's capacity and base
 
 #include <cstddef>
 #include <type_traits>
@@ -58,6 +59,7 @@ struct PartGeom {
     uint64_t l1_real;  // segmented level 1: k-mers a bucket holds at most (workgroups x the segments' k-mer capacity; its slots -- group padding included -- are more): what level 2's runs and the spill list are sized by
     uint64_t spill_cap;// k-mers the apply's spill list holds (this pass's part of the level-1 buffer); what is beyond is counted, not written: the host fails the call
     uint32_t cbits;    // the table's (kg_device.hpp: packed slots); 0: KV12
+    uint32_t l2_trim;  // this round's one-pass level 2 sizes its runs by the trimmed form (kg_arena_plan.hpp: l2_trims -- blocked items, long runs)
     Place pl;          // the placement hash's bit budget for this table (kg_device.hpp)
 };
 // ---- the level-2 buffer ----
@@ -77,7 +79,6 @@ template <int HB> struct L2Fmt {
     static constexpr uint32_t GS = 16 + 4 * HB;              // bytes of a group
     static constexpr uint64_t NONE = HB == 4 ? ~0ULL : (1ULL << (32 + 8 * HB)) - 1;
 };
-__device__ __host__ __forceinline__ uint32_t l2_tile_items(uint32_t hb) { return hb == 4 ? 12 * 1024 : 16 * 1024; }
 // ---- 5-byte items (HB = 1: the bench's tables) live in 64-BYTE BLOCKS OF TWELVE (round 6) ----
 // block = [12 low words: 48 B | 12 high bytes | 4 B unused], 64-byte aligned; group g of the buffer (four items, still the unit of the
 // readers: a lane of the apply takes one) is part g % 3 of block g / 3: its low words 16 bytes at 16 (g % 3), its high bytes the dword at
@@ -87,8 +88,6 @@ __device__ __host__ __forceinline__ uint32_t l2_tile_items(uint32_t hb) { return
 // round 5's "C") 19.0; the same blocks stored by a QUAD of lanes in one instruction -- sixteen bytes each, a whole line per request --
 // 16.6, stores alone 7.4 against 13.0.  So the one-pass level 2 keeps an incomplete block per sub-bucket in LDS until it is full
 // (scatter_tile2_blk) and everything else addresses groups through these two functions.
-__device__ __host__ __forceinline__ constexpr bool l2_blocked(uint32_t hb) { return hb == 1; }
-constexpr uint32_t L2_BLOCK_ITEMS = 12, L2_BLOCK_BYTES = 64;
 template <int HB> __device__ __host__ __forceinline__ uint64_t l2_lo_at(uint64_t grp) {          // byte offset of group grp's four low words
     if (l2_blocked(HB)) { const uint64_t b = grp / 3; return b * L2_BLOCK_BYTES + (grp - 3 * b) * 16; }
     return grp * L2Fmt<HB>::GS;
@@ -97,10 +96,6 @@ template <int HB> __device__ __host__ __forceinline__ uint64_t l2_hi_at(uint64_t
     if (l2_blocked(HB)) { const uint64_t b = grp / 3; return b * L2_BLOCK_BYTES + 48 + (grp - 3 * b) * 4; }
     return grp * L2Fmt<HB>::GS + 16;
 }
-// bytes the level-2 buffer takes for `items` items (a multiple of 4) + the granule runs are aligned to, in items
-__device__ __host__ __forceinline__ uint64_t l2_buffer_bytes(uint32_t hb, uint64_t items) { return l2_blocked(hb) ? (items / L2_BLOCK_ITEMS + 2) * L2_BLOCK_BYTES : items / 4 * (16 + 4 * hb); }
-__device__ __host__ __forceinline__ double l2_bytes_per_item(uint32_t hb) { return l2_blocked(hb) ? (double)L2_BLOCK_BYTES / L2_BLOCK_ITEMS : 4.0 + hb; }
-__device__ __host__ __forceinline__ uint32_t l2_run_align(uint32_t hb) { return l2_blocked(hb) ? L2_BLOCK_ITEMS : 4u; }
 template <int HB> struct HiWord { typedef uint32_t type; };
 template <> struct HiWord<1> { typedef uint8_t type; };
 template <> struct HiWord<2> { typedef uint16_t type; };
@@ -248,7 +243,6 @@ constexpr int P1_LANES_WITH_STARTS = P1_TILE_STARTS / PART_ITEMS; // 510
 // l1_bucket_base(first item of b, b): the buffer keeps 8 bytes per item whatever the group size, because a pass's part of it, once
 // its level 2 is through, is the spill list of that pass's apply -- 8-byte k-mers, as many as there were items in the worst case.
 // The all-ones item is "no item" (segment padding): n1 < 8 (4 + HB1) wherever this path runs (part_geometry).
-__device__ __host__ __forceinline__ uint64_t l1_bucket_base(uint64_t first_item, uint32_t b) { return 8 * first_item + 32ULL * b; }   // (+ 32 b: a bucket's last group may hold up to three items more than the bucket)
 template <uint32_t HB1>
 __device__ __forceinline__ void l1_put(uint8_t* __restrict__ bucket, uint64_t group_byte, uint32_t q, uint32_t lo, uint32_t hi) {
     uint8_t* grp = bucket + group_byte;
@@ -1224,8 +1218,6 @@ __device__ __forceinline__ uint32_t flush_carry_blk(P2BLds& L, const PartGeom g,
     return blocks;
 }
 
-// first item of bucket b1's runs in the exact edition: every run may end on up to three padding items
-__device__ __host__ __forceinline__ uint64_t p2_exact_base(uint64_t beg, uint32_t b1, uint32_t P2) { return (beg + 4 * ((uint64_t)P2 + 1) * b1 + 3) & ~3ULL; }
 
 // The exact edition: one workgroup per level-1 bucket: histogram by digit, scan, scatter.  off2[r] = start of region r's run (a
 // multiple of 4: runs begin on group boundaries; the up to three items between a run's last k-mer and the next run are "no item").
@@ -1284,18 +1276,8 @@ k_p2(PartGeom g, const uint64_t* __restrict__ l1_off, const uint8_t* __restrict_
 // beyond a region's capacity (heavy hitters, or a very unlucky region) go to a small overflow list that the host
 // inserts through the direct path; if even that list overflows, the host redoes the round with the exact kernel
 // (the level-1 buffer is only read here) and stays exact for the rest of the call.
-// Both in ITEMS, both multiples of 4.  p2_out_base(beg + n) - p2_out_base(beg) >= P2 * p2_region_cap(n): buckets do not overlap.
-// (`al`: l2_run_align -- 4, or 12 where the items are blocked: runs start and end on block boundaries there; the 48 items of slack per run
-// in p2_out_base cover the rounding of either.)
-constexpr uint32_t P2_RUN_SLACK = 48;
-__device__ __host__ __forceinline__ uint64_t p2_region_cap(uint64_t n_b, uint32_t P2, uint32_t tile, uint32_t al = 4) {
-    const uint64_t c = ((n_b + (n_b >> 4)) >> (31 - __builtin_clz(P2))) + 2 * (n_b / tile + 1) + 16;      // (P2 is a power of two: a 64-bit division here kept its reciprocal in two spilled registers)
-    return (c + al - 1) / al * al;
-}
-__device__ __host__ __forceinline__ uint64_t p2_out_base(uint64_t beg, uint32_t b1, uint32_t P2, uint32_t tile, uint32_t al = 4) {
-    const uint64_t o = beg + (beg >> 4) + 2 * (uint64_t)P2 * (beg / tile) + (uint64_t)b1 * P2 * P2_RUN_SLACK;
-    return (o + al - 1) / al * al;
-}
+// A run's capacity and base -- p2_region_cap, p2_out_base -- are kg_arena_plan.hpp's: the host sizes the level-2 buffer by the same text; g.l2_trim
+// selects the trimmed form (blocked items, a round of long runs).
 
 template <int HB, bool W1, bool STAMP = false, bool L1B = false /* the level-1 buffer holds blocks of ten (kg_l1_blocks.hpp) */>
 __global__ void __launch_bounds__(PART_BLOCK)
@@ -1316,8 +1298,8 @@ k_p2_fast(PartGeom g, const uint64_t* __restrict__ l1_off, const uint8_t* __rest
     for (uint32_t b1 = g.b_lo + blockIdx.x; b1 < g.b_hi; b1 += gridDim.x) {
         uint64_t beg, n_items, n_real;
         const uint8_t* bucket = l1_buf + l1_bucket_range(g, l1_off, seg_slots, b1, beg, n_items, n_real);
-        const uint64_t cap = p2_region_cap(n_real, g.P2, L2Fmt<HB>::TILE, AL);
-        const uint64_t obase = p2_out_base(beg, b1, g.P2, L2Fmt<HB>::TILE, AL) - p2_out_base(beg0, g.b_lo, g.P2, L2Fmt<HB>::TILE, AL);   // the level-2 buffer holds this pass only
+        const uint64_t cap = p2_region_cap(n_real, g.P2, L2Fmt<HB>::TILE, AL, g.l2_trim != 0);
+        const uint64_t obase = p2_out_base(beg, b1, g.P2, L2Fmt<HB>::TILE, AL, g.l2_trim != 0) - p2_out_base(beg0, g.b_lo, g.P2, L2Fmt<HB>::TILE, AL, g.l2_trim != 0);   // the level-2 buffer holds this pass only
         uint8_t* runs = l2_buf + l2_lo_at<HB>(obase >> 2);                      // run of sub-bucket b: groups [b * capg, (b + 1) * capg) from here (blocked: blocks [b * capg, ...): capg counts blocks)
         const uint32_t capg = (uint32_t)(cap / AL);                             // (< 2^32: host-checked through the buffer's size)
         lds_barrier();
