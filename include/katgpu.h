@@ -237,6 +237,20 @@ int katgpu_table_record_regions_host(katgpu_table* t, const char* bases, size_t 
 int katgpu_table_record_regions_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
                                        const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, const katgpu_count_range* ranges,
                                        uint32_t n_ranges, katgpu_region* dev_regions, size_t cap, size_t n_out[/* n_ranges */]);
+/* The two above from a dense array of counts instead of a table: dev_counts[p] is the count of the window that starts at base p of
+ * dev_bases, n - k + 1 words for n >= k (unused, and may be NULL, when n < k) -- what katgpu_table_profile_device writes, or what a
+ * gathered profile leaves on rank 0's device.  No table, so the calls take a context and k (1 <= k <= KATGPU_MAX_K, else KATGPU_ERR_K
+ * with a message), as katgpu_record_gc_text_device does; a dev_counts that is not 8-byte aligned is KATGPU_ERR_INVALID_ARG.  Results,
+ * record conventions, `cap` and the true totals, and what the pool is asked for are those of katgpu_table_record_stats_device and
+ * katgpu_table_record_regions_device with c[j] taken from dev_counts: validity comes from the bases, the count of an invalid window is
+ * never read and counts 0, the counts of windows that lie in no record are never read, and records shorter than k still get their
+ * gc_bases and n_bases.  There are no host forms: they would send 8 bytes per position up the bus. */
+int katgpu_record_stats_from_counts_device(katgpu_ctx* ctx, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_counts,
+                                           const uint64_t* dev_rec_start, const uint64_t* dev_rec_len, size_t n_rec, katgpu_record_stats* dev_out);
+int katgpu_record_regions_from_counts_device(katgpu_ctx* ctx, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_counts,
+                                             const uint64_t* dev_rec_start, const uint64_t* dev_rec_len, size_t n_rec,
+                                             const katgpu_count_range* ranges, uint32_t n_ranges, katgpu_region* dev_regions, size_t cap,
+                                             size_t n_out[/* n_ranges */]);
 /* `kat sect` without -n: the text Sect::printCounts (src/sect.cc:328-346) writes to -counts.cvg for a record, without its ">name"
  * line, rendered on the device.  Records are given as for katgpu_table_seq_hits_*; nb = rec_len - k + 1 when rec_len >= k, else 0;
  * c[j] is what katgpu_table_profile_* writes for window j of a record (the full 64-bit count, side table included; 0 for a window
@@ -522,6 +536,35 @@ int  katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_table* t, cons
 int  katgpu_table_seq_hits_gathered_host(katgpu_comm* comm, katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start,
                                          const uint64_t* rec_len, size_t n_rec, int canonicalise,
                                          uint64_t* hits /* rank 0; ignored elsewhere, may be NULL */);
+/* katgpu_table_record_stats_host and katgpu_table_record_regions_host for the tables of all ranks, after the exchange (`katgpu cold
+ * --gpus N`, `katgpu sect -n [-E] [-F] --gpus N`).  Collective: every rank calls it with its own table and the SAME bases, records
+ * and ranges (n_ranges = 0, 1 or 2; 0: statistics only, `regions` and `n_out` unused).  On rank 0, `stats` and -- with ranges --
+ * *regions (katgpu_free_host; never NULL on success) and n_out are what the two host forms would return for one table holding the union;
+ * the three are ignored on the other ranks and may be NULL there.  Both key widths, both table layouts, canonical and non-canonical
+ * tables; a world of one rank runs the whole protocol.  The precondition of katgpu_table_profile_gathered_host holds here too.
+ * The records go through in the batches of katgpu_table_record_stats_host (the same limits, the same rule for long records).  Per
+ * record batch the gather of katgpu_table_profile_gathered_host runs over the batch's bases, in its batches of 2^25 window starts,
+ * and leaves the counts in one dense array on rank 0's device; rank 0 then runs the statistics kernels and, with ranges, the region
+ * kernels from that array (katgpu_record_*_from_counts_device), once each, and the other ranks run nothing more.  What comes back from
+ * the device is 48 bytes per record and 24 per region: no per-position array crosses the bus.  A buffer shorter than k runs no gather;
+ * the statistics (gc_bases, n_bases) are still made.
+ * Device memory, from the context's pool and beside the table: on every rank the bases and 64 bytes per record of a record batch
+ * (katgpu_table_record_stats_host) and the gather's run (12 bytes per window start of a gather batch, + 32); on rank 0 also 8 bytes
+ * per base of a record batch for the dense counts -- 256 MiB for a full batch -- and what the two host forms take there (the long
+ * records' workspace; the masks, counters and regions of a batch).
+ * The ranks agree on n, n_rec, k, a checksum of the records and the ranges before anything else: a mismatch, or a rank with unusable
+ * arguments, is KATGPU_ERR_INVALID_ARG on every rank; the records are then validated as the host forms do.  n_rec == 0 is KATGPU_OK
+ * everywhere.  They allocate the run and the dense counts first and agree on that too: when one cannot, every rank returns
+ * KATGPU_ERR_NOMEM (katgpu_last_error names the rank); either way the communicator is as usable as before.  A rank that fails later
+ * raises the communicator's abort flag, so that its peers leave their waits: an error on every rank.
+ * KATGPU_TIMING: rank 0 prints the gather's line once per call, its fields summed over the call's record batches (none when no batch
+ * reaches k bases), and after it
+ * katgpu_timing {"phase": "record_stats_gathered", "batches": <record batches>, "ranks": .., "records": n_rec, "regions": ..,
+ * "back_bytes": 48 * n_rec + 24 * regions}. */
+int  katgpu_table_record_stats_gathered_host(katgpu_comm* comm, katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start,
+                                             const uint64_t* rec_len, size_t n_rec, int canonicalise, const katgpu_count_range* ranges,
+                                             uint32_t n_ranges /* 0, 1 or 2 */, katgpu_record_stats* stats /* rank 0 */,
+                                             katgpu_region** regions /* rank 0; katgpu_free_host */, size_t n_out[/* n_ranges; rank 0 */]);
 /* wall time spent so far in extraction / on the wire (posting + waiting) / merging / all-reducing (ms), bytes sent, merge calls */
 int  katgpu_comm_stats(katgpu_comm* comm, double* ms_extract, double* ms_exchange, double* ms_merge, double* ms_allreduce,
                        uint64_t* bytes_sent, uint64_t* merge_launches);

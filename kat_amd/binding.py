@@ -45,6 +45,7 @@ EXPORTS = (
     "katgpu_table_record_regions_host", "katgpu_table_record_regions_device", "katgpu_jf_dump_gathered",
     "katgpu_table_profile_gathered_host", "katgpu_table_record_cvg_text_host", "katgpu_table_record_cvg_text_device",
     "katgpu_table_seq_hits_gathered_host", "katgpu_record_gc_text_host", "katgpu_record_gc_text_device",
+    "katgpu_record_stats_from_counts_device", "katgpu_record_regions_from_counts_device", "katgpu_table_record_stats_gathered_host",
 )
 
 # katgpu_record_stats: one record of Table.record_stats
@@ -129,6 +130,8 @@ def load_library():
     L.katgpu_table_record_cvg_text_device.argtypes = [vp, vp, sz, vp, vp, sz, C.c_int, vp, sz, vp, vp]
     L.katgpu_record_gc_text_host.argtypes = [vp, u32, vp, sz, vp, vp, sz, vp, vp]
     L.katgpu_record_gc_text_device.argtypes = [vp, u32, vp, sz, vp, vp, sz, vp, sz, vp, vp]
+    L.katgpu_record_stats_from_counts_device.argtypes = [vp, u32, vp, sz, vp, vp, vp, sz, vp]
+    L.katgpu_record_regions_from_counts_device.argtypes = [vp, u32, vp, sz, vp, vp, vp, sz, vp, u32, vp, sz, vp]
     L.katgpu_hist.argtypes = [vp, u64, u64, u64, vp, sz]
     L.katgpu_gcp.argtypes = [vp, C.c_double, u32, vp]
     L.katgpu_comp.argtypes = [vp, vp, C.c_int, C.c_int, C.c_double, C.c_double, u32, u32, vp, vp, vp]
@@ -479,6 +482,22 @@ class Engine:
         total = C.c_uint64()
         self._chk(self.L.katgpu_record_gc_text_device(self.h, k, p[0], n, p[1], p[2], n_rec, p[3], cap, p[4], C.byref(total)))
         return int(total.value)
+
+    def record_stats_from_counts_device(self, k, dev_bases, n, dev_counts, dev_rec_start, dev_rec_len, n_rec, dev_out):
+        """Table.record_stats_device from a dense array of counts (katgpu_record_stats_from_counts_device): DeviceBuffers or raw device
+        addresses; `dev_counts` holds the n - k + 1 counts of the windows of `dev_bases` (None when n < k), `dev_out` takes n_rec
+        entries of RECORD_STATS."""
+        p = [getattr(x, "ptr", x) for x in (dev_bases, dev_counts, dev_rec_start, dev_rec_len, dev_out)]
+        self._chk(self.L.katgpu_record_stats_from_counts_device(self.h, k, p[0], n, p[1], p[2], p[3], n_rec, p[4]))
+
+    def record_regions_from_counts_device(self, k, dev_bases, n, dev_counts, dev_rec_start, dev_rec_len, n_rec, ranges, dev_regions, cap):
+        """Table.record_regions_device from a dense array of counts (katgpu_record_regions_from_counts_device).  Returns the true
+        number of regions per range, whatever `cap`."""
+        p = [getattr(x, "ptr", x) for x in (dev_bases, dev_counts, dev_rec_start, dev_rec_len, dev_regions)]
+        rg = np.ascontiguousarray(ranges, np.uint64).reshape(-1, 2)
+        n_out = (C.c_size_t * max(rg.shape[0], 2))()
+        self._chk(self.L.katgpu_record_regions_from_counts_device(self.h, k, p[0], n, p[1], p[2], p[3], n_rec, rg.ctypes.data, rg.shape[0], p[4], cap, n_out))
+        return [int(n_out[q]) for q in range(rg.shape[0])]
 
     def profile_reset(self):
         self._chk(self.L.katgpu_profile_reset(self.h))
@@ -912,6 +931,8 @@ class Comm:
         L.katgpu_jf_dump_gathered.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
         L.katgpu_table_profile_gathered_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
         L.katgpu_table_seq_hits_gathered_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        L.katgpu_table_record_stats_gathered_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int,
+                                                              C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.katgpu_comm_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_double)] * 4 + [C.POINTER(C.c_uint64)] * 2
         L.katgpu_comm_wire.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
         h = C.c_void_p()
@@ -987,6 +1008,31 @@ class Comm:
         self.engine._chk(self.engine.L.katgpu_table_seq_hits_gathered_host(self.h, table.h, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size,
                                                                            int(bool(canon)), out.ctypes.data if out is not None else None))
         return out
+
+    def record_stats_gathered(self, table, bases, starts, lens, ranges=None, canonicalise=None):
+        """Collective, after exchange_merge: Table.record_stats and, with `ranges` (one or two (min, max) pairs), Table.record_regions
+        of the records (the same bases, starts, lengths and ranges on every rank) against the union of the ranks' tables, from one
+        gather.  Rank 0 gets (stats, [one (m, 3) array per range]), the other ranks None."""
+        b, st, ln = _record_args(bases, starts, lens)
+        rg = np.ascontiguousarray(ranges if ranges is not None else [], np.uint64).reshape(-1, 2)
+        nr = rg.shape[0]
+        out = np.zeros(st.size, RECORD_STATS) if self.rank == 0 else None
+        canon = table.canonical if canonicalise is None else canonicalise
+        p = C.c_void_p()
+        n_out = (C.c_size_t * max(nr, 2))()
+        speak = self.rank == 0
+        self.engine._chk(self.engine.L.katgpu_table_record_stats_gathered_host(
+            self.h, table.h, b.ctypes.data, b.size, st.ctypes.data, ln.ctypes.data, st.size, int(bool(canon)), rg.ctypes.data if nr else None, nr,
+            out.ctypes.data if speak else None, C.byref(p) if speak and nr else None, n_out if speak and nr else None))
+        if not speak:
+            return None
+        try:
+            total = sum(n_out[q] for q in range(nr))
+            flat = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint64)), shape=(total * 3,)).copy() if total else np.zeros(0, np.uint64)
+        finally:
+            self.engine.L.katgpu_free_host(p)
+        cuts = np.cumsum([0] + [n_out[q] for q in range(nr)])
+        return out, [flat[3 * cuts[q]:3 * cuts[q + 1]].reshape(-1, 3) for q in range(nr)]
 
     def stats(self):
         d = [C.c_double() for _ in range(4)]

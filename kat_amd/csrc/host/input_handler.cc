@@ -88,6 +88,12 @@ void Engine::profileGathered(katgpu_table* t, const char* bases, size_t n, bool 
     finishPending();
     check(katgpu_table_profile_gathered_host(comm(), t, bases, n, canonicalise ? 1 : 0, counts));
 }
+void Engine::recordStatsGathered(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec,
+                                 bool canonicalise, const katgpu_count_range* ranges, uint32_t n_ranges, katgpu_record_stats* stats,
+                                 katgpu_region** regions, size_t* n_out) {
+    finishPending();
+    check(katgpu_table_record_stats_gathered_host(comm(), t, bases, n, rec_start, rec_len, n_rec, canonicalise ? 1 : 0, ranges, n_ranges, stats, regions, n_out));
+}
 void Engine::seqHitsGathered(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec,
                              bool canonicalise, uint64_t* hits) {
     finishPending();

@@ -81,6 +81,11 @@ public:
     static void barrier();                          // idem
     // the per-position counts of `bases` against a table that lies on the ranks by owner, on rank 0 (katgpu_table_profile_gathered_host); idem
     static void profileGathered(katgpu_table* t, const char* bases, size_t n, bool canonicalise, uint64_t* counts);
+    // the per-record statistics and, with ranges, the count-range regions of the records of `bases` against such a table, on rank 0: reduced on
+    // rank 0's device from one gather, nothing per position comes to the host (katgpu_table_record_stats_gathered_host); idem
+    static void recordStatsGathered(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec,
+                                    bool canonicalise, const katgpu_count_range* ranges, uint32_t n_ranges, katgpu_record_stats* stats,
+                                    katgpu_region** regions, size_t* n_out);
     // the per-record hits of the records of `bases` against such a table, on rank 0 (katgpu_table_seq_hits_gathered_host); idem
     static void seqHitsGathered(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec,
                                 bool canonicalise, uint64_t* hits);

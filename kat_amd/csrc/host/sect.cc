@@ -7,7 +7,10 @@
 // per-record statistics (katgpu_table_record_stats_host) and the regions of -E / -F (katgpu_table_record_regions_host) come back.
 // With KATGPU_SECT_DEVICE_TEXT=1 that holds without -n as well: the lines of -counts.cvg are rendered on the device
 // (katgpu_table_record_cvg_text_host) and no count comes back in any one-GPU mode.  In both of these modes the lines of -g's -counts.gc
-// come from the device as well (katgpu_record_gc_text_host), so nothing walks a record's bases on the host.  Records are read with the semantics of the vendored SeqAn 2.0.0 reader
+// come from the device as well (katgpu_record_gc_text_host), so nothing walks a record's bases on the host.  --gpus N with -n does
+// the same against a hash that lies on the ranks: one collective per batch (katgpu_table_record_stats_gathered_host) gathers the counts
+// on rank 0's device and reduces them there, statistics and regions alike; without -n it gathers the per-position counts on rank 0's host
+// (katgpu_table_profile_gathered_host).  Records are read with the semantics of the vendored SeqAn 2.0.0 reader
 // (deps/seqan-library-2.0.0/include/seqan/seq_io/fasta_fastq.h:306-380, CharString target).
 #include "kat_host.hpp"
 #include "record_stats_host.hpp"
@@ -332,9 +335,10 @@ void Sect::processSeqFile() {                                                   
     SeqRecordReader reader(seqFile);
     if (verbose) std::cerr << endl;
     // --gpus N: after the exchange a k-mer lives on one rank.  Every rank reads the sequence file and takes part in one collective
-    // profile per batch (katgpu_table_profile_gathered_host); the per-position counts arrive on rank 0, which alone opens the outputs
-    // and runs processSeq on them -- whatever the options: processSeq makes every output from the counts.  The other ranks create,
-    // truncate and write nothing.
+    // per batch.  With -n that is katgpu_table_record_stats_gathered_host: the counts are gathered on rank 0's device and reduced
+    // there, the statistics and the regions of -E / -F from the same gather.  Without -n it is katgpu_table_profile_gathered_host: the
+    // per-position counts arrive on rank 0's host and processSeq makes every output from them.  Rank 0 alone opens the outputs; the other
+    // ranks create, truncate and write nothing.
     const bool dist = Engine::dist(), speak = !dist || Engine::speaker();
     std::ofstream count_path_stream, gc_count_path_stream, nr_path_stream, r_path_stream, cvg_gc_stream;
     if (speak) {
@@ -355,11 +359,12 @@ void Sect::processSeqFile() {                                                   
     vector<uint64_t> counts, offs, lens;
     vector<katgpu_record_stats> stats;
     // -n: nothing per position is written.  The device reduces the counts per record, and with -E / -F it finds the regions as well
-    // (one GPU: the statistics, regions and text kernels look a window up in the table of their own rank only).
-    // KATGPU_SECT_DEVICE_TEXT=1: the same without -n, the lines of -counts.cvg rendered on the device too.  It is asked for, not the
+    // (--gpus N: from the gathered counts on rank 0's device).
+    // KATGPU_SECT_DEVICE_TEXT=1: the same without -n, the lines of -counts.cvg rendered on the device too, one GPU only (the text kernel
+    // looks a window up in the table of its own rank).  It is asked for, not the
     // default: a one-GPU run without -n is pinned to the per-position profile by the suite (tests/test_gpu_record_stats.py).
     const char* dt = getenv("KATGPU_SECT_DEVICE_TEXT");
-    const bool cvg_text = !dist && !noCountStats && dt && atoi(dt) != 0, stats_only = !dist && (noCountStats || cvg_text);
+    const bool cvg_text = !dist && !noCountStats && dt && atoi(dt) != 0, stats_only = noCountStats || cvg_text;
     const bool gc_text = stats_only && outputGCStats;        // -g there: the lines of -counts.gc from the device too, from the bases alone
     vector<katgpu_count_range> ranges;
     if (stats_only && extractNR) ranges.push_back({1, minRepeat});
@@ -400,10 +405,17 @@ void Sect::processSeqFile() {                                                   
         if (stats_only) {
             lens.resize(n); stats.resize(n);
             for (size_t i = 0; i < n; i++) lens[i] = seqs[i].size();
-            Engine::check(katgpu_table_record_stats_host(input.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, input.canonical ? 1 : 0, stats.data()));
+            if (dist) {
+                Engine::recordStatsGathered(input.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, input.canonical, ranges.data(),
+                                            (uint32_t)ranges.size(), speak ? stats.data() : nullptr, speak ? &found : nullptr, speak ? n_found : nullptr);
+                if (!speak) continue;
+            } else {
+                Engine::check(katgpu_table_record_stats_host(input.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, input.canonical ? 1 : 0, stats.data()));
+                if (!ranges.empty())
+                    Engine::check(katgpu_table_record_regions_host(input.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, input.canonical ? 1 : 0,
+                                                                   ranges.data(), (uint32_t)ranges.size(), &found, n_found));
+            }
             if (!ranges.empty()) {
-                Engine::check(katgpu_table_record_regions_host(input.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, input.canonical ? 1 : 0,
-                                                               ranges.data(), (uint32_t)ranges.size(), &found, n_found));
                 auto index = [&](vector<size_t>& first, const katgpu_region* rg, size_t m) {      // the regions come sorted by record
                     first.assign(n + 1, 0);
                     for (size_t i = 0; i < m; i++) first[rg[i].record + 1]++;
@@ -525,8 +537,8 @@ int Sect::main(int argc, char* argv[]) {                                        
 // ================================================================ Cold (src/cold.cc) ==============================
 // Every record of the assembly against the reads hash and against the assembly's own hash: two
 // katgpu_table_record_stats_host calls per batch, one -stats.tsv row per record.  --gpus N: the hashes lie on the ranks by owner, so
-// the two calls are collective per-position profiles gathered on rank 0 (katgpu_table_profile_gathered_host), which reduces them per
-// record on the host (record_stats_host.hpp) and writes the rows; the other ranks write nothing.
+// the two calls are collective (katgpu_table_record_stats_gathered_host, no ranges): the counts are gathered on rank 0's device and
+// reduced per record there; rank 0 writes the rows, the other ranks write nothing.
 
 Cold::Cold(const vector<string>& reads_files, const string& asm_file) {                          // src/cold.cc:67-77
     reads.setMultipleInputs(reads_files);
@@ -591,7 +603,7 @@ void Cold::processSeqFile() {                                                   
     vector<Row> rows;
     string joined;
     vector<katgpu_record_stats> rstats, astats;
-    vector<uint64_t> offs, lens, counts;
+    vector<uint64_t> offs, lens;
     while (!reader.atEnd()) {
         if (verbose) std::cerr << "Loading Batch of sequences... ";
         names.clear(); seqs.clear();
@@ -609,10 +621,9 @@ void Cold::processSeqFile() {                                                   
         rstats.resize(n); astats.resize(n);
         // the device reduces every record's counts: everything from the reads hash, the median (asm_cn) from the assembly's
         if (dist) {
-            if (speak && counts.size() < joined.size()) counts.resize(joined.size());
             auto gathered = [&](InputHandler& in, vector<katgpu_record_stats>& st) {
-                Engine::profileGathered(in.hash, joined.data(), joined.size(), in.canonical, speak ? counts.data() : nullptr);
-                for (size_t i = 0; speak && i < n; i++) st[i] = recordStatsFromCounts(seqs[i].data(), seqs[i].size(), in.merLen, counts.data() + offs[i]);
+                Engine::recordStatsGathered(in.hash, joined.data(), joined.size(), offs.data(), lens.data(), n, in.canonical, nullptr, 0,
+                                            speak ? st.data() : nullptr, nullptr, nullptr);
             };
             gathered(reads, rstats);
             gathered(assembly, astats);

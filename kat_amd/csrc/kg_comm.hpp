@@ -64,3 +64,29 @@ int comm_agree_to_start(katgpu_comm* m, int rc, const std::function<int(int who,
 // KATGPU_ERR_DEVICE for KATGPU_ERR_NOMEM, which is the collective one of the moment before; its peers get the communicator's failure,
 // or KATGPU_ERR_DEVICE with rank_failed_fmt (one %d: the rank).
 int comm_agree_done(katgpu_comm* m, int rc, const char* rank_failed_fmt);
+
+// what the ranks of a gathered per-record call compare of their records: every start and length, in order, folded into one word
+inline uint64_t records_checksum(const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec) {
+    uint64_t h = 0x9E3779B97F4A7C15ULL;
+    auto fold = [&](uint64_t x) { h ^= x; h *= 0xFF51AFD7ED558CCDULL; h ^= h >> 32; };
+    for (size_t r = 0; r < n_rec; ++r) { fold(rec_start[r]); fold(rec_len[r]); }
+    return h;
+}
+
+// ---- the gather of a profile from the ranks' tables (kg_query.hip), for the collectives built on it: katgpu_table_profile_gathered_host
+// there, katgpu_table_record_stats_gathered_host in kg_per_record.hip.  One object per collective call; its counters add up over gather(). ----
+struct ProfileGather {
+    katgpu_comm* comm; katgpu_table* t; int canonicalise;
+    size_t batch = 0;                             // window starts per batch (KATGPU_TEST_GATHER_BATCH)
+    size_t idx_off = 0, len_off = 0;
+    DevBuf db, run, dense;                        // a batch's bases (stage_bases) | its run: counts, indices, length | its dense counts on rank 0 (stage_counts)
+    uint64_t n_batches = 0, records = 0, wire_bytes = 0;
+    // Before the work (comm_agree_to_start): the table read, the buffers of a batch of at most max_starts window starts from the pool.
+    // stage_bases: gather() will be given host bases; stage_counts: it will send the counts to the host.
+    int prepare(size_t max_starts, bool stage_bases, bool stage_counts);
+    // Every rank, with the same n bases (n < k: nothing happens): from the host (bases) or already on this rank's device (dev_bases, which
+    // wins).  On rank 0 the n - k + 1 counts go to the host array `counts`, or stay in the device array dev_counts (which wins).
+    int gather(const char* bases, const uint8_t* dev_bases, size_t n, uint64_t* counts, uint64_t* dev_counts);
+    void print_timing() const;                    // rank 0, under KATGPU_TIMING: the "profile_gathered" line of the call
+};
+int gather_peer_error(katgpu_comm* comm, const ProfileGather& g, int p, int code);      // comm_agree_to_start's peer_error for prepare()

@@ -3,7 +3,8 @@
 //   kg_context.hip   context, pool, profile counters, device buffers, the synthetic workload
 //   kg_table.hip     table life cycle: geometry, create / regrow / free, counters and statistics, room for records to come
 //   kg_query.hip     a sequence or keys against a table: lookups, profiles and per-record hits (one table, or the ranks' tables gathered)
-//   kg_per_record.hip  the per-record calls of sect and cold: coverage statistics, count-range regions, -counts.cvg and -counts.gc text
+//   kg_per_record.hip  the per-record calls of sect and cold: coverage statistics, count-range regions (from one table, from a dense array of
+//                    counts, or from the ranks' tables gathered), -counts.cvg and -counts.gc text
 //   kg_records.hip  records out of a table and into one: partition / export / merge, the k-mer filter
 //   kg_jf_device.hip .jf records in file order out of a table, and streamed from a file into one
 //   kg_count.hip     counting: the direct kernel, the partitioned counter's host loop, the host feeder, katgpu_count*

@@ -2,7 +2,10 @@
 // `cold` (katgpu_table_record_stats_*), the count-range regions of `sect -E / -F` (katgpu_table_record_regions_*), the -counts.cvg text
 // of `sect` (katgpu_table_record_cvg_text_*) and the -counts.gc text of `sect -g` (katgpu_record_gc_text_*: bases only, no table).
 // Every call has a device form and a host form; the host forms send their records through the device in batches (for_record_batches).
-#include "kg_host.hpp"
+// The statistics and regions also read their counts from a dense array instead of a table (katgpu_record_*_from_counts_device: device
+// forms only), which is how they are made of a table that lies on several ranks (katgpu_table_record_stats_gathered_host, on
+// kg_query.hip's gather: kg_comm.hpp).
+#include "kg_comm.hpp"
 #include "kg_record_stats.hpp"
 #include "kg_record_regions.hpp"
 #include "kg_cvg_text.hpp"
@@ -17,22 +20,20 @@ static_assert(sizeof(katgpu_record_stats) == RS_FIELDS * sizeof(uint64_t), "the 
 // Everything on the stream: the result cleared, K11 over the tiles, and, when n_long records are long (long_windows windows in all),
 // their slots, K12 and the eight passes of K13 over those windows.  ws takes the workspace of the long records (none: left empty), to be
 // let go once the stream has run.  Two timed sections: the second only when there are long records.
-static int launch_record_stats(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec,
-                               int canonicalise, katgpu_record_stats* dev_out, uint64_t n_long, uint64_t long_windows, DevBuf& ws) {
-    katgpu_ctx* c = t->ctx;
+// src: where the counts come from (kg_record_stats.hpp), of k-mers of length k.
+template <typename Src>
+static int launch_record_stats(katgpu_ctx* c, const Src& src, uint32_t k, bool wide, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len,
+                               size_t n_rec, katgpu_record_stats* dev_out, uint64_t n_long, uint64_t long_windows, DevBuf& ws) {
     ws.reset();
     HIPCHK(c, hipMemsetAsync(dev_out, 0, n_rec * sizeof(katgpu_record_stats), c->stream));
     if (!n || !n_rec) return KATGPU_OK;
-    const DevTable& d = t->dev();
-    const uint32_t k = d.k;
-    const bool wide = d.keys_b != nullptr;
     const bool aligned = aligned16(dev_bases);
     const uint64_t n_out = n >= k ? n - k + 1 : 0;
     unsigned long long* o = (unsigned long long*)dev_out;
     {
         ScopedTimer tm(c, KATGPU_K_PROFILE, n_out);
         launch_aligned_wide(c, aligned, wide, n, RS_TILE_STRIDE, [&](auto A, auto W, dim3 grid, uint64_t n_tiles) {
-            hipLaunchKernelGGL((k_rstats_short<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, d, t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_tiles, dev_start, dev_len, (uint64_t)n_rec, g_stats_short, o);
+            hipLaunchKernelGGL((k_rstats_short<decltype(A)::value, decltype(W)::value, Src>), grid, dim3(COUNT_BLOCK), 0, c->stream, src, dev_bases, (uint64_t)n, n_tiles, dev_start, dev_len, (uint64_t)n_rec, g_stats_short, o);
         });
         HIPCHK(c, hipGetLastError());
     }
@@ -53,7 +54,7 @@ static int launch_record_stats(katgpu_table* t, const uint8_t* dev_bases, size_t
     HIPCHK(c, hipMemsetAsync(rec_slot, 0xFF, n_rec * sizeof(uint32_t), c->stream));
     hipLaunchKernelGGL(k_rstats_classify, dim3(1), dim3(RS_CLASSIFY_BLOCK), 0, c->stream, dev_len, (uint64_t)n_rec, k, g_stats_short, n_long, long_windows, rec_slot, sel);
     launch_aligned_wide(c, aligned, wide, n, chunk_starts(wide), [&](auto A, auto W, dim3 grid, uint64_t n_chunks) {
-        hipLaunchKernelGGL((k_rstats_long<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, d, t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, rec_slot, cnt, long_windows, sel, o);
+        hipLaunchKernelGGL((k_rstats_long<decltype(A)::value, decltype(W)::value, Src>), grid, dim3(COUNT_BLOCK), 0, c->stream, src, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, rec_slot, cnt, long_windows, sel, o);
     });
     const uint64_t sel_chunks = (long_windows + RS_SEL_CHUNK - 1) / RS_SEL_CHUNK;
     const dim3 hg((unsigned)std::min<uint64_t>(sel_chunks, (uint64_t)c->n_cu * 8)), pg((unsigned)((n_long + 3) / 4));
@@ -65,8 +66,36 @@ static int launch_record_stats(katgpu_table* t, const uint8_t* dev_bases, size_t
     return KATGPU_OK;
 }
 
-// Device form.  The number of long records and of their windows comes back from the device first (two words; refresh_counters has synchronised already);
-// with none, the rest is asynchronous on the stream, otherwise the call returns when the selection's workspace has been released.
+static CountsTable counts_of(katgpu_table* t, int canonicalise) { return CountsTable{t->dev(), t->n_ovf, canonicalise}; }
+static bool is_wide(const katgpu_table* t) { return t->dv.keys_b != nullptr; }
+// a dense array of counts as a source: the window kernels cut their chunks by the key width of k
+static CountsDense counts_of(const uint64_t* dev_counts, size_t n, uint32_t k) { return CountsDense{dev_counts, n >= k ? (uint64_t)(n - k + 1) : 0, k}; }
+static int counts_check(katgpu_ctx* c, const char* what, uint32_t k, const uint64_t* dev_counts) {
+    if (k < 1 || k > KATGPU_MAX_K) return fail(c, KATGPU_ERR_K, "%s: k = %u unsupported (1 <= k <= %d)", what, k, KATGPU_MAX_K);
+    if (reinterpret_cast<uintptr_t>(dev_counts) & 7) return fail(c, KATGPU_ERR_INVALID_ARG, "%s: the counts are not 8-byte aligned", what);
+    return KATGPU_OK;
+}
+
+// The number of long records and of their windows from the device (two words, through `scratch`), then launch_record_stats; with none, the
+// rest is asynchronous on the stream, otherwise the call returns when the selection's workspace has been released.
+template <typename Src>
+static int record_stats_device(katgpu_ctx* c, const Src& src, uint32_t k, bool wide, unsigned long long* scratch, const uint8_t* dev_bases, size_t n,
+                               const uint64_t* dev_rec_start, const uint64_t* dev_rec_len, size_t n_rec, katgpu_record_stats* dev_out) {
+    unsigned long long n_long[2] = {0, 0};
+    HIPCHK(c, hipMemsetAsync(scratch, 0, sizeof n_long, c->stream));
+    hipLaunchKernelGGL(k_rstats_count_long, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, c->stream, dev_rec_len, (uint64_t)n_rec, k, g_stats_short, scratch);
+    HIPCHK(c, hipMemcpyAsync(n_long, scratch, sizeof n_long, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    DevBuf ws;
+    int rc = launch_record_stats(c, src, k, wide, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, dev_out, n_long[0], n_long[1], ws);
+    if (ws.p) {
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (!rc && e != hipSuccess) rc = fail(c, KATGPU_ERR_DEVICE, "record stats: %s", hipGetErrorString(e));
+    }
+    return rc;
+}
+
+// Device form (refresh_counters has synchronised already; the two words are two of the table's counters).
 extern "C" int katgpu_table_record_stats_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
                                                 const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, katgpu_record_stats* dev_out) {
     if (!t || (n_rec && (!dev_rec_start || !dev_rec_len || !dev_out)) || (n && !dev_bases)) return KATGPU_ERR_INVALID_ARG;
@@ -74,20 +103,37 @@ extern "C" int katgpu_table_record_stats_device(katgpu_table* t, const uint8_t* 
     katgpu_ctx* c = t->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = refresh_counters(t); if (rc) return rc;
-    unsigned long long* scratch = (unsigned long long*)&t->dev().ctrs[CTR_SCRATCH];
-    unsigned long long n_long[2] = {0, 0};
-    HIPCHK(c, hipMemsetAsync(scratch, 0, sizeof n_long, c->stream));
-    hipLaunchKernelGGL(k_rstats_count_long, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, c->stream, dev_rec_len, (uint64_t)n_rec, t->dev().k, g_stats_short, scratch);
-    HIPCHK(c, hipMemcpyAsync(n_long, scratch, sizeof n_long, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    DevBuf ws;
-    rc = launch_record_stats(t, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, canonicalise, dev_out, n_long[0], n_long[1], ws);
-    if (ws.p) {
-        const hipError_t e = hipStreamSynchronize(c->stream);
-        if (!rc && e != hipSuccess) rc = fail(c, KATGPU_ERR_DEVICE, "record stats: %s", hipGetErrorString(e));
-    }
-    return rc;
+    return record_stats_device(c, counts_of(t, canonicalise), t->dev().k, is_wide(t), (unsigned long long*)&t->dev().ctrs[CTR_SCRATCH], dev_bases, n,
+                               dev_rec_start, dev_rec_len, n_rec, dev_out);
 }
+
+// The same from a dense array of counts: no table, so a context and k, as katgpu_record_gc_text_device takes them.
+extern "C" int katgpu_record_stats_from_counts_device(katgpu_ctx* c, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_counts,
+                                                      const uint64_t* dev_rec_start, const uint64_t* dev_rec_len, size_t n_rec, katgpu_record_stats* dev_out) {
+    if (!c || (n_rec && (!dev_rec_start || !dev_rec_len || !dev_out)) || (n && !dev_bases)) return KATGPU_ERR_INVALID_ARG;
+    int rc = counts_check(c, "record stats from counts", k, dev_counts); if (rc) return rc;
+    if (n >= k && !dev_counts) return KATGPU_ERR_INVALID_ARG;
+    if (!n_rec) return KATGPU_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf two;                                                    // (a table form borrows two of its table's counters for this)
+    if (two.pooled(c, 16) != hipSuccess) { (void)hipGetLastError(); return fail(c, KATGPU_ERR_NOMEM, "record stats from counts: no device memory"); }
+    return record_stats_device(c, counts_of(dev_counts, n, k), k, k > 32, two.as<unsigned long long>(), dev_bases, n, dev_rec_start, dev_rec_len, n_rec, dev_out);
+}
+
+// Where a batch of the host form (and of the gathered one) ends beside for_record_batches' two limits: the long records of the batch being cut
+constexpr size_t STATS_RECS = (size_t)1 << 20;
+struct StatsJoins {
+    const uint64_t* rec_len; uint32_t k;
+    uint64_t n_long = 0, long_windows = 0;
+    bool operator()(size_t r, bool first) {
+        if (first) n_long = long_windows = 0;
+        uint64_t w = rec_len[r] >= k ? rec_len[r] - k + 1 : 0;
+        if (w <= g_stats_short) w = 0;
+        if (!first && long_windows + w > std::max<uint64_t>(g_stats_batch / 4, 1)) return false;
+        n_long += w != 0; long_windows += w;
+        return true;
+    }
+};
 
 // Host form: the records go through the device in batches of at most g_stats_batch bases and STATS_RECS records (for_record_batches),
 // so any input fits next to the table; a batch also ends where its long records would have more than
@@ -102,21 +148,13 @@ extern "C" int katgpu_table_record_stats_host(katgpu_table* t, const char* bases
     HIPCHK(c, hipSetDevice(c->device));
     rc = refresh_counters(t); if (rc) return rc;
     const uint32_t k = t->dev().k;
-    const size_t cap = std::min(n_rec, (size_t)1 << 20);           // records per batch
+    const size_t cap = std::min(n_rec, STATS_RECS);                // records per batch
     DevBuf ws;                                                     // the long records' workspace
-    uint64_t n_long = 0, long_windows = 0;                         // of the batch being cut
-    auto joins = [&](size_t r, bool first) {
-        if (first) n_long = long_windows = 0;
-        uint64_t w = rec_len[r] >= k ? rec_len[r] - k + 1 : 0;
-        if (w <= g_stats_short) w = 0;
-        if (!first && long_windows + w > std::max<uint64_t>(g_stats_batch / 4, 1)) return false;
-        n_long += w != 0; long_windows += w;
-        return true;
-    };
+    StatsJoins joins{rec_len, k};
     return for_record_batches(c, bases, n, rec_start, rec_len, n_rec, g_stats_batch, cap, RS_FIELDS, "record stats", "record statistics", joins,   // (a record's six result words)
                               [&](const uint8_t* db, size_t nb, const uint64_t* ds, const uint64_t* dl, size_t m, size_t r0, uint64_t* words) {
         katgpu_record_stats* d_out = (katgpu_record_stats*)words;
-        int rc = launch_record_stats(t, db, nb, ds, dl, m, canonicalise, d_out, n_long, long_windows, ws);
+        int rc = launch_record_stats(c, counts_of(t, canonicalise), k, is_wide(t), db, nb, ds, dl, m, d_out, joins.n_long, joins.long_windows, ws);
         if (rc) return rc;
         const hipError_t e = hipMemcpyAsync(out + r0, d_out, m * sizeof(katgpu_record_stats), hipMemcpyDeviceToHost, c->stream);
         return e == hipSuccess ? KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "record stats: %s", hipGetErrorString(e));
@@ -152,14 +190,12 @@ static bool regions_args(const katgpu_count_range* ranges, uint32_t n_ranges, Rg
 }
 
 // On the stream: K14 over the chunks of the n bases (n != 0), K15 and K16 over the masks; w.totals then holds the regions of every range.
-static int launch_regions_find(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec,
-                               int canonicalise, const RgRanges& rg, RegionsWork& w) {
-    katgpu_ctx* c = t->ctx;
-    const DevTable& d = t->dev();
-    const bool wide = d.keys_b != nullptr;
-    ScopedTimer tm(c, KATGPU_K_PROFILE, n >= d.k ? n - d.k + 1 : 0);
+template <typename Src>
+static int launch_regions_find(katgpu_ctx* c, const Src& src, uint32_t k, bool wide, const uint8_t* dev_bases, size_t n, const uint64_t* dev_start,
+                               const uint64_t* dev_len, size_t n_rec, const RgRanges& rg, RegionsWork& w) {
+    ScopedTimer tm(c, KATGPU_K_PROFILE, n >= k ? n - k + 1 : 0);
     launch_aligned_wide(c, aligned16(dev_bases), wide, w.n_words * 64, chunk_starts(wide), [&](auto A, auto W, dim3 grid, uint64_t n_chunks) {
-        hipLaunchKernelGGL((k_regions_mask<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, d, t->n_ovf, canonicalise, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, rg, w.n_words, (uint16_t*)w.masks);
+        hipLaunchKernelGGL((k_regions_mask<decltype(A)::value, decltype(W)::value, Src>), grid, dim3(COUNT_BLOCK), 0, c->stream, src, dev_bases, (uint64_t)n, n_chunks, dev_start, dev_len, (uint64_t)n_rec, rg, w.n_words, (uint16_t*)w.masks);
     });
     const dim3 grid((unsigned)std::min<uint64_t>(w.n_blk, (uint64_t)c->n_cu * 8));
     hipLaunchKernelGGL(k_regions_count, grid, dim3(RG_BLOCK), 0, c->stream, w.masks, w.n_words, w.n_blk, rg.n, w.cnt);
@@ -169,14 +205,28 @@ static int launch_regions_find(katgpu_table* t, const uint8_t* dev_bases, size_t
 }
 
 // K17 behind it: the first `cap` regions to dev_regions, their records numbered from rec_base
-static int launch_regions_emit(katgpu_table* t, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec, uint64_t rec_base, const RgRanges& rg,
+static int launch_regions_emit(katgpu_ctx* c, const uint64_t* dev_start, const uint64_t* dev_len, size_t n_rec, uint64_t rec_base, const RgRanges& rg,
                                const RegionsWork& w, katgpu_region* dev_regions, size_t cap) {
-    katgpu_ctx* c = t->ctx;
     if (!cap) return KATGPU_OK;
     ScopedTimer tm(c, KATGPU_K_PROFILE, 0);
     const dim3 grid((unsigned)std::min<uint64_t>(w.n_blk, (uint64_t)c->n_cu * 8));
     hipLaunchKernelGGL(k_regions_emit, grid, dim3(RG_BLOCK), 0, c->stream, w.masks, w.n_words, w.n_blk, rg.n, w.cnt, dev_start, dev_len, (uint64_t)n_rec, rec_base, (unsigned long long*)dev_regions, (uint64_t)cap);
     HIPCHK(c, hipGetLastError());
+    return KATGPU_OK;
+}
+
+// K14 - K17 over one buffer, and the true totals back
+template <typename Src>
+static int record_regions_device(katgpu_ctx* c, const Src& src, uint32_t k, bool wide, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
+                                 const uint64_t* dev_rec_len, size_t n_rec, const RgRanges& rg, katgpu_region* dev_regions, size_t cap, size_t n_out[]) {
+    RegionsWork w;
+    int rc = w.fit(c, n, rg.n); if (rc) return rc;
+    rc = launch_regions_find(c, src, k, wide, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, rg, w);
+    if (!rc) rc = launch_regions_emit(c, dev_rec_start, dev_rec_len, n_rec, 0, rg, w, dev_regions, cap);
+    if (rc) return rc;                                             // (w waits for the stream before it lets its block go)
+    unsigned long long totals[RG_MAX_RANGES] = {0, 0};
+    rc = read_totals(c, w.totals, rg.n, "record regions", totals); if (rc) return rc;
+    for (uint32_t q = 0; q < rg.n; ++q) n_out[q] = (size_t)totals[q];
     return KATGPU_OK;
 }
 
@@ -191,14 +241,60 @@ extern "C" int katgpu_table_record_regions_device(katgpu_table* t, const uint8_t
     if (!n_rec || !n) return KATGPU_OK;
     HIPCHK(c, hipSetDevice(c->device));
     int rc = refresh_counters(t); if (rc) return rc;
-    RegionsWork w;
-    rc = w.fit(c, n, n_ranges); if (rc) return rc;
-    rc = launch_regions_find(t, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, canonicalise, rg, w);
-    if (!rc) rc = launch_regions_emit(t, dev_rec_start, dev_rec_len, n_rec, 0, rg, w, dev_regions, cap);
-    if (rc) return rc;                                             // (w waits for the stream before it lets its block go)
+    return record_regions_device(c, counts_of(t, canonicalise), t->dev().k, is_wide(t), dev_bases, n, dev_rec_start, dev_rec_len, n_rec, rg, dev_regions, cap, n_out);
+}
+
+// The same from a dense array of counts (katgpu_record_stats_from_counts_device).
+extern "C" int katgpu_record_regions_from_counts_device(katgpu_ctx* c, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_counts,
+                                                        const uint64_t* dev_rec_start, const uint64_t* dev_rec_len, size_t n_rec,
+                                                        const katgpu_count_range* ranges, uint32_t n_ranges, katgpu_region* dev_regions, size_t cap, size_t n_out[]) {
+    RgRanges rg;
+    if (!c || !n_out || (n_rec && (!dev_rec_start || !dev_rec_len)) || (n && !dev_bases) || (cap && !dev_regions)) return KATGPU_ERR_INVALID_ARG;
+    int rc = counts_check(c, "record regions from counts", k, dev_counts); if (rc) return rc;
+    if (n >= k && !dev_counts) return KATGPU_ERR_INVALID_ARG;
+    if (!regions_args(ranges, n_ranges, rg)) return fail(c, KATGPU_ERR_INVALID_ARG, "record regions: one or two count ranges, not %u", ranges ? n_ranges : 0);
+    for (uint32_t q = 0; q < n_ranges; ++q) n_out[q] = 0;
+    if (!n_rec || !n) return KATGPU_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return record_regions_device(c, counts_of(dev_counts, n, k), k, k > 32, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, rg, dev_regions, cap, n_out);
+}
+
+// One batch of a host form: the totals come back first, then room for that many regions is found (out) and K17 fills it; the copies to
+// found[] are queued on the stream (the vectors grow before that and rest until the batch's synchronize).
+template <typename Src>
+static int regions_batch(katgpu_ctx* c, const Src& src, uint32_t k, bool wide, const uint8_t* db, size_t nb, const uint64_t* ds, const uint64_t* dl, size_t m,
+                         size_t r0, const RgRanges& rg, RegionsWork& w, DevBuf& out, std::vector<katgpu_region> (&found)[RG_MAX_RANGES]) {
+    if (!nb) return KATGPU_OK;
+    int rc = w.fit(c, nb, rg.n); if (rc) return rc;
+    rc = launch_regions_find(c, src, k, wide, db, nb, ds, dl, m, rg, w); if (rc) return rc;
     unsigned long long totals[RG_MAX_RANGES] = {0, 0};
-    rc = read_totals(c, w.totals, n_ranges, "record regions", totals); if (rc) return rc;
-    for (uint32_t q = 0; q < n_ranges; ++q) n_out[q] = (size_t)totals[q];
+    rc = read_totals(c, w.totals, rg.n, "record regions", totals); if (rc) return rc;
+    const size_t total = (size_t)(totals[0] + totals[1]);
+    if (!total) return KATGPU_OK;
+    if (out.fit(c, total * sizeof(katgpu_region)) != hipSuccess)
+        return fail(c, KATGPU_ERR_NOMEM, "record regions: no %zu bytes of device memory for the %zu regions of a batch", total * sizeof(katgpu_region), total);
+    katgpu_region* d_out = out.as<katgpu_region>();
+    rc = launch_regions_emit(c, ds, dl, m, r0, rg, w, d_out, total); if (rc) return rc;
+    hipError_t e = hipSuccess;
+    for (uint32_t q = 0; q < rg.n && e == hipSuccess; ++q) {
+        const size_t have = found[q].size();
+        found[q].resize(have + (size_t)totals[q]);
+        if (totals[q]) e = hipMemcpyAsync(found[q].data() + have, d_out + (q ? totals[0] : 0), (size_t)totals[q] * sizeof(katgpu_region), hipMemcpyDeviceToHost, c->stream);
+    }
+    return e == hipSuccess ? KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "record regions: %s", hipGetErrorString(e));
+}
+
+// the regions of a host form, range after range, in one block for katgpu_free_host
+static int regions_result(katgpu_ctx* c, const std::vector<katgpu_region> (&found)[RG_MAX_RANGES], uint32_t n_ranges, katgpu_region** regions, size_t n_out[]) {
+    const size_t total = found[0].size() + found[1].size();
+    katgpu_region* res = (katgpu_region*)malloc(std::max<size_t>(total, 1) * sizeof(katgpu_region));
+    if (!res) return fail(c, KATGPU_ERR_NOMEM, "record regions: no host memory for %zu regions", total);
+    size_t at = 0;
+    for (uint32_t q = 0; q < n_ranges; ++q) {
+        if (!found[q].empty()) memcpy(res + at, found[q].data(), found[q].size() * sizeof(katgpu_region));
+        at += found[q].size(); n_out[q] = found[q].size();
+    }
+    *regions = res;
     return KATGPU_OK;
 }
 
@@ -224,36 +320,117 @@ extern "C" int katgpu_table_record_regions_host(katgpu_table* t, const char* bas
         rc = for_record_batches(c, bases, n, rec_start, rec_len, n_rec, g_regions_batch, std::min(n_rec, (size_t)1 << 20), 0, "record regions", "record regions",
                                 [](size_t, bool) { return true; },
                                 [&](const uint8_t* db, size_t nb, const uint64_t* ds, const uint64_t* dl, size_t m, size_t r0, uint64_t*) {
-            if (!nb) return (int)KATGPU_OK;
-            int rc = w.fit(c, nb, n_ranges); if (rc) return rc;
-            rc = launch_regions_find(t, db, nb, ds, dl, m, canonicalise, rg, w); if (rc) return rc;
-            unsigned long long totals[RG_MAX_RANGES] = {0, 0};
-            rc = read_totals(c, w.totals, n_ranges, "record regions", totals); if (rc) return rc;
-            const size_t total = (size_t)(totals[0] + totals[1]);
-            if (!total) return (int)KATGPU_OK;
-            if (out.fit(c, total * sizeof(katgpu_region)) != hipSuccess)
-                return fail(c, KATGPU_ERR_NOMEM, "record regions: no %zu bytes of device memory for the %zu regions of a batch", total * sizeof(katgpu_region), total);
-            katgpu_region* d_out = out.as<katgpu_region>();
-            rc = launch_regions_emit(t, ds, dl, m, r0, rg, w, d_out, total); if (rc) return rc;
-            hipError_t e = hipSuccess;
-            for (uint32_t q = 0; q < n_ranges && e == hipSuccess; ++q) {    // (the vectors grow before the copies are queued and rest until the batch's synchronize)
-                const size_t have = found[q].size();
-                found[q].resize(have + (size_t)totals[q]);
-                if (totals[q]) e = hipMemcpyAsync(found[q].data() + have, d_out + (q ? totals[0] : 0), (size_t)totals[q] * sizeof(katgpu_region), hipMemcpyDeviceToHost, c->stream);
-            }
-            return e == hipSuccess ? (int)KATGPU_OK : fail(c, KATGPU_ERR_DEVICE, "record regions: %s", hipGetErrorString(e));
+            return regions_batch(c, counts_of(t, canonicalise), t->dev().k, is_wide(t), db, nb, ds, dl, m, r0, rg, w, out, found);
         });
         if (rc) return rc;
     }
-    const size_t total = found[0].size() + found[1].size();
-    katgpu_region* res = (katgpu_region*)malloc(std::max<size_t>(total, 1) * sizeof(katgpu_region));
-    if (!res) return fail(c, KATGPU_ERR_NOMEM, "record regions: no host memory for %zu regions", total);
-    size_t at = 0;
-    for (uint32_t q = 0; q < n_ranges; ++q) {
-        if (!found[q].empty()) memcpy(res + at, found[q].data(), found[q].size() * sizeof(katgpu_region));
-        at += found[q].size(); n_out[q] = found[q].size();
+    return regions_result(c, found, n_ranges, regions, n_out);
+}
+
+// ------------------------------------------------------------------ both, of a table that lies on several ranks ----
+
+// Collective, after katgpu_exchange_merge: every rank walks the same records in the batches of katgpu_table_record_stats_host (StatsJoins).
+// Per record batch the gather of katgpu_table_profile_gathered_host (kg_comm.hpp: ProfileGather) runs over the batch's bases, which are
+// on every rank's device already, and leaves the dense counts of its window starts in one array on rank 0's device; rank 0 then runs the
+// statistics kernels and, with ranges, the region kernels from that array (CountsDense) -- what comes back is 48 bytes per record and 24 per
+// region, none per position -- and the other ranks run nothing more.  The batches are cut from the records, so the ranks first make sure
+// that they hold the same ones.
+// From the pool: for_record_batches' buffers (start, length and statistics per record, the batch's bases) and the gather's run (12 bytes
+// per window start of a gather batch) on every rank; on rank 0 the dense counts, 8 bytes per base of a record batch, and what the two host
+// forms take (the long records' workspace, the masks and regions of a batch).  The run and the dense counts are allocated before any work
+// and agreed on; a rank that finds no room for the rest fails inside the batches, where comm_agree_done hears of it.
+extern "C" int katgpu_table_record_stats_gathered_host(katgpu_comm* comm, katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start,
+                                                       const uint64_t* rec_len, size_t n_rec, int canonicalise, const katgpu_count_range* ranges,
+                                                       uint32_t n_ranges, katgpu_record_stats* stats, katgpu_region** regions, size_t n_out[]) {
+    if (!comm || !t) return KATGPU_ERR_INVALID_ARG;
+    katgpu_ctx* c = t->ctx;
+    const int rank = katgpu_comm_rank(comm), world = katgpu_comm_world(comm);
+    const uint32_t k = t->dv.k;
+    RgRanges rg{{0, 0}, {0, 0}, 0};
+    // ---- the same records and ranges, one k and usable pointers everywhere, before anything else: all ranks go on, or none does ----
+    {
+        const bool unusable = (n && !bases) || (n_rec && (!rec_start || !rec_len)) || n_ranges > RG_MAX_RANGES || (n_ranges && !ranges) ||
+                              (rank == 0 && ((n_rec && !stats) || (n_ranges && (!regions || !n_out))));
+        uint64_t mine[10] = {(uint64_t)n, (uint64_t)n_rec, k, unusable ? 0 : records_checksum(rec_start, rec_len, n_rec), (uint64_t)unusable, n_ranges, 0, 0, 0, 0};
+        if (!unusable) { regions_args(ranges, n_ranges, rg); for (uint32_t q = 0; q < n_ranges; ++q) { mine[6 + 2 * q] = rg.min[q]; mine[7 + 2 * q] = rg.max[q]; } }
+        std::vector<uint64_t> all((size_t)world * 10, 0);
+        const int crc = allgather_u64(comm, mine, 10, all.data());
+        if (crc) return crc;
+        for (int p = 0; p < world; ++p)
+            if (all[(size_t)p * 10 + 4]) return fail(c, KATGPU_ERR_INVALID_ARG, "record stats gathered: rank %d was given no bases, no records or more than two ranges, or rank 0 no room for the results", p);
+        for (int p = 0; p < world; ++p) {
+            const uint64_t* a = &all[(size_t)p * 10];
+            if (a[0] != all[0] || a[1] != all[1] || a[2] != all[2])
+                return fail(c, KATGPU_ERR_INVALID_ARG, "record stats gathered: the ranks disagree: rank 0 has %llu bases in %llu records at k = %llu, rank %d %llu in %llu at k = %llu",
+                            (unsigned long long)all[0], (unsigned long long)all[1], (unsigned long long)all[2], p, (unsigned long long)a[0], (unsigned long long)a[1], (unsigned long long)a[2]);
+            if (a[3] != all[3]) return fail(c, KATGPU_ERR_INVALID_ARG, "record stats gathered: the ranks disagree: rank %d's %llu records are not where rank 0's are", p, (unsigned long long)a[1]);
+            if (memcmp(a + 5, &all[5], 5 * sizeof(uint64_t))) return fail(c, KATGPU_ERR_INVALID_ARG, "record stats gathered: the ranks disagree: rank %d's count ranges are not rank 0's", p);
+        }
     }
-    *regions = res;
+    if (rank == 0 && n_ranges) { *regions = nullptr; for (uint32_t q = 0; q < n_ranges; ++q) n_out[q] = 0; }
+    std::vector<katgpu_region> found[RG_MAX_RANGES];
+    if (!n_rec) return rank == 0 && n_ranges ? regions_result(c, found, n_ranges, regions, n_out) : KATGPU_OK;
+    int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;      // (the same records everywhere: the same answer)
+    // ---- the batches as they will be cut: the most bases of one, and whether any reaches k bases ----
+    const size_t cap = std::min(n_rec, STATS_RECS);
+    size_t max_nb = 0;
+    {
+        StatsJoins joins{rec_len, k};
+        for (size_t r0 = 0; r0 < n_rec;) {                         // (for_record_batches' cut)
+            const uint64_t base = rec_start[r0];
+            size_t r1 = r0;
+            joins(r1++, true);
+            while (r1 < n_rec && r1 - r0 < cap && rec_start[r1] + rec_len[r1] - base <= g_stats_batch && joins(r1, false)) ++r1;
+            max_nb = std::max<size_t>(max_nb, rec_start[r1 - 1] + rec_len[r1 - 1] - base);
+            r0 = r1;
+        }
+    }
+    const bool gathers = max_nb >= k;
+    ProfileGather g{comm, t, canonicalise};
+    DevBuf dense;                                                  // rank 0: the counts of a record batch's window starts
+    auto prepare = [&]() -> int {
+        if (!gathers) { HIPCHK(c, hipSetDevice(c->device)); return refresh_counters(t); }
+        int rc = g.prepare(max_nb - k + 1, false, false); if (rc) return rc;
+        if (rank == 0 && dense.pooled(c, (max_nb - k + 1) * sizeof(uint64_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, KATGPU_ERR_NOMEM, "record stats gathered: no %zu bytes of device memory for the counts of a batch of %zu bases", (max_nb - k + 1) * sizeof(uint64_t), max_nb);
+        }
+        return KATGPU_OK;
+    };
+    rc = comm_agree_to_start(comm, prepare(), [&](int p, int code) {
+        if (code == KATGPU_ERR_NOMEM) return fail(c, code, "record stats gathered: rank %d of %d has no device memory for a batch of %zu bases", p, world, max_nb);
+        return fail(c, code, "record stats gathered: rank %d could not read its table", p);
+    });
+    if (rc) return rc;
+
+    // ---- the batches.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end (comm_agree_done) ----
+    uint64_t n_batches = 0;
+    DevBuf ws, out;                                                // the long records' workspace | the regions of a batch
+    RegionsWork w;
+    StatsJoins joins{rec_len, k};
+    rc = for_record_batches(c, bases, n, rec_start, rec_len, n_rec, g_stats_batch, cap, RS_FIELDS, "record stats gathered", "record stats gathered", joins,
+                            [&](const uint8_t* db, size_t nb, const uint64_t* ds, const uint64_t* dl, size_t m, size_t r0, uint64_t* words) -> int {
+        uint64_t* d_counts = dense.as<uint64_t>();
+        int rc = g.gather(nullptr, db, nb, nullptr, d_counts); if (rc) return rc;
+        ++n_batches;
+        if (rank != 0) return KATGPU_OK;
+        katgpu_record_stats* d_out = (katgpu_record_stats*)words;
+        const CountsDense src = counts_of(d_counts, nb, k);
+        rc = launch_record_stats(c, src, k, k > 32, db, nb, ds, dl, m, d_out, joins.n_long, joins.long_windows, ws); if (rc) return rc;
+        HIPCHK(c, hipMemcpyAsync(stats + r0, d_out, m * sizeof(katgpu_record_stats), hipMemcpyDeviceToHost, c->stream));
+        return n_ranges ? regions_batch(c, src, k, k > 32, db, nb, ds, dl, m, r0, rg, w, out, found) : KATGPU_OK;
+    });
+    rc = comm_agree_done(comm, rc, "record stats gathered: rank %d failed");
+    if (rc) return rc;
+    if (g.n_batches) g.print_timing();
+    if (rank != 0) return KATGPU_OK;
+    if (n_ranges) { rc = regions_result(c, found, n_ranges, regions, n_out); if (rc) return rc; }
+    if (g_timing) {
+        const uint64_t n_regions = found[0].size() + found[1].size();
+        fprintf(stderr, "katgpu_timing {\"phase\": \"record_stats_gathered\", \"batches\": %llu, \"ranks\": %d, \"records\": %llu, \"regions\": %llu, \"back_bytes\": %llu}\n",
+                (unsigned long long)n_batches, world, (unsigned long long)n_rec, (unsigned long long)n_regions,
+                (unsigned long long)(sizeof(katgpu_record_stats) * n_rec + sizeof(katgpu_region) * n_regions));
+    }
     return KATGPU_OK;
 }
 

@@ -1,6 +1,7 @@
 // kg_query.hip -- a sequence or keys against a table, which is left as it is: batch lookups (katgpu_table_get*), per-position profiles
 // (katgpu_table_profile_*; _gathered_host: of a table that lies on several ranks, gathered on rank 0), the per-record hit counts of `kat filter seq` (katgpu_table_seq_hits_*; _gathered_host: summed over the ranks' tables on rank 0).
-// The host forms send their input through the device in batches.  What sect and cold ask per record is kg_per_record.hip's.
+// The host forms send their input through the device in batches.  What sect and cold ask per record is kg_per_record.hip's, the
+// gathered form included: it runs this unit's gather (ProfileGather, kg_comm.hpp).
 #include "kg_comm.hpp"
 #include "kg_query_kernels.hpp"
 #include "kg_filter.hpp"
@@ -97,69 +98,50 @@ extern "C" int katgpu_table_profile_host(katgpu_table* t, const char* bases, siz
 static const size_t g_gather_batch = (size_t)std::min<uint64_t>(std::max<uint64_t>(hook_u64("KATGPU_TEST_GATHER_BATCH", (uint64_t)32 << 20), 1), (uint64_t)1 << 31);   // tests: window starts per batch of profile_gathered_host (a run names a window in 32 bits)
 static const int64_t g_gather_nomem = hook("KATGPU_TEST_GATHER_NOMEM") ? atoll(hook("KATGPU_TEST_GATHER_NOMEM")) : -1;   // tests: this rank reports that it could not allocate
 
-// Collective, after katgpu_exchange_merge: every rank walks the same bases in batches of g_gather_batch window starts (each batch
-// re-sends the k-1 bases it shares with the next one, as katgpu_table_profile_host does) and keeps (window, count) of the windows
-// whose k-mer it owns and counts (k_profile_owned); the runs' lengths go round, the runs themselves to rank 0 -- one grouped
-// transfer per batch, indices and counts of a run as two messages, behind rank 0's own run in the buffer that run was written to:
-// the runs of a batch hold at most a record per window start between them, so one buffer of that size takes them all -- and rank 0
-// scatters them into the batch's dense array (k_profile_scatter), which goes to `counts` through the stream.
-// From the pool, per window start of a batch: 12 bytes of run on every rank and 8 of dense counts on rank 0, beside the batch's bases.
-extern "C" int katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_table* t, const char* bases, size_t n, int canonicalise, uint64_t* counts) {
-    if (!comm || !t) return KATGPU_ERR_INVALID_ARG;
+static const bool g_forbid_profile_gathered = hook_u64("KATGPU_TEST_FORBID_PROFILE_GATHERED", 0) != 0;   // tests: a driver that should gather no per-position counts on the host asks for none
+
+// The gather itself (kg_comm.hpp: ProfileGather).  Every rank walks the same bases in batches of g_gather_batch window starts and keeps
+// (window, count) of the windows whose k-mer it owns and counts (k_profile_owned); the runs' lengths go round, the runs themselves to
+// rank 0 -- one grouped transfer per batch, indices and counts of a run as two messages, behind rank 0's own run in the buffer that run
+// was written to: the runs of a batch hold at most a record per window start between them, so one buffer of that size takes them all --
+// and rank 0 scatters them into the batch's dense array (k_profile_scatter): its own scratch, which goes to the host through the
+// stream, or the batch's stretch of an array the caller keeps on the device.
+int ProfileGather::prepare(size_t max_starts, bool stage_bases, bool stage_counts) {
+    katgpu_ctx* c = t->ctx;
+    const int rank = katgpu_comm_rank(comm);
+    batch = std::max<size_t>(std::min(max_starts, g_gather_batch), 1);
+    idx_off = batch * sizeof(uint64_t); len_off = align_up(idx_off + batch * sizeof(uint32_t), 16);
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = refresh_counters(t); if (rc) return rc;
+    if (g_gather_nomem == rank || (stage_bases && db.pooled(c, batch + t->dv.k - 1 + 64) != hipSuccess) || run.pooled(c, len_off + 16) != hipSuccess ||
+        (rank == 0 && stage_counts && dense.pooled(c, batch * sizeof(uint64_t)) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(c, KATGPU_ERR_NOMEM, "profile gathered: no device memory for a batch of %zu window starts", batch);
+    }
+    return KATGPU_OK;
+}
+
+int ProfileGather::gather(const char* bases, const uint8_t* dev_bases, size_t n, uint64_t* counts, uint64_t* dev_counts) {
     katgpu_ctx* c = t->ctx;
     const int rank = katgpu_comm_rank(comm), world = katgpu_comm_world(comm);
     const uint32_t k = t->dv.k;
     const bool wide = t->dv.keys_b != nullptr;
-    // ---- one sequence length, one k and usable pointers everywhere, before anything else: all ranks go on, or none does ----
-    {
-        const uint64_t mine[3] = {(uint64_t)n, k, (uint64_t)((n && !bases) || (rank == 0 && n >= k && !counts))};
-        std::vector<uint64_t> all((size_t)world * 3, 0);
-        const int crc = allgather_u64(comm, mine, 3, all.data());
-        if (crc) return crc;
-        for (int p = 0; p < world; ++p) {
-            if (all[(size_t)p * 3] != all[0] || all[(size_t)p * 3 + 1] != all[1])
-                return fail(c, KATGPU_ERR_INVALID_ARG, "profile gathered: the ranks disagree: rank 0 has %llu bases at k = %llu, rank %d %llu at k = %llu",
-                            (unsigned long long)all[0], (unsigned long long)all[1], p, (unsigned long long)all[(size_t)p * 3], (unsigned long long)all[(size_t)p * 3 + 1]);
-            if (all[(size_t)p * 3 + 2]) return fail(c, KATGPU_ERR_INVALID_ARG, "profile gathered: rank %d was given no bases, or rank 0 no room for the counts", p);
-        }
-    }
     if (n < k) return KATGPU_OK;
     const size_t n_out = n - k + 1;
-    const size_t batch = std::min(n_out, g_gather_batch);
-    // ---- everything a batch needs: the run's counts | its indices | its length, the dense array on rank 0 ----
-    DevBuf db, run, dense;
-    const size_t idx_off = batch * sizeof(uint64_t), len_off = align_up(idx_off + batch * sizeof(uint32_t), 16);
-    auto prepare = [&]() -> int {
-        HIPCHK(c, hipSetDevice(c->device));
-        int rc = refresh_counters(t); if (rc) return rc;
-        if (g_gather_nomem == rank || db.pooled(c, batch + k - 1 + 64) != hipSuccess || run.pooled(c, len_off + 16) != hipSuccess ||
-            (rank == 0 && dense.pooled(c, batch * sizeof(uint64_t)) != hipSuccess)) {
-            (void)hipGetLastError();
-            return fail(c, KATGPU_ERR_NOMEM, "profile gathered: no device memory for a batch of %zu window starts", batch);
-        }
-        return KATGPU_OK;
-    };
-    int rc = comm_agree_to_start(comm, prepare(), [&](int p, int code) {
-        if (code == KATGPU_ERR_NOMEM) return fail(c, code, "profile gathered: rank %d of %d has no device memory for a batch of %zu window starts", p, world, batch);
-        return fail(c, code, "profile gathered: rank %d could not read its table", p);
-    });
-    if (rc) return rc;
     uint64_t* run_cnt = run.as<uint64_t>();
     uint32_t* run_idx = (uint32_t*)(run.as<uint8_t>() + idx_off);
     unsigned long long* run_len = (unsigned long long*)(run.as<uint8_t>() + len_off);
-
-    // ---- the batches.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end (comm_agree_done) ----
-    uint64_t n_batches = 0, records = 0, wire_bytes = 0;
     std::vector<uint64_t> lens((size_t)world, 0);
     auto one_batch = [&](size_t pos) -> int {
         const size_t starts = std::min(batch, n_out - pos), nb = starts + k - 1;
         unsigned long long own = 0;
-        HIPCHK(c, hipMemcpyAsync(db.p, bases + pos, nb, hipMemcpyHostToDevice, c->stream));
+        const uint8_t* b = dev_bases ? dev_bases + pos : db.as<uint8_t>();
+        if (!dev_bases) HIPCHK(c, hipMemcpyAsync(db.p, bases + pos, nb, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemsetAsync(run_len, 0, sizeof own, c->stream));
         {
             ScopedTimer tm(c, KATGPU_K_PROFILE, starts);
-            launch_aligned_wide(c, aligned16(db.p), wide, starts, chunk_starts(wide), [&](auto A, auto W, dim3 grid, uint64_t n_chunks) {
-                hipLaunchKernelGGL((k_profile_owned<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, t->dev(), t->n_ovf, canonicalise, db.as<uint8_t>(), (uint64_t)nb, n_chunks, (uint32_t)rank, (uint32_t)world, run_idx, run_cnt, run_len);
+            launch_aligned_wide(c, aligned16(b), wide, starts, chunk_starts(wide), [&](auto A, auto W, dim3 grid, uint64_t n_chunks) {
+                hipLaunchKernelGGL((k_profile_owned<decltype(A)::value, decltype(W)::value>), grid, dim3(COUNT_BLOCK), 0, c->stream, t->dev(), t->n_ovf, canonicalise, b, (uint64_t)nb, n_chunks, (uint32_t)rank, (uint32_t)world, run_idx, run_cnt, run_len);
             });
             HIPCHK(c, hipGetLastError());
         }
@@ -185,23 +167,65 @@ extern "C" int katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_tabl
         }
         ++n_batches; records += total; wire_bytes += remote * (sizeof(uint32_t) + sizeof(uint64_t));
         if (rank != 0) return KATGPU_OK;
-        uint64_t* d = dense.as<uint64_t>();
+        uint64_t* d = dev_counts ? dev_counts + pos : dense.as<uint64_t>();
         {
             ScopedTimer tm(c, KATGPU_K_PROFILE, 0);
             hipLaunchKernelGGL(k_profile_scatter<true>, dim3((unsigned)grid_for(c, starts, 256, 8)), dim3(256), 0, c->stream, d, (uint64_t)starts, run_idx, run_cnt, (uint64_t)0);
             if (total) hipLaunchKernelGGL(k_profile_scatter<false>, dim3((unsigned)grid_for(c, total, 256, 8)), dim3(256), 0, c->stream, d, (uint64_t)starts, run_idx, run_cnt, total);
             HIPCHK(c, hipGetLastError());
         }
-        HIPCHK(c, hipMemcpyAsync(counts + pos, d, starts * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (!dev_counts) HIPCHK(c, hipMemcpyAsync(counts + pos, d, starts * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));             // (the run buffer is the next batch's)
         return KATGPU_OK;
     };
+    int rc = KATGPU_OK;
     for (size_t pos = 0; pos < n_out && !rc; pos += batch) rc = one_batch(pos);
-    rc = comm_agree_done(comm, rc, "profile gathered: rank %d failed");
-    if (rc) return rc;
-    if (rank == 0 && g_timing)
+    return rc;
+}
+
+void ProfileGather::print_timing() const {
+    if (katgpu_comm_rank(comm) == 0 && g_timing)
         fprintf(stderr, "katgpu_timing {\"phase\": \"profile_gathered\", \"batches\": %llu, \"ranks\": %d, \"records\": %llu, \"wire_bytes\": %llu}\n",
-                (unsigned long long)n_batches, world, (unsigned long long)records, (unsigned long long)wire_bytes);
+                (unsigned long long)n_batches, katgpu_comm_world(comm), (unsigned long long)records, (unsigned long long)wire_bytes);
+}
+
+int gather_peer_error(katgpu_comm* comm, const ProfileGather& g, int p, int code) {
+    katgpu_ctx* c = g.t->ctx;
+    if (code == KATGPU_ERR_NOMEM) return fail(c, code, "profile gathered: rank %d of %d has no device memory for a batch of %zu window starts", p, katgpu_comm_world(comm), g.batch);
+    return fail(c, code, "profile gathered: rank %d could not read its table", p);
+}
+
+// Collective, after katgpu_exchange_merge: the gather above over the whole sequence (each batch re-sends the k-1 bases it shares with the
+// next one, as katgpu_table_profile_host does), the dense counts of every batch to `counts` on rank 0.
+// From the pool, per window start of a batch: 12 bytes of run on every rank and 8 of dense counts on rank 0, beside the batch's bases.
+extern "C" int katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_table* t, const char* bases, size_t n, int canonicalise, uint64_t* counts) {
+    if (!comm || !t) return KATGPU_ERR_INVALID_ARG;
+    katgpu_ctx* c = t->ctx;
+    if (g_forbid_profile_gathered) return fail(c, KATGPU_ERR_INVALID_ARG, "katgpu_table_profile_gathered_host is forbidden (KATGPU_TEST_FORBID_PROFILE_GATHERED)");
+    const int rank = katgpu_comm_rank(comm), world = katgpu_comm_world(comm);
+    const uint32_t k = t->dv.k;
+    // ---- one sequence length, one k and usable pointers everywhere, before anything else: all ranks go on, or none does ----
+    {
+        const uint64_t mine[3] = {(uint64_t)n, k, (uint64_t)((n && !bases) || (rank == 0 && n >= k && !counts))};
+        std::vector<uint64_t> all((size_t)world * 3, 0);
+        const int crc = allgather_u64(comm, mine, 3, all.data());
+        if (crc) return crc;
+        for (int p = 0; p < world; ++p) {
+            if (all[(size_t)p * 3] != all[0] || all[(size_t)p * 3 + 1] != all[1])
+                return fail(c, KATGPU_ERR_INVALID_ARG, "profile gathered: the ranks disagree: rank 0 has %llu bases at k = %llu, rank %d %llu at k = %llu",
+                            (unsigned long long)all[0], (unsigned long long)all[1], p, (unsigned long long)all[(size_t)p * 3], (unsigned long long)all[(size_t)p * 3 + 1]);
+            if (all[(size_t)p * 3 + 2]) return fail(c, KATGPU_ERR_INVALID_ARG, "profile gathered: rank %d was given no bases, or rank 0 no room for the counts", p);
+        }
+    }
+    if (n < k) return KATGPU_OK;
+    // ---- everything a batch needs: the run's counts | its indices | its length, the dense array on rank 0 ----
+    ProfileGather g{comm, t, canonicalise};
+    int rc = comm_agree_to_start(comm, g.prepare(n - k + 1, true, true), [&](int p, int code) { return gather_peer_error(comm, g, p, code); });
+    if (rc) return rc;
+    // ---- the batches.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end (comm_agree_done) ----
+    rc = comm_agree_done(comm, g.gather(bases, nullptr, n, counts, nullptr), "profile gathered: rank %d failed");
+    if (rc) return rc;
+    g.print_timing();
     return KATGPU_OK;
 }
 
@@ -255,14 +279,6 @@ extern "C" int katgpu_table_seq_hits_host(katgpu_table* t, const char* bases, si
 // ------------------------------------------------------------------ the hits of a table that lies on several ranks ----
 
 static const int64_t g_hits_gather_nomem = hook("KATGPU_TEST_HITS_GATHER_NOMEM") ? atoll(hook("KATGPU_TEST_HITS_GATHER_NOMEM")) : -1;   // tests: this rank reports that it could not allocate
-
-// what the ranks compare of their records: every start and length, in order, folded into one word
-static uint64_t records_checksum(const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec) {
-    uint64_t h = 0x9E3779B97F4A7C15ULL;
-    auto fold = [&](uint64_t x) { h ^= x; h *= 0xFF51AFD7ED558CCDULL; h ^= h >> 32; };
-    for (size_t r = 0; r < n_rec; ++r) { fold(rec_start[r]); fold(rec_len[r]); }
-    return h;
-}
 
 // Collective, after katgpu_exchange_merge: every rank walks the same records in the batches of katgpu_table_seq_hits_host (for_record_batches:
 // at most g_hits_batch bases and g_hits_recs records) and counts, per record, the hits among the windows whose k-mer it owns

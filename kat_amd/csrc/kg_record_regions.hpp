@@ -9,8 +9,8 @@
 //  K17 k_regions_emit    the masks again, no table access: the i-th run start writes (record, start) of region i, the i-th run end its
 //                        stop -- starts and ends alternate in position order, so they meet in the same region
 //
-// K14 uses the front end of kg_windows.hpp (load16 / encode16 / Chunk<W>::Tile / Window) and k_rstats_long's walk along the records, so
-// one body serves both key widths.  Records are given by start and length, increasing and disjoint (the convention of k_seq_hits); a
+// K14 uses the front end of kg_windows.hpp (load16 / encode16 / Chunk<W>::Tile / Window), k_rstats_long's walk along the records and
+// its two sources of counts (kg_record_stats.hpp: CountsTable / CountsDense), so one body serves both key widths and both sources.  Records are given by start and length, increasing and disjoint (the convention of k_seq_hits); a
 // window belongs to a record when it lies wholly inside it; an invalid window (a byte outside ACGTacgt) counts 0.  A position's bit in a
 // mask is bit (position & 63) of word (position >> 6): a lane's 16 starts are one 16-bit store, and nobody else writes them.
 // Whether a run opens at a position depends on the position before it, which another lane, chunk or block owns: K15 and K17 take
@@ -18,7 +18,7 @@
 // never continues into another record: records that touch have their last and first windows side by side only at k = 1, and there
 // the "first window" bit cuts the run.
 #pragma once
-#include "kg_filter.hpp"
+#include "kg_record_stats.hpp"
 
 namespace kg {
 
@@ -36,16 +36,16 @@ __device__ __forceinline__ bool rg_in(const RgRanges& rg, int q, uint64_t c) { r
 // runs along its 16 positions, knows the record they lie in, looks up the windows that lie inside it (0 for an invalid one) and keeps
 // three 16-bit words: first window of a record | in range 0 | in range 1.  Every position below 64 * n_words gets its bits, zeros where
 // no window starts: the masks need no clearing.  mask: 1 + rg.n arrays of 4 * n_words 16-bit words.
-template <bool ALIGNED, bool W>
+template <bool ALIGNED, bool W, typename Src>
 __global__ void __launch_bounds__(COUNT_BLOCK)
-k_regions_mask(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
+k_regions_mask(Src src, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
                const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len, uint64_t n_rec, RgRanges rg, uint64_t n_words,
                uint16_t* __restrict__ mask) {
     constexpr int CS = Chunk<W>::STARTS;
     __shared__ typename Chunk<W>::Tile s;
     __shared__ uint64_t s_r[2];
     const uint32_t tid = threadIdx.x;
-    const uint32_t k = t.k;
+    const uint32_t k = src.k();
     s.pad();
 
     for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
@@ -79,11 +79,7 @@ k_regions_mask(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __re
                 while (pos >= ns) { ++r; rs = ns; re = rs + rec_len[r]; ns = (uint64_t)(r + 1) < r_hi ? rec_start[r + 1] : ~0ULL; }
                 if (r < (int64_t)r_lo || pos < rs || pos + k > re || pos + k > n) continue;
                 uint64_t c = 0;
-                if (lw.valid()) {
-                    auto key = lw.fwd();
-                    if (canonicalise) key = kmer_canonical(key, k);
-                    c = table_get(t, key, n_ovf);
-                }
+                if (lw.valid()) c = src.get(lw, pos);
                 first |= (uint32_t)(pos == rs) << j;
                 in0 |= (uint32_t)rg_in(rg, 0, c) << j;
                 in1 |= (uint32_t)(rg.n > 1 && rg_in(rg, 1, c)) << j;

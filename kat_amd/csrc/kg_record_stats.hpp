@@ -2,7 +2,7 @@
 // (src/sect.cc:490-589) and Cold::processSeq (src/cold.cc:303-406) compute from a record's per-position counts -- their sum, the
 // non-zero and the invalid windows, the G/C and N bases, and sorted(counts)[nb / 2] -- without the counts leaving the device.
 //
-//  K11 k_rstats_short   records of at most RS_SHORT_WINDOWS windows: counts looked up into LDS, reduced and radix-selected there
+//  K11 k_rstats_short   records of at most RS_SHORT_WINDOWS windows: counts looked up (or read from a dense array: CountsTable / CountsDense) into LDS, reduced and radix-selected there
 //  K12 k_rstats_long    the other records: counts to a device scratch array that holds the long records' windows and no others,
 //                       sums by k_seq_hits' pattern
 //  K13 k_rstats_hist / k_rstats_pick   exact multi-pass radix select over that array, 8 bits a pass, per record
@@ -60,6 +60,26 @@ __device__ __forceinline__ uint32_t rs_range_mask(uint32_t word, uint32_t a, uin
     const uint32_t lo = a > w0 ? a - w0 : 0, hi = b < w0 + BASES_PER_LANE ? b - w0 : BASES_PER_LANE;
     return ((1u << hi) - 1) & ~((1u << lo) - 1);
 }
+// Where a window's count comes from, a compile-time choice of K11, K12 and K14 (kg_record_regions.hpp); the rest of their bodies is one.
+// get(lw, p): the count of the valid window lw, which starts at base p of the buffer -- asked for the windows of records only.
+//  CountsTable  looked up in a table of this rank (katgpu_table_record_*)
+//  CountsDense  counts[p], a dense array of n_counts = n - k + 1 words made elsewhere (katgpu_record_*_from_counts_device: the gathered
+//               profile of a table that lies on several ranks); 8-byte aligned, no more
+struct CountsTable {
+    DevTable t; uint32_t n_ovf; int canonicalise;
+    __device__ __forceinline__ uint32_t k() const { return t.k; }
+    template <typename Win> __device__ __forceinline__ uint64_t get(const Win& lw, uint64_t) const {
+        auto key = lw.fwd();
+        if (canonicalise) key = kmer_canonical(key, t.k);
+        return table_get(t, key, n_ovf);
+    }
+};
+struct CountsDense {
+    const uint64_t* __restrict__ counts; uint64_t n_counts; uint32_t k_;
+    __device__ __forceinline__ uint32_t k() const { return k_; }
+    template <typename Win> __device__ __forceinline__ uint64_t get(const Win&, uint64_t p) const { return p < n_counts ? counts[p] : 0; }
+};
+
 // a lane's 16 bytes: which are G g C c, which are N n (bit j = byte j)
 __device__ __forceinline__ void rs_base_masks(const uint32_t (&w)[4], uint32_t& gc, uint32_t& nn) {
     gc = 0; nn = 0;
@@ -77,9 +97,9 @@ __device__ __forceinline__ void rs_base_masks(const uint32_t (&w)[4], uint32_t& 
 // counts and masks, the nb/2-th smallest by a bit-wise radix select from the highest bit set in any count of the record down (genomic
 // counts: a dozen rounds of one LDS read per 64 windows and a ballot).  A wave loads the records 64 at a time and walks those a ballot
 // names, so runs of empty records cost one load.  `out` was cleared by the caller: an empty record is never written.
-template <bool ALIGNED, bool W>
+template <bool ALIGNED, bool W, typename Src>
 __global__ void __launch_bounds__(COUNT_BLOCK)
-k_rstats_short(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_tiles,
+k_rstats_short(Src src, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_tiles,
                const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len, uint64_t n_rec, uint32_t limit,
                unsigned long long* __restrict__ out) {
     __shared__ typename Chunk<W>::Tile s;
@@ -87,7 +107,7 @@ k_rstats_short(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __re
     __shared__ uint32_t s_own[COUNT_BLOCK], s_inv[COUNT_BLOCK], s_gc[COUNT_BLOCK], s_nn[COUNT_BLOCK];
     __shared__ uint64_t s_r[2];
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t k = t.k;
+    const uint32_t k = src.k();
     s.pad();
 
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -141,11 +161,8 @@ k_rstats_short(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __re
                 for (int j = 0; j < BASES_PER_LANE; ++j, lw.step()) {
                     if (!((own >> j) & 1)) continue;
                     uint64_t c = 0;
-                    if (lw.valid()) {
-                        auto key = lw.fwd();
-                        if (canonicalise) key = kmer_canonical(key, k);
-                        c = table_get(t, key, n_ovf);
-                    } else inv |= 1u << j;
+                    if (lw.valid()) c = src.get(lw, off + j);
+                    else inv |= 1u << j;
                     s_cnt[tid * BASES_PER_LANE + j] = c;
                 }
             }
@@ -244,9 +261,9 @@ k_rstats_classify(const uint64_t* __restrict__ rec_len, uint64_t n_rec, uint32_t
 // Chunk<W>::STARTS bytes and the windows that start on them), knows the record they lie in, writes every window's count to the record's stretch of cnt[] (0
 // for an invalid one; the radix select reads them there) and keeps its run of sum / non-zero / invalid / G+C / N / OR-of-counts for that
 // record, which goes to LDS bins when the record changes and from there to HBM once per chunk, one atomic per record and field.
-template <bool ALIGNED, bool W>
+template <bool ALIGNED, bool W, typename Src>
 __global__ void __launch_bounds__(COUNT_BLOCK)
-k_rstats_long(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
+k_rstats_long(Src src, const uint8_t* __restrict__ bases, uint64_t n, uint64_t n_chunks,
               const uint64_t* __restrict__ rec_start, const uint64_t* __restrict__ rec_len, uint64_t n_rec,
               const uint32_t* __restrict__ rec_slot, uint64_t* __restrict__ cnt, uint64_t n_cnt, RsSel* __restrict__ sel,
               unsigned long long* __restrict__ out) {
@@ -256,7 +273,7 @@ k_rstats_long(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __res
     __shared__ uint32_t s_u[4][RS_LDS_RECS];                       // non-zero, invalid, G+C, N
     __shared__ uint64_t s_r[2];
     const uint32_t tid = threadIdx.x;
-    const uint32_t k = t.k;
+    const uint32_t k = src.k();
     s.pad();
     if (tid < RS_LDS_RECS) { s_sum[tid] = 0; s_or[tid] = 0; s_u[0][tid] = 0; s_u[1][tid] = 0; s_u[2][tid] = 0; s_u[3][tid] = 0; }
 
@@ -324,9 +341,7 @@ k_rstats_long(DevTable t, uint32_t n_ovf, int canonicalise, const uint8_t* __res
                 if (pos + k <= re && pos + k <= n) {
                     uint64_t c = 0;
                     if (lw.valid()) {
-                        auto key = lw.fwd();
-                        if (canonicalise) key = kmer_canonical(key, k);
-                        c = table_get(t, key, n_ovf);
+                        c = src.get(lw, pos);
                         sum += c; orv |= c; nz += c != 0;
                     } else ++ninv;
                     const uint64_t ci = coff + (pos - rs);
