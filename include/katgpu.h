@@ -109,7 +109,7 @@ void katgpu_table_free(katgpu_table* t);
  * receives the message on failure.  This is what katgpu_count_files streams to the GPU. */
 int  katgpu_parse_file(const char* path, uint32_t trim5p, uint8_t** bases, size_t* n, const char** err_msg);
 /* The same for one input group (InputHandler::count's file list, lib/src/input_handler.cc:180-202): the stream
- * katgpu_count_files feeds to the counter for these paths.  Files that stream (gzip, 5' trim, small) are read
+ * katgpu_count_files feeds to the counter for these paths.  Files that stream (gzip, small) are read
  * concurrently, so the stream interleaves their blocks -- with 'N' + the file's previous k-1 bytes at every switch
  * of source, which keeps the k-mer multiset equal to that of the files read one after the other.  The byte ORDER
  * may differ from call to call; KATGPU_INGEST_FILES=1 reads the files in sequence. */
@@ -121,6 +121,11 @@ void katgpu_free_host(void* p);
  * Returns KATGPU_OK, or KATGPU_ERR_FASTQ when the bytes are not whole plain four-line records (such pieces go through the host state
  * machine, katgpu_parse_file's, instead: it alone knows what multi-line records and odd quality lengths mean). */
 int  katgpu_strip_fastq(const uint8_t* fastq, size_t n, uint8_t* out, size_t* out_n);
+/* The same under a 5' trim (--5ptrim): every record gives its sequence line without the first trim5p bytes, then 'N'.  KATGPU_ERR_FASTQ
+ * also when a record is not plain under the trim -- a sequence line no longer than trim5p, or one whose byte trim5p is '+': there the
+ * reference's is.ignore(trim5p) runs over a line end or uncovers the '+' (DESIGN.md section 4), which the state machine alone follows.
+ * The quality line has the UNTRIMMED sequence's length.  trim5p = 0: katgpu_strip_fastq. */
+int  katgpu_strip_fastq_trim(const uint8_t* fastq, size_t n, uint32_t trim5p, uint8_t* out, size_t* out_n);
 /* The inflated bytes of ONE ordinary gzip stream through the thread team that katgpu_count_files / katgpu_parse_file use for .gz
  * files of size (kg_pgzip.cpp: the file cut into chunks, each entered at a deflate block start found by search and decoded without
  * its 32 KiB of history, stitched and resolved in order; every member's CRC-32 and ISIZE checked) -- for tests and tools: the

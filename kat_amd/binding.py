@@ -31,7 +31,7 @@ EXPORTS = (
     "katgpu_table_merge_host", "katgpu_table_geometry", "katgpu_table_extract_sizes", "katgpu_table_extract", "katgpu_table_clear",
     "katgpu_table_merge_device32", "katgpu_table_merge_regions", "katgpu_profile_reset", "katgpu_profile_get", "katgpu_dev_alloc",
     "katgpu_dev_free", "katgpu_dev_upload", "katgpu_dev_download", "katgpu_dev_mem_info",
-    "katgpu_synth_genome_device", "katgpu_synth_reads_device", "katgpu_parse_file", "katgpu_parse_files", "katgpu_free_host", "katgpu_strip_fastq", "katgpu_inflate_file",
+    "katgpu_synth_genome_device", "katgpu_synth_reads_device", "katgpu_parse_file", "katgpu_parse_files", "katgpu_free_host", "katgpu_strip_fastq", "katgpu_strip_fastq_trim", "katgpu_inflate_file",
     "katgpu_table_get_wide", "katgpu_table_export_wide", "katgpu_table_merge_host_wide",
     "katgpu_table_partition_wide", "katgpu_table_merge_device_wide", "katgpu_table_regrows",
     "katgpu_jf_load", "katgpu_jf_dump", "katgpu_jf_write_records", "katgpu_jf_read_records", "katgpu_jf_last_error",
@@ -107,6 +107,7 @@ def load_library():
     L.katgpu_table_create.argtypes = [vp, u32, C.c_int, u64, C.c_int, pp]
     L.katgpu_table_create_like.argtypes = [vp, vp, u32, C.c_int, u64, C.c_int, pp]
     L.katgpu_count_files.argtypes = [vp, cpp, sz, C.POINTER(C.c_uint16)]
+    L.katgpu_count_files_sharded.argtypes = [vp, cpp, sz, C.POINTER(C.c_uint16), C.c_int, C.c_int]
     L.katgpu_count_bases_host.argtypes = [vp, vp, sz]
     L.katgpu_count_bases_device.argtypes = [vp, vp, sz]
     L.katgpu_table_free.argtypes = [vp]
@@ -215,14 +216,15 @@ def inflate_file(path, keep=True):
         L.katgpu_free_host(p)
 
 
-def strip_fastq(data):
-    """katgpu_strip_fastq: whole plain four-line FASTQ records -> their sequence lines, each followed by 'N' (bytes), or None when the
-    bytes are not exactly that."""
+def strip_fastq(data, trim5p=0):
+    """katgpu_strip_fastq / katgpu_strip_fastq_trim: whole plain four-line FASTQ records -> their sequence lines (without the first trim5p
+    bytes), each followed by 'N' (bytes), or None when the bytes are not exactly that or a record is not plain under the trim."""
     L = load_library()
     L.katgpu_strip_fastq.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
+    L.katgpu_strip_fastq_trim.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32, C.c_void_p, C.POINTER(C.c_size_t)]
     out = C.create_string_buffer(len(data) // 2 + 1)
     n = C.c_size_t()
-    rc = L.katgpu_strip_fastq(bytes(data), len(data), out, C.byref(n))
+    rc = L.katgpu_strip_fastq_trim(bytes(data), len(data), trim5p, out, C.byref(n)) if trim5p else L.katgpu_strip_fastq(bytes(data), len(data), out, C.byref(n))
     return out.raw[:n.value] if rc == 0 else None
 
 

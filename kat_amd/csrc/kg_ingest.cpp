@@ -208,8 +208,11 @@ struct Segment {
 
 int64_t find_record_start(ParseState::Type type, const uint8_t* buf, int64_t buf_off, int64_t len, int64_t from) { return find_cut(type, buf, buf_off, len, from); }
 
-bool strip_fastq_records(const uint8_t* p, size_t n, uint8_t* out, size_t* out_n) {
+bool strip_fastq_records(const uint8_t* p, size_t n, uint8_t* out, size_t* out_n) { return strip_fastq_records(p, n, 0, out, out_n); }
+
+bool strip_fastq_records(const uint8_t* p, size_t n, uint32_t trim5p, uint8_t* out, size_t* out_n) {
     const uint8_t* const end = p + n;
+    const size_t t = trim5p;
     uint8_t* o = out;
     while (p < end) {
         if (*p != '@') return false;
@@ -219,7 +222,7 @@ bool strip_fastq_records(const uint8_t* p, size_t n, uint8_t* out, size_t* out_n
         const uint8_t* se = s < end ? (const uint8_t*)memchr(s, '\n', (size_t)(end - s)) : nullptr;  // end of the sequence line
         if (!se) return false;
         const size_t len = (size_t)(se - s);
-        if (len == 0 || *s == '+') return false;                                                     // (a record without bases, or a "sequence" line that the reference's loop takes for the '+' line of one -- it stops reading bases at the first line that begins with '+', mer_overlap_sequence_parser.hpp:226-233 --: the state machine's to say, it words the reference's error)
+        if (len <= t || s[t] == '+') return false;                                                   // (plain under the trim, kg_scan.hpp; without one: a record without bases, or a "sequence" line that the reference's loop takes for the '+' line of one -- it stops reading bases at the first line that begins with '+', mer_overlap_sequence_parser.hpp:226-233 --: the state machine's to say, it words the reference's error)
         const uint8_t* pl = se + 1;
         if (pl >= end || *pl != '+') return false;                                                   // (a second sequence line: not plain)
         const uint8_t* ple = (const uint8_t*)memchr(pl, '\n', (size_t)(end - pl));                   // end of the '+' line
@@ -227,8 +230,8 @@ bool strip_fastq_records(const uint8_t* p, size_t n, uint8_t* out, size_t* out_n
         const uint8_t* q = ple + 1;
         if ((size_t)(end - q) < len + 1 || q[len] != '\n') return false;                             // the quality line: exactly the sequence's length ...
         if (memchr(q, '\n', len)) return false;                                                    // ... in ONE line
-        memcpy(o, s, len);
-        o += len;
+        memcpy(o, s + t, len - t);
+        o += len - t;
         *o++ = 'N';
         p = q + len + 1;
     }
@@ -238,7 +241,7 @@ bool strip_fastq_records(const uint8_t* p, size_t n, uint8_t* out, size_t* out_n
 
 // The conditions under which the team takes a file; *size_out / *first_byte for the caller that goes on.
 static bool team_applies_impl(const char* path, uint32_t trim5p, int64_t* size_out, uint8_t* first_byte) {
-    if (trim5p) return false;                                // is.ignore(trim5p) swallows line starts: keep that case on the streaming path
+    (void)trim5p;                                            // (every piece's machine carries the trim; one that ran across a guessed cut leaves the piece before it off a record boundary)
     struct stat st;
     if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false;
     if ((uint64_t)st.st_size < env_u64("KATGPU_INGEST_MIN_BYTES", (uint64_t)256 << 20)) return false;
@@ -273,6 +276,7 @@ int parse_file_parallel(const char* path, uint32_t trim5p, const std::function<i
     struct Closer { int fd; ~Closer() { ::close(fd); } } closer{fd};
     ParseState state;                                        // the machine's TRUE state at file offset `pos`
     state.begin(first);
+    state.trim5p = trim5p;
     const ParseState::Type type = state.type;
     int64_t pos = 0;
 
@@ -307,7 +311,7 @@ int parse_file_parallel(const char* path, uint32_t trim5p, const std::function<i
                 if (g.s < 0 || g.e < 0 || g.e < g.s) { g.s = g.e = -1; return; }
                 ParseState ps = first_state;
                 if (i > 0) {                                 // assumed: a record starts here, i.e. the piece before ended at a boundary
-                    ps = ParseState(); ps.type = type;
+                    ps = ParseState(); ps.type = type; ps.trim5p = trim5p;
                     ps.st = type == ParseState::FASTA ? ParseState::LOOP_CHECK : ParseState::QUAL_DONE_SKIPNL;
                 }
                 g.out.reserve((size_t)(g.e - g.s));
@@ -732,6 +736,12 @@ extern "C" int katgpu_strip_fastq(const uint8_t* fastq, size_t n, uint8_t* out, 
     if ((n && !fastq) || !out || !out_n) return KATGPU_ERR_INVALID_ARG;
     *out_n = 0;
     return kg::strip_fastq_records(fastq, n, out, out_n) ? KATGPU_OK : KATGPU_ERR_FASTQ;
+}
+
+extern "C" int katgpu_strip_fastq_trim(const uint8_t* fastq, size_t n, uint32_t trim5p, uint8_t* out, size_t* out_n) {
+    if ((n && !fastq) || !out || !out_n) return KATGPU_ERR_INVALID_ARG;
+    *out_n = 0;
+    return kg::strip_fastq_records(fastq, n, trim5p, out, out_n) ? KATGPU_OK : KATGPU_ERR_FASTQ;
 }
 
 extern "C" int katgpu_parse_file(const char* path, uint32_t trim5p, uint8_t** bases, size_t* n, const char** err_msg) {

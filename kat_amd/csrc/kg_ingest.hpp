@@ -57,6 +57,9 @@ int64_t find_record_start(ParseState::Type type, const uint8_t* buf, int64_t buf
 // newline, a stray byte.
 // The reader threads of kg_scan.hip run it on record-aligned pieces of large FASTQ files, so that only the bases cross PCIe.
 bool strip_fastq_records(const uint8_t* p, size_t n, uint8_t* out, size_t* out_n);
+// ... under a 5' trim: every record must be plain under it (kg_scan.hpp states the rule: a sequence line longer than the trim whose byte
+// `trim5p` is not '+'), and gives its sequence line without the first trim5p bytes.  The quality line still has the untrimmed length.
+bool strip_fastq_records(const uint8_t* p, size_t n, uint32_t trim5p, uint8_t* out, size_t* out_n);
 
 class SeqFileParser {
 public:
@@ -83,7 +86,9 @@ private:
 // FASTA; "\n@", a line, then "\n+" for FASTQ): a piece is accepted only if the piece before it -- parsed from a state known to
 // be right -- ends in the record-boundary state exactly where the piece begins; otherwise the rest of the file goes through
 // the machine serially from that known state.  The output is therefore byte-identical to the streaming parser's whatever the
-// file looks like.  Returns a katgpu_status, or -1 when the file does not qualify (the caller then streams it).
+// file looks like -- under a 5' trim too: every piece's machine carries it, and a trim that runs across a guessed cut (kg_scan.hpp:
+// a record that is not plain under the trim) leaves the piece before it in a trim state, which is no record boundary.
+// Returns a katgpu_status, or -1 when the file does not qualify (the caller then streams it).
 int parse_file_parallel(const char* path, uint32_t trim5p, const std::function<int(const uint8_t*, size_t)>& sink, std::string* err);
 bool team_applies(const char* path, uint32_t trim5p);      // would parse_file_parallel take this file?
 
@@ -108,7 +113,7 @@ bool pgz_applies(const char* path, uint32_t trim5p);
 // One input group (InputHandler::count's file list) -> the base stream the counter consumes, handed to `sink` piece by piece.
 // Files never join (mer_overlap_sequence_parser.hpp:151-155), so the stream is a sequence of file pieces with an 'N' wherever
 // the source changes.  Large plain files and BGZF files go through their thread teams, one file after the other.  Runs of files that have to
-// stream (gzip, 5' trim, small) are read CONCURRENTLY, one reader thread per file (inflate is ~0.3 GB/s per stream, and paired
+// stream (gzip, small) are read CONCURRENTLY, one reader thread per file (inflate is ~0.3 GB/s per stream, and paired
 // libraries come as two or more .gz files): the sink then sees the files' blocks interleaved, and every time the source
 // switches back to a file the stream carries 'N' followed by that file's previous k-1 bytes, so that each k-mer window of each
 // file appears in the stream exactly once.  The k-mer MULTISET of the stream is therefore that of the files read one by one

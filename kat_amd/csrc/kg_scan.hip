@@ -22,6 +22,11 @@
 // counter will be handed.  No scan kernel runs and half the bytes travel.  A segment that is not plain four-line FASTQ (multi-line
 // records, odd quality lengths, a last line without its newline, a record longer than the look-ahead) stops the fast path there: what was
 // committed is counted, and the file's rest goes through the host state machine from the last proven record start -- as above.
+//
+// A 5' trim stays on both paths: the scan kernels and the strip take it, and a record that is not plain under the trim (kg_scan.hpp's head
+// states the rule once) declines its batch or segment like any other the fast path cannot vouch for.  FASTA batches are cut at line
+// starts, so the scan reports whether a chunk ended on a header line: the next chunk's first line, or the host machine on a hand-over
+// (host_rest), begins with that record's trim still to come.
 #include "kg_host.hpp"
 #include "kg_ingest.hpp"
 #include "kg_scan.hpp"
@@ -65,7 +70,8 @@ static const uint64_t g_test_strip_fail_at = hook_u64("KATGPU_TEST_STRIP_FAIL_AT
 static const size_t g_strip_acc = (size_t)3 << 30;                // strip path: base stream per count call (one partition round of a 32 GB arena)
 
 bool device_scan_applies(const char* path, uint32_t trim5p, uint64_t* size_out, uint8_t* first_byte) {
-    if (g_scan_off || trim5p) return false;                       // (a 5' trim swallows line starts the way is.ignore does: the host machine's job)
+    (void)trim5p;                                                 // (a 5' trim no longer keeps a file off this path: kg_scan.hpp states which records are plain under one)
+    if (g_scan_off) return false;
     struct stat st;
     if (stat(path, &st) != 0 || !S_ISREG(st.st_mode)) return false;
     if ((uint64_t)st.st_size < (g_test_scan_batch || g_test_strip_segment ? 1 : g_scan_min_bytes)) return false;
@@ -90,6 +96,8 @@ struct RawFeeder {
     const char* path; int fd = -1;
     uint64_t size = 0;
     ScanType type = SCAN_FASTQ;
+    uint32_t trim = 0;                                            // the file's 5' trim (kg_scan.hpp: which records are plain under it)
+    bool after_hdr = false;                                       // FASTA under a trim: the line before the next chunk is a header line (the scan of the chunk before said so)
     size_t batch = 0, segment = 0, overlap = 0, buf_bytes = 0;
     // Sharding over the ranks of a multi-GPU run (FASTQ only): rank r takes batches r, r + world, ...  A chunk's two ends are found
     // from the file bytes around its batch's nominal ends by ONE function (kg_ingest: find_record_start) -- the rank that owns the
@@ -129,7 +137,7 @@ struct RawFeeder {
     std::vector<int> half_state;                                  // [2 * reader + half]: 0 free, 1 stripped and waiting for its copy to be issued, 2 copy issued (event recorded)
     std::vector<hipEvent_t> half_ev;
 
-    RawFeeder(katgpu_table* t_, const char* p) : t(t_), c(t_->ctx), path(p) {}
+    RawFeeder(katgpu_table* t_, const char* p, uint32_t trim5p) : t(t_), c(t_->ctx), path(p), trim(trim5p) {}
     ~RawFeeder() { shutdown(); release(); }
 
     void shutdown() {
@@ -319,7 +327,7 @@ struct RawFeeder {
                 if (lo < 0 || hi < 0 || lo > hi || (uint64_t)(hi - lo) / 2 + 1 > c->scan.pin_seg_bytes) sg.state = 2;
                 else {
                     sg.lo = (uint64_t)lo; sg.hi = (uint64_t)hi;
-                    if (!kg::strip_fastq_records(buf + (sg.lo - w0), (size_t)(sg.hi - sg.lo), sg.pin, &sg.out_n)) sg.state = 2;
+                    if (!kg::strip_fastq_records(buf + (sg.lo - w0), (size_t)(sg.hi - sg.lo), trim, sg.pin, &sg.out_n)) sg.state = 2;
                 }
                 if (map) {
                     struct stat st0;
@@ -458,14 +466,17 @@ struct RawFeeder {
 
     // The record scan of raw[buf][lo, hi), on the context's second stream (the counting worker owns the first).  Phase 1 (measure): lines,
     // structure checks, output size.  *valid: the device vouches for the chunk; *out_n: bytes of base stream it will give.
+    // *why: the reason bits of a chunk the device declines (SCB_*); *last_hdr (FASTA under a trim): the chunk's last line is a header.
     struct Measured { const uint8_t* src; uint64_t n, n_lines; uint32_t n_tiles; };
-    int scan_measure(int buf, uint64_t lo, uint64_t hi, bool* valid, uint64_t* out_n, Measured* ms) {
+    int scan_measure(int buf, uint64_t lo, uint64_t hi, bool* valid, uint64_t* out_n, Measured* ms, uint64_t* why, bool* last_hdr) {
         const hipStream_t st = c->copy_stream;
         const uint8_t* src = raw[buf] + lo;
         const uint64_t n = hi - lo;
-        *valid = false; *out_n = 0;
+        *valid = false; *out_n = 0; *why = 0; *last_hdr = after_hdr;
         ms->src = src; ms->n = n; ms->n_lines = 0; ms->n_tiles = 0;
         if (n == 0) { *valid = true; return KATGPU_OK; }
+        const bool marked = trim && type == SCAN_FASTA;           // the lines' offsets carry SC_TRIMMED in their top bit
+        if (marked && n >= SC_TRIMMED) return KATGPU_OK;          // (a 2 GiB chunk: KATGPU_SCAN_BATCH_MB far above its default -- the host's)
         if (reinterpret_cast<uintptr_t>(src) & 15) {
             HIPCHK(c, hipMemcpyAsync(raw_al, src, n, hipMemcpyDeviceToDevice, st));
             src = raw_al;
@@ -481,18 +492,23 @@ struct RawFeeder {
         HIPCHK(c, hipMemcpyAsync(h, flags, sizeof h, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         const uint64_t n_lines = h[SCF_LINES];
+        *why = h[SCF_BAD];
         if (h[SCF_BAD] || n_lines == 0 || n_lines > cap_lines || (type == SCAN_FASTQ && (n_lines & 3))) return KATGPU_OK;     // the host's
         const uint64_t n_ltiles = (n_lines + SC_BLOCK - 1) / SC_BLOCK;
         const int lgrid = (int)std::min<uint64_t>(n_ltiles, (uint64_t)c->n_cu * 16);
         hipLaunchKernelGGL(k_nl_write, dim3(grid), dim3(SC_BLOCK), 0, st, src, n, n_tiles, (const uint64_t*)tile_off, NL, cap_lines);
-        if (type == SCAN_FASTQ) hipLaunchKernelGGL(k_line_len<SCAN_FASTQ>, dim3(lgrid), dim3(SC_BLOCK), 0, st, src, (const uint32_t*)NL, n_lines, len_off, line_tile_sum, flags);
-        else hipLaunchKernelGGL(k_line_len<SCAN_FASTA>, dim3(lgrid), dim3(SC_BLOCK), 0, st, src, (const uint32_t*)NL, n_lines, len_off, line_tile_sum, flags);
+        {
+            auto* const kern = type == SCAN_FASTQ ? (trim ? k_line_len<SCAN_FASTQ, true> : k_line_len<SCAN_FASTQ, false>) : (trim ? k_line_len<SCAN_FASTA, true> : k_line_len<SCAN_FASTA, false>);
+            hipLaunchKernelGGL(kern, dim3(lgrid), dim3(SC_BLOCK), 0, st, src, (const uint32_t*)NL, n_lines, len_off, line_tile_sum, flags, trim, (uint32_t)after_hdr);
+        }
         hipLaunchKernelGGL(k_rows_scan, dim3(1), dim3(1024), 0, st, (const uint32_t*)line_tile_sum, (uint32_t)n_ltiles, (uint64_t)n_ltiles, (const uint64_t*)nullptr,
                            line_tile_off, (uint64_t)(n_ltiles + 1), 1, (unsigned long long*)&flags[SCF_OUT]);
         HIPCHK(c, hipMemcpyAsync(h, flags, sizeof h, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
+        *why = h[SCF_BAD];
         if (h[SCF_BAD] || h[SCF_OUT] > buf_bytes) return KATGPU_OK;
-        hipLaunchKernelGGL(k_line_off, dim3(lgrid), dim3(SC_BLOCK), 0, st, n_lines, len_off, (const uint64_t*)line_tile_off);
+        if (marked) *last_hdr = h[SCF_LAST_HDR] != 0;
+        hipLaunchKernelGGL(marked ? k_line_off<true> : k_line_off<false>, dim3(lgrid), dim3(SC_BLOCK), 0, st, n_lines, len_off, (const uint64_t*)line_tile_off);
         ms->src = src; ms->n_lines = n_lines; ms->n_tiles = n_tiles;
         *valid = true; *out_n = h[SCF_OUT];
         return KATGPU_OK;
@@ -502,10 +518,8 @@ struct RawFeeder {
         if (!ms.n_lines) return KATGPU_OK;
         const hipStream_t st = c->copy_stream;
         const int grid = (int)std::min<uint64_t>(ms.n_tiles, (uint64_t)c->n_cu * 16);
-        if (type == SCAN_FASTQ) hipLaunchKernelGGL(k_emit<SCAN_FASTQ>, dim3(grid), dim3(SC_BLOCK), 0, st, ms.src, ms.n, ms.n_tiles, (const uint64_t*)tile_off, (const uint32_t*)NL,
-                                                   (const uint32_t*)len_off, ms.n_lines, dst);
-        else hipLaunchKernelGGL(k_emit<SCAN_FASTA>, dim3(grid), dim3(SC_BLOCK), 0, st, ms.src, ms.n, ms.n_tiles, (const uint64_t*)tile_off, (const uint32_t*)NL,
-                                (const uint32_t*)len_off, ms.n_lines, dst);
+        auto* const kern = type == SCAN_FASTQ ? (trim ? k_emit<SCAN_FASTQ, true> : k_emit<SCAN_FASTQ, false>) : (trim ? k_emit<SCAN_FASTA, true> : k_emit<SCAN_FASTA, false>);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(SC_BLOCK), 0, st, ms.src, ms.n, ms.n_tiles, (const uint64_t*)tile_off, (const uint32_t*)NL, (const uint32_t*)len_off, ms.n_lines, dst, trim);
         HIPCHK(c, hipGetLastError());
         return KATGPU_OK;
     }
@@ -573,9 +587,9 @@ struct RawFeeder {
     int host_rest(uint64_t from, const uint8_t* carry, uint32_t carry_n) {
         kg::ParseState ps;
         ps.begin(type == SCAN_FASTQ ? '@' : '>');
-        uint8_t first = 0;
-        if (from < size && pread(fd, &first, 1, (off_t)from) != 1) return fail(c, KATGPU_ERR_IO, "read error on %s", path);
-        if (type == SCAN_FASTA && first != '>') ps.st = kg::ParseState::LOOP_CHECK;        // in the middle of a record's sequence lines
+        ps.trim5p = trim;
+        if (type == SCAN_FASTA && trim && from && after_hdr) ps.st = kg::ParseState::TRIM_SKIPNL;      // right behind a header line: the record's trim is still to come, whatever the byte
+        else if (type == SCAN_FASTA && from) ps.st = kg::ParseState::LOOP_CHECK;            // behind a record's line: a '>' here gives the 'N' between records and then its header line (HEADER, the state of a file's first byte, would lose the 'N')
         std::vector<uint8_t> rawb((size_t)16 << 20), outb;
         outb.reserve(rawb.size() + 64);
         outb.insert(outb.end(), carry, carry + carry_n);
@@ -664,8 +678,8 @@ struct RawFeeder {
             const bool follows = j > 0 && my_segs[j] == my_segs[j - 1] + 1;
             const bool plain = sg.state == 1 && (!follows || sg.lo == prev_hi) && my_segs[j] < g_test_strip_fail_at;
             if (!plain && sharded)
-                return fail(c, KATGPU_ERR_FASTQ, "%s: the bytes around offset %llu are not plain four-line FASTQ: such a file cannot be cut between GPUs -- run it on one", path,
-                            (unsigned long long)(my_segs[j] * (uint64_t)segment));
+                return fail(c, KATGPU_ERR_FASTQ, "%s: the bytes around offset %llu are not plain four-line FASTQ%s: such a file cannot be cut between GPUs -- run it on one", path,
+                            (unsigned long long)(my_segs[j] * (uint64_t)segment), trim ? " (or hold a read no longer than the 5' trim, or one with '+' right behind it)" : "");
             if (!plain) {
                 // not plain four-line FASTQ from here on (or no certain cut): what has been committed is counted, the rest of the file goes
                 // through the host state machine from the last proven record start
@@ -757,14 +771,16 @@ struct RawFeeder {
                     if (!nl) cut_ok = false; else cut_hi = (nominal - 1) + (uint64_t)(nl - edge_hi[buf].data()) + 1;
                 }
             } else if (size && (edge_hi[buf].empty() || edge_hi[buf].back() != '\n')) cut_ok = false;              // a last line without its newline: the host machine knows what to do
-            bool valid = false; uint64_t out_n = 0;
+            bool valid = false, last_hdr = after_hdr; uint64_t out_n = 0, why = 0;
             Measured msd{};
             t0 = now_ms();
             if (cut_ok && cut_lo <= cut_hi && b < g_test_scan_fail_at) {
-                rc = scan_measure(buf, cut_lo - lo, cut_hi - lo, &valid, &out_n, &msd);
+                rc = scan_measure(buf, cut_lo - lo, cut_hi - lo, &valid, &out_n, &msd, &why, &last_hdr);
                 if (rc) return rc;
             }
             ms_scan += now_ms() - t0;
+            if (!valid && sharded && (why & SCB_TRIM))
+                return fail(c, KATGPU_ERR_FASTQ, "%s: batch %llu holds a read no longer than the 5' trim of %u, or one with '+' right behind the trim: such a file cannot be cut between GPUs -- run it on one", path, (unsigned long long)b, trim);
             if (!valid && sharded)
                 return fail(c, KATGPU_ERR_FASTQ, "%s: batch %llu is not plain four-line FASTQ (or holds a '\\r'): such a file cannot be cut between GPUs -- run it on one", path, (unsigned long long)b);
             if (!valid) {
@@ -795,7 +811,7 @@ struct RawFeeder {
             acc_fill += out_n;
             HIPCHK(c, hipStreamSynchronize(c->copy_stream));      // the scan's kernels are through with raw[buf]
             ms_scan += now_ms() - t0;
-            cut_lo = cut_hi;
+            cut_lo = cut_hi; after_hdr = last_hdr;
             batch_consumed();                                     // raw[buf] may take my batch after next
         }
         const double t0 = now_ms();
@@ -827,7 +843,7 @@ int count_file_device_scan(katgpu_table* t, const char* path, uint32_t trim5p, b
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b < ((size_t)6 << 30)) release_arena(c);    // the cached arena holds most of the free HBM: the batch buffers come first
     }
-    RawFeeder f(t, path);
+    RawFeeder f(t, path, trim5p);
     if (world > 1 && first != '@') return KATGPU_OK;              // only FASTQ is cut between ranks (the caller deals whole files otherwise)
     int rc = f.setup(size, first, rank, world);
     if (rc == KATGPU_ERR_NOMEM) { (void)hipGetLastError(); return KATGPU_OK; }      // no room for the batch buffers: the streaming path and its smaller rings
