@@ -354,6 +354,49 @@ int comm_agree_done(katgpu_comm* m, int rc, const char* rank_failed_fmt) {
     return KATGPU_OK;
 }
 
+std::function<int(int who, int code)> gathered_peer_error(katgpu_comm* m, katgpu_ctx* c, const char* name, const char* room_fmt, size_t room) {
+    return [=](int p, int code) {
+        if (code != KATGPU_ERR_NOMEM) return fail(c, code, "%s: rank %d could not read its table", name, p);
+        return fail(c, code, (std::string("%s: rank %d of %d has no device memory for ") + room_fmt).c_str(), name, p, m->world, room);
+    };
+}
+
+// ---- the same call on every rank (kg_comm.hpp) ----
+// every start and length, in order, folded into one word
+static uint64_t records_checksum(const CallRecords& recs) {
+    uint64_t h = 0x9E3779B97F4A7C15ULL;
+    auto fold = [&](uint64_t x) { h ^= x; h *= 0xFF51AFD7ED558CCDULL; h ^= h >> 32; };
+    for (size_t r = 0; r < recs.n; ++r) { fold(recs.start[r]); fold(recs.len[r]); }
+    return h;
+}
+
+int comm_agree_on_call(katgpu_comm* m, katgpu_ctx* c, const char* name, size_t n, uint32_t k, const CallRecords* recs, bool unusable, const char* unusable_what,
+                       const CallWords* extra) {
+    enum { N, K, N_REC, CHECKSUM, UNUSABLE, EXTRA };                // a rank's words
+    typedef unsigned long long ull;
+    const size_t n_extra = extra ? extra->n : 0, W = EXTRA + n_extra;
+    std::vector<uint64_t> mine(W, 0), all((size_t)m->world * W, 0);
+    mine[N] = n; mine[K] = k; mine[N_REC] = recs ? recs->n : 0; mine[UNUSABLE] = unusable;
+    if (recs && !unusable) mine[CHECKSUM] = records_checksum(*recs);
+    for (size_t i = 0; i < n_extra; ++i) mine[EXTRA + i] = extra->words[i];
+    const int crc = allgather_u64(m, mine.data(), W, all.data());
+    if (crc) return crc;
+    const uint64_t* r0 = all.data();
+    for (int p = 0; p < m->world; ++p)
+        if (all[(size_t)p * W + UNUSABLE]) return fail(c, KATGPU_ERR_INVALID_ARG, "%s: rank %d %s", name, p, unusable_what);
+    for (int p = 0; p < m->world; ++p) {
+        const uint64_t* a = &all[(size_t)p * W];
+        if (a[N] != r0[N] || a[N_REC] != r0[N_REC] || a[K] != r0[K]) {
+            if (recs) return fail(c, KATGPU_ERR_INVALID_ARG, "%s: the ranks disagree: rank 0 has %llu bases in %llu records at k = %llu, rank %d %llu in %llu at k = %llu", name,
+                                  (ull)r0[N], (ull)r0[N_REC], (ull)r0[K], p, (ull)a[N], (ull)a[N_REC], (ull)a[K]);
+            return fail(c, KATGPU_ERR_INVALID_ARG, "%s: the ranks disagree: rank 0 has %llu bases at k = %llu, rank %d %llu at k = %llu", name, (ull)r0[N], (ull)r0[K], p, (ull)a[N], (ull)a[K]);
+        }
+        if (a[CHECKSUM] != r0[CHECKSUM]) return fail(c, KATGPU_ERR_INVALID_ARG, "%s: the ranks disagree: rank %d's %llu records are not where rank 0's are", name, p, (ull)a[N_REC]);
+        if (n_extra && memcmp(a + EXTRA, r0 + EXTRA, n_extra * sizeof(uint64_t))) return fail(c, KATGPU_ERR_INVALID_ARG, "%s: the ranks disagree: rank %d's %s", name, p, extra->differ);
+    }
+    return KATGPU_OK;
+}
+
 // ------------------------------------------------------------------ the communicator ------------------
 
 extern "C" int katgpu_comm_unique_id(void* id_out) {

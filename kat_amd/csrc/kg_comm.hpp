@@ -1,5 +1,7 @@
 // kg_comm.hpp -- the communicator as the units that speak through it see it: kg_comm.hip (the transports, liveness, the small
-// collectives), kg_comm_exchange.hip (the exchange protocol), and the gathered paths, kg_jf_device.hip and kg_query.hip.
+// collectives), kg_comm_exchange.hip (the exchange protocol), and the gathered paths, kg_jf_device.hip, kg_query.hip and kg_per_record.hip.
+// What a gathered call's ranks settle among themselves is here once: that they were given the same call (comm_agree_on_call), that all
+// of them can start (comm_agree_to_start, with gathered_peer_error's words for a peer that cannot) and how it ended (comm_agree_done).
 // Nobody else includes it: the rest of the library and its callers know katgpu_comm as the opaque handle of include/katgpu.h.
 #pragma once
 #include "kg_host.hpp"
@@ -65,13 +67,23 @@ int comm_agree_to_start(katgpu_comm* m, int rc, const std::function<int(int who,
 // or KATGPU_ERR_DEVICE with rank_failed_fmt (one %d: the rank).
 int comm_agree_done(katgpu_comm* m, int rc, const char* rank_failed_fmt);
 
-// what the ranks of a gathered per-record call compare of their records: every start and length, in order, folded into one word
-inline uint64_t records_checksum(const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec) {
-    uint64_t h = 0x9E3779B97F4A7C15ULL;
-    auto fold = [&](uint64_t x) { h ^= x; h *= 0xFF51AFD7ED558CCDULL; h ^= h >> 32; };
-    for (size_t r = 0; r < n_rec; ++r) { fold(rec_start[r]); fold(rec_len[r]); }
-    return h;
-}
+// comm_agree_to_start's peer_error of a gathered call, into c: "<name>: rank p of w has no device memory for <room>", room_fmt being the
+// call's words for what a rank found no room for, with one %zu (room) -- "a batch of %zu bases" --, or "<name>: rank p could not read its table".
+std::function<int(int who, int code)> gathered_peer_error(katgpu_comm* m, katgpu_ctx* c, const char* name, const char* room_fmt, size_t room);
+
+// ---- the same call on every rank (kg_comm.hip) ----
+// A gathered call cuts its batches from its arguments, and a rank that cut them differently would wait in a collective of a batch that its
+// peers do not have, until the liveness timeout.  So, before anything else, one allgather_u64 of every rank's
+//   n | k | n_rec | a checksum of the records' starts and lengths | "my arguments are unusable" | the call's extra words
+// and the same verdict on every rank: KATGPU_OK, or KATGPU_ERR_INVALID_ARG with the text in c, `name` in front, for the first of
+//   1. a rank whose arguments are unusable (the lowest such rank; unusable_what says of what: "was given no bases, or rank 0 no room for ...");
+//   then, rank by rank against rank 0:
+//   2. another n, n_rec or k;  3. records that are not where rank 0's are;  4. other extra words (extra->differ: "count ranges are not rank 0's").
+// recs: the records of a per-record call, null for a call that has none.  Their checksum is taken only where the arguments are usable.
+struct CallRecords { const uint64_t *start, *len; size_t n; };
+struct CallWords { const uint64_t* words; size_t n; const char* differ; };
+int comm_agree_on_call(katgpu_comm* m, katgpu_ctx* c, const char* name, size_t n, uint32_t k, const CallRecords* recs, bool unusable, const char* unusable_what,
+                       const CallWords* extra = nullptr);
 
 // ---- the gather of a profile from the ranks' tables (kg_query.hip), for the collectives built on it: katgpu_table_profile_gathered_host
 // there, katgpu_table_record_stats_gathered_host in kg_per_record.hip.  One object per collective call; its counters add up over gather(). ----
@@ -89,4 +101,3 @@ struct ProfileGather {
     int gather(const char* bases, const uint8_t* dev_bases, size_t n, uint64_t* counts, uint64_t* dev_counts);
     void print_timing() const;                    // rank 0, under KATGPU_TIMING: the "profile_gathered" line of the call
 };
-int gather_peer_error(katgpu_comm* comm, const ProfileGather& g, int p, int code);      // comm_agree_to_start's peer_error for prepare()

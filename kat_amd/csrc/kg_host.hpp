@@ -20,10 +20,14 @@
 // (k_sweep), kg_partition.hpp and what that includes, kg_partition_wide.hpp; kg_scan.hip kg_scan.hpp; kg_exchange.hip kg_exchange_kernels.hpp;
 // kg_reduce.hip kg_reduce_kernels.hpp.  Shared: kg_kernels.hpp (the chunk geometry and the direct counter k_count) and kg_rows_scan.hpp
 // (kg_scan.hip, kg_exchange.hip).  tests/test_kernel_units.py holds every unit to it.
+// What the per-record calls of kg_query.hip and kg_per_record.hip share is below ("what the entry points share"): records_usable (the
+// pointer check of every entry), check_records, for_record_batches -- whose batches end where kg_record_batches.hpp says (plain C++, no
+// HIP: record_batch_at, and record_batches_max_bases for whoever sizes buffers by the cut before the walk).
 // gfx950 only; there is no CPU path in this library.
 #pragma once
 #include "../../include/katgpu.h"
 #include "kg_device.hpp"
+#include "kg_record_batches.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -316,6 +320,12 @@ void launch_wide(bool wide, F&& f) {
     else f(std::false_type{});
 }
 
+// what every per-record entry point asks of its records and bases: a pointer wherever there is something behind it (the device forms:
+// device pointers).  What else a call needs -- room for its results -- it checks itself.
+inline bool records_usable(const void* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec) {
+    return !(n_rec && (!rec_start || !rec_len)) && !(n && !bases);
+}
+
 // records of a host form: inside the n bases, in order and disjoint
 inline int check_records(katgpu_ctx* c, const uint64_t* rec_start, const uint64_t* rec_len, size_t n_rec, size_t n) {
     for (size_t r = 0; r < n_rec; ++r) {
@@ -327,7 +337,8 @@ inline int check_records(katgpu_ctx* c, const uint64_t* rec_start, const uint64_
 
 // The records of a host form through the device in batches [r0, r1) of at most max_bases bases and max_recs records (a record longer than that is a
 // batch of its own); joins(r, first) may end a batch earlier: it is asked once per record, in order, after the two limits (a batch's first record joins
-// whatever it says).  The records of a batch have a pooled buffer of max_recs x (2 + extra_words) words: start | length | the body's own.  Per batch
+// whatever it says).  Where a batch ends is kg_record_batches.hpp's to say (record_batch_at), for this walk and for whoever sizes buffers by the
+// batches beforehand (record_batches_max_bases).  The records of a batch have a pooled buffer of max_recs x (2 + extra_words) words: start | length | the body's own.  Per batch
 // the bases from its first record's start to its last one's end, the starts (counted from there) and the lengths go up,
 // body(dev_bases, nb, dev_start, dev_len, m, r0, dev_extra) queues its work -- dev_extra: the words behind start and length -- and the stream is waited for.
 // what_nomem != null: no device memory for the records or for a batch of bases is KATGPU_ERR_NOMEM, worded in its name; null: whatever HIP said, in `what`'s.
@@ -342,17 +353,14 @@ int for_record_batches(katgpu_ctx* c, const char* bases, size_t n, const uint64_
     std::vector<uint64_t> st(max_recs), ln(max_recs);
     int rc = KATGPU_OK;
     for (size_t r0 = 0; r0 < n_rec && !rc && e == hipSuccess;) {
-        const uint64_t base = rec_start[r0];
-        size_t r1 = r0;
-        joins(r1++, true);
-        while (r1 < n_rec && r1 - r0 < max_recs && rec_start[r1] + rec_len[r1] - base <= max_bases && joins(r1, false)) ++r1;
-        const size_t nb = rec_start[r1 - 1] + rec_len[r1 - 1] - base, m = r1 - r0;
+        const RecordBatch b = record_batch_at(rec_start, rec_len, n_rec, max_bases, max_recs, joins, r0);
+        const size_t r1 = b.r1, nb = b.nb, m = r1 - r0;
         if (nb + 64 > db.cap) {
             e = db.fit(c, std::max(nb + 64, std::min(max_bases, n) + 64));
             if (e != hipSuccess) { if (what_nomem) rc = fail(c, KATGPU_ERR_NOMEM, "%s: no %zu bytes of device memory for a batch of bases", what_nomem, nb + 64); break; }
         }
-        for (size_t r = r0; r < r1; ++r) { st[r - r0] = rec_start[r] - base; ln[r - r0] = rec_len[r]; }
-        if (nb) e = hipMemcpyAsync(db.p, bases + base, nb, hipMemcpyHostToDevice, c->stream);
+        for (size_t r = r0; r < r1; ++r) { st[r - r0] = rec_start[r] - b.base; ln[r - r0] = rec_len[r]; }
+        if (nb) e = hipMemcpyAsync(db.p, bases + b.base, nb, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dev_start, st.data(), m * 8, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(dev_len, ln.data(), m * 8, hipMemcpyHostToDevice, c->stream);
         if (e != hipSuccess) break;

@@ -98,7 +98,7 @@ static int record_stats_device(katgpu_ctx* c, const Src& src, uint32_t k, bool w
 // Device form (refresh_counters has synchronised already; the two words are two of the table's counters).
 extern "C" int katgpu_table_record_stats_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
                                                 const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, katgpu_record_stats* dev_out) {
-    if (!t || (n_rec && (!dev_rec_start || !dev_rec_len || !dev_out)) || (n && !dev_bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!t || !records_usable(dev_bases, n, dev_rec_start, dev_rec_len, n_rec) || (n_rec && !dev_out)) return KATGPU_ERR_INVALID_ARG;
     if (!n_rec) return KATGPU_OK;
     katgpu_ctx* c = t->ctx;
     HIPCHK(c, hipSetDevice(c->device));
@@ -110,7 +110,7 @@ extern "C" int katgpu_table_record_stats_device(katgpu_table* t, const uint8_t* 
 // The same from a dense array of counts: no table, so a context and k, as katgpu_record_gc_text_device takes them.
 extern "C" int katgpu_record_stats_from_counts_device(katgpu_ctx* c, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_counts,
                                                       const uint64_t* dev_rec_start, const uint64_t* dev_rec_len, size_t n_rec, katgpu_record_stats* dev_out) {
-    if (!c || (n_rec && (!dev_rec_start || !dev_rec_len || !dev_out)) || (n && !dev_bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!c || !records_usable(dev_bases, n, dev_rec_start, dev_rec_len, n_rec) || (n_rec && !dev_out)) return KATGPU_ERR_INVALID_ARG;
     int rc = counts_check(c, "record stats from counts", k, dev_counts); if (rc) return rc;
     if (n >= k && !dev_counts) return KATGPU_ERR_INVALID_ARG;
     if (!n_rec) return KATGPU_OK;
@@ -141,7 +141,7 @@ struct StatsJoins {
 // What comes back is sizeof(katgpu_record_stats) per record.
 extern "C" int katgpu_table_record_stats_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
                                               size_t n_rec, int canonicalise, katgpu_record_stats* out) {
-    if (!t || (n_rec && (!rec_start || !rec_len || !out)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!t || !records_usable(bases, n, rec_start, rec_len, n_rec) || (n_rec && !out)) return KATGPU_ERR_INVALID_ARG;
     if (!n_rec) return KATGPU_OK;
     katgpu_ctx* c = t->ctx;
     int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;
@@ -234,7 +234,7 @@ extern "C" int katgpu_table_record_regions_device(katgpu_table* t, const uint8_t
                                                   const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, const katgpu_count_range* ranges,
                                                   uint32_t n_ranges, katgpu_region* dev_regions, size_t cap, size_t n_out[]) {
     RgRanges rg;
-    if (!t || !n_out || (n_rec && (!dev_rec_start || !dev_rec_len)) || (n && !dev_bases) || (cap && !dev_regions)) return KATGPU_ERR_INVALID_ARG;
+    if (!t || !n_out || !records_usable(dev_bases, n, dev_rec_start, dev_rec_len, n_rec) || (cap && !dev_regions)) return KATGPU_ERR_INVALID_ARG;
     katgpu_ctx* c = t->ctx;
     if (!regions_args(ranges, n_ranges, rg)) return fail(c, KATGPU_ERR_INVALID_ARG, "record regions: one or two count ranges, not %u", ranges ? n_ranges : 0);
     for (uint32_t q = 0; q < n_ranges; ++q) n_out[q] = 0;
@@ -249,7 +249,7 @@ extern "C" int katgpu_record_regions_from_counts_device(katgpu_ctx* c, uint32_t 
                                                         const uint64_t* dev_rec_start, const uint64_t* dev_rec_len, size_t n_rec,
                                                         const katgpu_count_range* ranges, uint32_t n_ranges, katgpu_region* dev_regions, size_t cap, size_t n_out[]) {
     RgRanges rg;
-    if (!c || !n_out || (n_rec && (!dev_rec_start || !dev_rec_len)) || (n && !dev_bases) || (cap && !dev_regions)) return KATGPU_ERR_INVALID_ARG;
+    if (!c || !n_out || !records_usable(dev_bases, n, dev_rec_start, dev_rec_len, n_rec) || (cap && !dev_regions)) return KATGPU_ERR_INVALID_ARG;
     int rc = counts_check(c, "record regions from counts", k, dev_counts); if (rc) return rc;
     if (n >= k && !dev_counts) return KATGPU_ERR_INVALID_ARG;
     if (!regions_args(ranges, n_ranges, rg)) return fail(c, KATGPU_ERR_INVALID_ARG, "record regions: one or two count ranges, not %u", ranges ? n_ranges : 0);
@@ -305,7 +305,7 @@ extern "C" int katgpu_table_record_regions_host(katgpu_table* t, const char* bas
                                                 size_t n_rec, int canonicalise, const katgpu_count_range* ranges, uint32_t n_ranges,
                                                 katgpu_region** regions, size_t n_out[]) {
     RgRanges rg;
-    if (!t || !regions || !n_out || (n_rec && (!rec_start || !rec_len)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!t || !regions || !n_out || !records_usable(bases, n, rec_start, rec_len, n_rec)) return KATGPU_ERR_INVALID_ARG;
     katgpu_ctx* c = t->ctx;
     if (!regions_args(ranges, n_ranges, rg)) return fail(c, KATGPU_ERR_INVALID_ARG, "record regions: one or two count ranges, not %u", ranges ? n_ranges : 0);
     *regions = nullptr;
@@ -348,43 +348,21 @@ extern "C" int katgpu_table_record_stats_gathered_host(katgpu_comm* comm, katgpu
     const uint32_t k = t->dv.k;
     RgRanges rg{{0, 0}, {0, 0}, 0};
     // ---- the same records and ranges, one k and usable pointers everywhere, before anything else: all ranks go on, or none does ----
-    {
-        const bool unusable = (n && !bases) || (n_rec && (!rec_start || !rec_len)) || n_ranges > RG_MAX_RANGES || (n_ranges && !ranges) ||
-                              (rank == 0 && ((n_rec && !stats) || (n_ranges && (!regions || !n_out))));
-        uint64_t mine[10] = {(uint64_t)n, (uint64_t)n_rec, k, unusable ? 0 : records_checksum(rec_start, rec_len, n_rec), (uint64_t)unusable, n_ranges, 0, 0, 0, 0};
-        if (!unusable) { regions_args(ranges, n_ranges, rg); for (uint32_t q = 0; q < n_ranges; ++q) { mine[6 + 2 * q] = rg.min[q]; mine[7 + 2 * q] = rg.max[q]; } }
-        std::vector<uint64_t> all((size_t)world * 10, 0);
-        const int crc = allgather_u64(comm, mine, 10, all.data());
-        if (crc) return crc;
-        for (int p = 0; p < world; ++p)
-            if (all[(size_t)p * 10 + 4]) return fail(c, KATGPU_ERR_INVALID_ARG, "record stats gathered: rank %d was given no bases, no records or more than two ranges, or rank 0 no room for the results", p);
-        for (int p = 0; p < world; ++p) {
-            const uint64_t* a = &all[(size_t)p * 10];
-            if (a[0] != all[0] || a[1] != all[1] || a[2] != all[2])
-                return fail(c, KATGPU_ERR_INVALID_ARG, "record stats gathered: the ranks disagree: rank 0 has %llu bases in %llu records at k = %llu, rank %d %llu in %llu at k = %llu",
-                            (unsigned long long)all[0], (unsigned long long)all[1], (unsigned long long)all[2], p, (unsigned long long)a[0], (unsigned long long)a[1], (unsigned long long)a[2]);
-            if (a[3] != all[3]) return fail(c, KATGPU_ERR_INVALID_ARG, "record stats gathered: the ranks disagree: rank %d's %llu records are not where rank 0's are", p, (unsigned long long)a[1]);
-            if (memcmp(a + 5, &all[5], 5 * sizeof(uint64_t))) return fail(c, KATGPU_ERR_INVALID_ARG, "record stats gathered: the ranks disagree: rank %d's count ranges are not rank 0's", p);
-        }
-    }
+    const bool unusable = !records_usable(bases, n, rec_start, rec_len, n_rec) || n_ranges > RG_MAX_RANGES || (n_ranges && !ranges) ||
+                          (rank == 0 && ((n_rec && !stats) || (n_ranges && (!regions || !n_out))));
+    uint64_t range_words[1 + 2 * RG_MAX_RANGES] = {n_ranges, 0, 0, 0, 0};          // n_ranges | min and max of every range
+    if (!unusable) { regions_args(ranges, n_ranges, rg); for (uint32_t q = 0; q < n_ranges; ++q) { range_words[1 + 2 * q] = rg.min[q]; range_words[2 + 2 * q] = rg.max[q]; } }
+    const CallRecords recs{rec_start, rec_len, n_rec};
+    const CallWords range_call{range_words, 1 + 2 * RG_MAX_RANGES, "count ranges are not rank 0's"};
+    int rc = comm_agree_on_call(comm, c, "record stats gathered", n, k, &recs, unusable, "was given no bases, no records or more than two ranges, or rank 0 no room for the results", &range_call);
+    if (rc) return rc;
     if (rank == 0 && n_ranges) { *regions = nullptr; for (uint32_t q = 0; q < n_ranges; ++q) n_out[q] = 0; }
     std::vector<katgpu_region> found[RG_MAX_RANGES];
     if (!n_rec) return rank == 0 && n_ranges ? regions_result(c, found, n_ranges, regions, n_out) : KATGPU_OK;
-    int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;      // (the same records everywhere: the same answer)
-    // ---- the batches as they will be cut: the most bases of one, and whether any reaches k bases ----
+    rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;          // (the same records everywhere: the same answer)
+    // ---- the batches as they will be cut (a StatsJoins of their own): the most bases of one, and whether any reaches k bases ----
     const size_t cap = std::min(n_rec, STATS_RECS);
-    size_t max_nb = 0;
-    {
-        StatsJoins joins{rec_len, k};
-        for (size_t r0 = 0; r0 < n_rec;) {                         // (for_record_batches' cut)
-            const uint64_t base = rec_start[r0];
-            size_t r1 = r0;
-            joins(r1++, true);
-            while (r1 < n_rec && r1 - r0 < cap && rec_start[r1] + rec_len[r1] - base <= g_stats_batch && joins(r1, false)) ++r1;
-            max_nb = std::max<size_t>(max_nb, rec_start[r1 - 1] + rec_len[r1 - 1] - base);
-            r0 = r1;
-        }
-    }
+    const size_t max_nb = record_batches_max_bases(rec_start, rec_len, n_rec, g_stats_batch, cap, StatsJoins{rec_len, k});
     const bool gathers = max_nb >= k;
     ProfileGather g{comm, t, canonicalise};
     DevBuf dense;                                                  // rank 0: the counts of a record batch's window starts
@@ -397,10 +375,7 @@ extern "C" int katgpu_table_record_stats_gathered_host(katgpu_comm* comm, katgpu
         }
         return KATGPU_OK;
     };
-    rc = comm_agree_to_start(comm, prepare(), [&](int p, int code) {
-        if (code == KATGPU_ERR_NOMEM) return fail(c, code, "record stats gathered: rank %d of %d has no device memory for a batch of %zu bases", p, world, max_nb);
-        return fail(c, code, "record stats gathered: rank %d could not read its table", p);
-    });
+    rc = comm_agree_to_start(comm, prepare(), gathered_peer_error(comm, c, "record stats gathered", "a batch of %zu bases", max_nb));
     if (rc) return rc;
 
     // ---- the batches.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end (comm_agree_done) ----
@@ -642,21 +617,21 @@ static int record_text_host(katgpu_ctx* c, const Src& src, size_t max_bases, con
 extern "C" int katgpu_table_record_cvg_text_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
                                                    const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, uint8_t* dev_text, size_t cap,
                                                    uint64_t* dev_text_off, uint64_t* total) {
-    if (!t || !total || !dev_text_off || (n_rec && (!dev_rec_start || !dev_rec_len)) || (n && !dev_bases) || (cap && !dev_text)) return KATGPU_ERR_INVALID_ARG;
+    if (!t || !total || !dev_text_off || !records_usable(dev_bases, n, dev_rec_start, dev_rec_len, n_rec) || (cap && !dev_text)) return KATGPU_ERR_INVALID_ARG;
     *total = 0;
     return record_text_device(t->ctx, CvgText{t, canonicalise}, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, dev_text, cap, dev_text_off, total);
 }
 
 extern "C" int katgpu_table_record_cvg_text_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
                                                  size_t n_rec, int canonicalise, char** text, uint64_t* text_off) {
-    if (!t || !text || !text_off || (n_rec && (!rec_start || !rec_len)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!t || !text || !text_off || !records_usable(bases, n, rec_start, rec_len, n_rec)) return KATGPU_ERR_INVALID_ARG;
     *text = nullptr;
     return record_text_host(t->ctx, CvgText{t, canonicalise}, g_cvg_batch, bases, n, rec_start, rec_len, n_rec, text, text_off);
 }
 
 extern "C" int katgpu_record_gc_text_device(katgpu_ctx* c, uint32_t k, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
                                             const uint64_t* dev_rec_len, size_t n_rec, uint8_t* dev_text, size_t cap, uint64_t* dev_text_off, uint64_t* total) {
-    if (!c || !total || !dev_text_off || (n_rec && (!dev_rec_start || !dev_rec_len)) || (n && !dev_bases) || (cap && !dev_text)) return KATGPU_ERR_INVALID_ARG;
+    if (!c || !total || !dev_text_off || !records_usable(dev_bases, n, dev_rec_start, dev_rec_len, n_rec) || (cap && !dev_text)) return KATGPU_ERR_INVALID_ARG;
     *total = 0;
     int rc = gc_check_k(c, k); if (rc) return rc;
     return record_text_device(c, GcText{c, k, gc_strings(k)}, dev_bases, n, dev_rec_start, dev_rec_len, n_rec, dev_text, cap, dev_text_off, total);
@@ -664,7 +639,7 @@ extern "C" int katgpu_record_gc_text_device(katgpu_ctx* c, uint32_t k, const uin
 
 extern "C" int katgpu_record_gc_text_host(katgpu_ctx* c, uint32_t k, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
                                           size_t n_rec, char** text, uint64_t* text_off) {
-    if (!c || !text || !text_off || (n_rec && (!rec_start || !rec_len)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!c || !text || !text_off || !records_usable(bases, n, rec_start, rec_len, n_rec)) return KATGPU_ERR_INVALID_ARG;
     *text = nullptr;
     int rc = gc_check_k(c, k); if (rc) return rc;
     return record_text_host(c, GcText{c, k, gc_strings(k)}, g_gc_batch, bases, n, rec_start, rec_len, n_rec, text, text_off);

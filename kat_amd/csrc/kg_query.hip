@@ -189,12 +189,6 @@ void ProfileGather::print_timing() const {
                 (unsigned long long)n_batches, katgpu_comm_world(comm), (unsigned long long)records, (unsigned long long)wire_bytes);
 }
 
-int gather_peer_error(katgpu_comm* comm, const ProfileGather& g, int p, int code) {
-    katgpu_ctx* c = g.t->ctx;
-    if (code == KATGPU_ERR_NOMEM) return fail(c, code, "profile gathered: rank %d of %d has no device memory for a batch of %zu window starts", p, katgpu_comm_world(comm), g.batch);
-    return fail(c, code, "profile gathered: rank %d could not read its table", p);
-}
-
 // Collective, after katgpu_exchange_merge: the gather above over the whole sequence (each batch re-sends the k-1 bases it shares with the
 // next one, as katgpu_table_profile_host does), the dense counts of every batch to `counts` on rank 0.
 // From the pool, per window start of a batch: 12 bytes of run on every rank and 8 of dense counts on rank 0, beside the batch's bases.
@@ -202,25 +196,16 @@ extern "C" int katgpu_table_profile_gathered_host(katgpu_comm* comm, katgpu_tabl
     if (!comm || !t) return KATGPU_ERR_INVALID_ARG;
     katgpu_ctx* c = t->ctx;
     if (g_forbid_profile_gathered) return fail(c, KATGPU_ERR_INVALID_ARG, "katgpu_table_profile_gathered_host is forbidden (KATGPU_TEST_FORBID_PROFILE_GATHERED)");
-    const int rank = katgpu_comm_rank(comm), world = katgpu_comm_world(comm);
+    const int rank = katgpu_comm_rank(comm);
     const uint32_t k = t->dv.k;
     // ---- one sequence length, one k and usable pointers everywhere, before anything else: all ranks go on, or none does ----
-    {
-        const uint64_t mine[3] = {(uint64_t)n, k, (uint64_t)((n && !bases) || (rank == 0 && n >= k && !counts))};
-        std::vector<uint64_t> all((size_t)world * 3, 0);
-        const int crc = allgather_u64(comm, mine, 3, all.data());
-        if (crc) return crc;
-        for (int p = 0; p < world; ++p) {
-            if (all[(size_t)p * 3] != all[0] || all[(size_t)p * 3 + 1] != all[1])
-                return fail(c, KATGPU_ERR_INVALID_ARG, "profile gathered: the ranks disagree: rank 0 has %llu bases at k = %llu, rank %d %llu at k = %llu",
-                            (unsigned long long)all[0], (unsigned long long)all[1], p, (unsigned long long)all[(size_t)p * 3], (unsigned long long)all[(size_t)p * 3 + 1]);
-            if (all[(size_t)p * 3 + 2]) return fail(c, KATGPU_ERR_INVALID_ARG, "profile gathered: rank %d was given no bases, or rank 0 no room for the counts", p);
-        }
-    }
+    int rc = comm_agree_on_call(comm, c, "profile gathered", n, k, nullptr, (n && !bases) || (rank == 0 && n >= k && !counts), "was given no bases, or rank 0 no room for the counts");
+    if (rc) return rc;
     if (n < k) return KATGPU_OK;
     // ---- everything a batch needs: the run's counts | its indices | its length, the dense array on rank 0 ----
     ProfileGather g{comm, t, canonicalise};
-    int rc = comm_agree_to_start(comm, g.prepare(n - k + 1, true, true), [&](int p, int code) { return gather_peer_error(comm, g, p, code); });
+    rc = g.prepare(n - k + 1, true, true);
+    rc = comm_agree_to_start(comm, rc, gathered_peer_error(comm, c, "profile gathered", "a batch of %zu window starts", g.batch));
     if (rc) return rc;
     // ---- the batches.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end (comm_agree_done) ----
     rc = comm_agree_done(comm, g.gather(bases, nullptr, n, counts, nullptr), "profile gathered: rank %d failed");
@@ -248,7 +233,7 @@ static int launch_seq_hits(katgpu_table* t, const uint8_t* dev_bases, size_t n, 
 
 extern "C" int katgpu_table_seq_hits_device(katgpu_table* t, const uint8_t* dev_bases, size_t n, const uint64_t* dev_rec_start,
                                             const uint64_t* dev_rec_len, size_t n_rec, int canonicalise, uint64_t* dev_hits) {
-    if (!t || (n_rec && (!dev_rec_start || !dev_rec_len || !dev_hits)) || (n && !dev_bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!t || !records_usable(dev_bases, n, dev_rec_start, dev_rec_len, n_rec) || (n_rec && !dev_hits)) return KATGPU_ERR_INVALID_ARG;
     if (!n_rec) return KATGPU_OK;
     katgpu_ctx* c = t->ctx;
     HIPCHK(c, hipSetDevice(c->device));
@@ -260,7 +245,7 @@ extern "C" int katgpu_table_seq_hits_device(katgpu_table* t, const uint8_t* dev_
 // so any input fits next to the table.
 extern "C" int katgpu_table_seq_hits_host(katgpu_table* t, const char* bases, size_t n, const uint64_t* rec_start, const uint64_t* rec_len,
                                           size_t n_rec, int canonicalise, uint64_t* hits) {
-    if (!t || (n_rec && (!rec_start || !rec_len || !hits)) || (n && !bases)) return KATGPU_ERR_INVALID_ARG;
+    if (!t || !records_usable(bases, n, rec_start, rec_len, n_rec) || (n_rec && !hits)) return KATGPU_ERR_INVALID_ARG;
     if (!n_rec) return KATGPU_OK;
     katgpu_ctx* c = t->ctx;
     int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;
@@ -295,24 +280,12 @@ extern "C" int katgpu_table_seq_hits_gathered_host(katgpu_comm* comm, katgpu_tab
     const uint32_t k = t->dv.k;
     const bool wide = t->dv.keys_b != nullptr;
     // ---- the same records, one k and usable pointers everywhere, before anything else: all ranks go on, or none does ----
-    {
-        const bool unusable = (n && !bases) || (n_rec && (!rec_start || !rec_len)) || (rank == 0 && n_rec && !hits);
-        const uint64_t mine[5] = {(uint64_t)n, (uint64_t)n_rec, k, unusable ? 0 : records_checksum(rec_start, rec_len, n_rec), (uint64_t)unusable};
-        std::vector<uint64_t> all((size_t)world * 5, 0);
-        const int crc = allgather_u64(comm, mine, 5, all.data());
-        if (crc) return crc;
-        for (int p = 0; p < world; ++p)
-            if (all[(size_t)p * 5 + 4]) return fail(c, KATGPU_ERR_INVALID_ARG, "seq hits gathered: rank %d was given no bases or no records, or rank 0 no room for the hits", p);
-        for (int p = 0; p < world; ++p) {
-            const uint64_t* a = &all[(size_t)p * 5];
-            if (a[0] != all[0] || a[1] != all[1] || a[2] != all[2])
-                return fail(c, KATGPU_ERR_INVALID_ARG, "seq hits gathered: the ranks disagree: rank 0 has %llu bases in %llu records at k = %llu, rank %d %llu in %llu at k = %llu",
-                            (unsigned long long)all[0], (unsigned long long)all[1], (unsigned long long)all[2], p, (unsigned long long)a[0], (unsigned long long)a[1], (unsigned long long)a[2]);
-            if (a[3] != all[3]) return fail(c, KATGPU_ERR_INVALID_ARG, "seq hits gathered: the ranks disagree: rank %d's %llu records are not where rank 0's are", p, (unsigned long long)a[1]);
-        }
-    }
+    const CallRecords recs{rec_start, rec_len, n_rec};
+    int rc = comm_agree_on_call(comm, c, "seq hits gathered", n, k, &recs, !records_usable(bases, n, rec_start, rec_len, n_rec) || (rank == 0 && n_rec && !hits),
+                                "was given no bases or no records, or rank 0 no room for the hits");
+    if (rc) return rc;
     if (!n_rec) return KATGPU_OK;
-    int rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;      // (the same records everywhere: the same answer)
+    rc = check_records(c, rec_start, rec_len, n_rec, n); if (rc) return rc;          // (the same records everywhere: the same answer)
     // ---- what a batch needs beside for_record_batches' buffers: the other ranks' hits on rank 0 ----
     const size_t cap = std::min(n_rec, g_hits_recs);               // records per batch
     DevBuf stage;
@@ -325,10 +298,7 @@ extern "C" int katgpu_table_seq_hits_gathered_host(katgpu_comm* comm, katgpu_tab
         }
         return KATGPU_OK;
     };
-    rc = comm_agree_to_start(comm, prepare(), [&](int p, int code) {
-        if (code == KATGPU_ERR_NOMEM) return fail(c, code, "seq hits gathered: rank %d of %d has no device memory for a batch of %zu records", p, world, cap);
-        return fail(c, code, "seq hits gathered: rank %d could not read its table", p);
-    });
+    rc = comm_agree_to_start(comm, prepare(), gathered_peer_error(comm, c, "seq hits gathered", "a batch of %zu records", cap));
     if (rc) return rc;
 
     // ---- the batches.  From here on a rank that fails raises the communicator's abort flag: its peers' waits end (comm_agree_done) ----

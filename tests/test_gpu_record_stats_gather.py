@@ -83,7 +83,8 @@ def _assert_case(path, want_s, want_r, what):
     (2, 27, "plans_nc", 1 << 16, 12, {}),
     (3, 41, "plans", 1 << 16, 20, {"KATGPU_TEST_STATS_SHORT": "20"}),           # records of more than 20 windows go the long way
     (3, 27, "plans", 1 << 23, 8, {"KATGPU_TEST_STATS_BATCH": "700"}),           # several record batches per call
-    (2, 5, "plans", 1 << 16, 0, {})])
+    (2, 5, "plans", 1 << 16, 0, {}),
+    (2, 27, "plans", 1 << 16, 12, {"KATGPU_TEST_STATS_SHORT": "20", "KATGPU_TEST_STATS_BATCH": "700"})])   # the long records' window budget ends batches (last: the rows above keep their ids)
 def test_gathered_statistics_and_regions_are_the_models(tmp_path, world, k, mode, hint, slot, hooks):
     canonical = mode == "plans"
     outs = _launch(tmp_path, world, k, mode, dict(hooks, PROFILE_GATHER_SIZE_HINT=str(hint)))
